@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- AIR train-step throughput on MI355X (the BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--precision bf16|fp32] [--no-graph]
+  python bench.py --gpus N --steps K --warmup W [--precision bf16|fp32] [--no-graph] [--full] [--dump-outputs DIR]
   (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL)
 
 A "step" = one full AIR train step on one batch of synthetic 50x50 multi-object
 canvases resident in HBM: Philox noise + annealing, hoisted x.Wx, 3 x (LSTM,
 heads, glimpse read, VAE, canvas write), ELBO, full backward, weight grads,
 [all-reduce], global-norm clip, TF-style Adam.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds
+everything else: the per-replay spread, per-kernel roofline, inference, fp32, stress
+and backward-order blocks, the CPU baseline, and on several GPUs the all-reduce
+timing and the replica check.  --dump-outputs DIR writes what the last timed step
+computed as DIR/<name>.npy (float32; seeded inputs, identical from run to run).
 """
 import argparse
 import json
@@ -60,6 +66,29 @@ def synthetic_canvases(batch, canvas, max_digits, seed):
             placed += 1
         counts[b] = placed
     return imgs.reshape(batch, canvas * canvas), counts
+
+
+DUMP_MAX_ELEMS = 1 << 22              # per array; larger ones (the stress configuration) are a fixed, seeded sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(model):
+    """What a caller of the train step receives from its last step, as float32 host arrays: the forward's outputs
+    (loss, accuracy, reconstruction, per-item losses, counts, attention) and the variables and gradient it left."""
+    n = model.store.n
+    outs = {"loss": model.loss, "accuracy": model.accuracy, "reconstruction": model.reconstruction,
+            "reconstruction_loss": model.reconstruction_loss, "loss_per_item": model.loss_per_item,
+            "rec_num_digits": model.rec_num_digits, "z_pres_probs": model.z_pres_probs, "rec_scales": model.rec_scales,
+            "rec_shifts": model.rec_shifts, "params": model.store.params, "grads": model.store.grads[:n]}
+    res = {}
+    for k, v in outs.items():
+        a = v.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        res[k] = np.ascontiguousarray(a, dtype=np.float32)
+    assert sum(a.nbytes for a in res.values()) <= DUMP_MAX_BYTES
+    return res
 
 
 def per_kernel_times(model, iters):
@@ -280,14 +309,20 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--graph-steps", type=int, default=100, help="train steps captured per hipGraph replay (1 GPU), at most "
                     "(20 / 50 / 100 / 200 per replay: 0.1785 / 0.1780 / 0.1778 / 0.1776 ms per step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary blocks (fp32 step, stress config, inference)")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement and check (see the module docstring); "
+                    "a plain run does only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary blocks (fp32 step, stress config, inference)")
     ap.add_argument("--backward", default=None,
                     help="sampler-backward order: reference | reference_carried | exact, or a schedule FIRST>SECOND@N (AIRModel(backward=(FIRST, "
                          "SECOND, N))).  Default: what training.py runs (air_model.TRAINING_BACKWARD).  With a schedule the line's "
                          "headline is the step after the switch and `init_phase` holds the step before it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -434,11 +469,12 @@ def main():
             sync()
             assert model.backward == sched[1], model.backward
         dt = timed_region()
+        outs = step_outputs(model) if args.dump_outputs and rank == 0 else None      # before anything below steps the model again
         # ... and the SAME K steps once more, outside the timed region, cut into >= MIN_REPLAYS replays with a HIP event
         # between them: the spread of the step time over the run (min / median / max per replay).  Not the headline: a
         # replay boundary costs ~18 us, which K / 5 steps amortise less well than K.
         spread = None
-        if world == 1 and not args.no_graph:
+        if args.full and world == 1 and not args.no_graph:
             ok = [g for g in range(1, args.steps + 1) if args.steps % g == 0 and args.steps // g >= MIN_REPLAYS]
             if ok:
                 g2 = max(ok)
@@ -458,12 +494,12 @@ def main():
                           "max": round(per[-1], 4), "unit": "ms per step, per replay (HIP events)",
                           "note": "a second pass of the same K steps after the timed region, in shorter replays; `value` is the "
                                   "timed region above (%d steps per replay)" % gsteps}
-        return model, dt, gsteps, mode, spread, init_phase
+        return model, dt, gsteps, mode, spread, init_phase, outs
 
     exchange = os.environ.get("AIR_DP_EXCHANGE") or "flat"
     phase["build_models"] = 0.0
     t_ph = time.perf_counter()
-    model, dt, gsteps, graph_mode, spread, init_phase = build_and_time("air", exchange)
+    model, dt, gsteps, graph_mode, spread, init_phase, outs = build_and_time("air", exchange)
     phase["timed"] = round(dt, 3)
     phase["build_models"] = round(time.perf_counter() - t_ph - dt, 3)      # construction, capture and warm-up
     exchange_runs = {exchange: round(dt / args.steps * 1e3, 4)}
@@ -476,13 +512,17 @@ def main():
         if res is None:
             exchange_runs[other] = "skipped: a rank could not build it"
         else:
-            m2, dt2, g2, mode2, spread2, init2 = res
+            m2, dt2, g2, mode2, spread2, init2, outs2 = res
             exchange_runs[other] = round(dt2 / args.steps * 1e3, 4)
             if dt2 < dt:
-                model, dt, gsteps, graph_mode, exchange, spread, init_phase = m2, dt2, g2, mode2, other, spread2, init2
+                model, dt, gsteps, graph_mode, exchange, spread, init_phase, outs = m2, dt2, g2, mode2, other, spread2, init2, outs2
+    if outs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, a in outs.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
     loss = float(model.loss)
     replicas_identical = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank applied the same all-reduced gradient to the same state: the parameters must be
         # bit-identical across ranks after the run (int64 sum of the raw words, min == max over ranks)
         chk = model.store.params.view(torch.int32).to(torch.int64).sum().reshape(1)
@@ -494,7 +534,7 @@ def main():
     # the step's only collective, timed on its own (all ranks take part): SURVEY 8(e) asks for its
     # duration and bus bandwidth against the 153 GB/s/link xGMI bound
     ar = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             g = model.store.grads
             for _ in range(5):
@@ -541,7 +581,7 @@ def main():
             line["init_phase"] = init_phase
             line["init_phase_ms_per_step"] = init_phase["ms_per_step"]
         t_ph = time.perf_counter()
-        if not args.no_roofline and world == 1:
+        if args.full and not args.no_roofline and world == 1:
             model.release_graph()
             kt = per_kernel_times(model, 20)
             meta = kt.pop("__meta__")
@@ -594,7 +634,7 @@ def main():
                                                                 / MFMA_PEAK_TF[args.precision], 5)}
             line["kernels"] = {k: {"us_per_step": round(v["us"], 2), "launches": v["launches"], "ops": v["ops"]}
                                for k, v in ranked}
-        if not args.no_extras and world == 1:
+        if args.full and not args.no_extras and world == 1:
             # secondary metric of SURVEY 8(d): inference (train=False forward, z_pres rounded) on the same batch
             inf = am.AIRModel(model.input_images, model.target_num_digits, cnn=False, train=False, reuse=True,
                               scope="air", annealing_schedules=ANNEAL, seed=rank, gemm_precision=args.precision, **hp)
@@ -618,7 +658,7 @@ def main():
                                  "us_per_forward_graph": round(us_graph, 1), "us_per_forward_eager": round(us_eager, 1),
                                  "launches": len(inf._fwd) + 1,
                                  "mode": ("one hipGraph replay per forward" if us_graph <= us_eager else "eager launches") + ", train=False"}
-        if not args.no_extras and world == 1 and args.workload == "configs[1]":
+        if args.full and not args.no_extras and world == 1 and args.workload == "configs[1]":
             # the same step at the reference's own precision (fp32 operands, exact-fp32 MFMA) ...
             def secondary(tag, prec, hp2, B2, steps, backward=model.backward):
                 im2, tg2 = synthetic_canvases(B2, hp2["canvas_size"], hp2["max_digits"], seed=2000)
@@ -660,8 +700,9 @@ def main():
                     "configs[3]": (line["stress_configs3"]["ms_per_step"] if mode == model.backward else
                                    secondary("air_stress_" + mode, args.precision, hp3, 256, 40, backward=mode)["ms_per_step"])}
             line["backward_orders"]["unit"] = "ms per step (secondary blocks: 4 steps per replay, 100 / 40 steps)"
-        phase["extras"] = round(time.perf_counter() - t_ph, 3)      # per-kernel events, inference, fp32 and stress blocks
-        if not args.no_cpu_baseline and world == 1 and args.workload == "configs[1]":
+        if args.full:
+            phase["extras"] = round(time.perf_counter() - t_ph, 3)      # per-kernel events, inference, fp32 and stress blocks
+        if args.full and not args.no_cpu_baseline and world == 1 and args.workload == "configs[1]":
             t_ph = time.perf_counter()
             line["cpu_baseline"] = cpu_baseline(B)
             phase["cpu_baseline"] = round(time.perf_counter() - t_ph, 3)

@@ -252,7 +252,7 @@ def test_bench_eight_rank_flow_on_one_device():
         pytest.skip("needs a GPU")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, AIR_BENCH_SAME_DEVICE="1", AIR_BENCH_BACKEND="gloo")
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "10", "--warmup", "2"], cwd=root, env=env,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "10", "--warmup", "2", "--full"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -279,7 +279,7 @@ def test_bench_multi_rank_flow_on_one_device(tmp_path):
         pytest.skip("needs a GPU")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, AIR_BENCH_SAME_DEVICE="1", AIR_BENCH_BACKEND="gloo")
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "12", "--warmup", "4"], cwd=root, env=env,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "12", "--warmup", "4", "--full"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

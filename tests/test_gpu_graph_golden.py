@@ -26,13 +26,16 @@ from oracle.synth import blob_canvases  # noqa: E402
 
 HP = dict(ao.TRAINING_HP)
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "graph_b64.npz")
+GOLD_KERN = os.path.join(os.path.dirname(__file__), "golden", "graph_b64_kern.npz")   # its kern/* vectors (1 MiB per file)
 SEEDS = dict(images=3, params=0, noise=1)            # tests/golden/make_graph_golden.py
 KB, SUB = 16, 2048
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return np.load(GOLD)
+    g = dict(np.load(GOLD))
+    g.update(np.load(GOLD_KERN))
+    return g
 
 
 @pytest.fixture(scope="module")

@@ -1,7 +1,7 @@
 """TensorFlow bundle import/export against the reference's own checkpoint index.
 
-tests/golden/tf_index_listing.json holds the entries of /root/reference/model/air-model.index
-(TensorFlow 1.3, step 270 000; the matching data blob is not in the repository).  It pins
+tests/golden/tf_index_listing.json holds the entries of the reference's model/air-model.index (a copy is
+tests/golden/air-model.index; TensorFlow 1.3, step 270 000; the matching data blob is not in the repository).  It pins
  * the CRC-32C + mask implementation against values TensorFlow itself wrote (scalars whose
    content is known: beta powers underflowed to 0.0, global_step = 270 000),
  * the exporter's layout: the same tensors exported here must land at the same offsets / sizes /
@@ -86,9 +86,10 @@ def test_name_mapping_roundtrip():
         assert np.array_equal(back[k], v) and float(back[k + "/Adam"].ravel()[0]) == 0.5
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/model/air-model.index"), reason="reference not mounted")
 def test_reference_index_parses_to_the_committed_listing():
-    header, entries = tfc.read_index("/root/reference/model/air-model.index", verify=True)
+    path = os.path.join(os.path.dirname(__file__), "golden", "air-model.index")      # the reference's index file, as TF wrote it
+    header, entries = tfc.read_index(path, verify=True)
+    assert os.path.getsize(path) == LISTING["file_bytes"]
     assert json.loads(json.dumps(entries)) == ENTRIES
 
 

@@ -9,7 +9,7 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python3 $root/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-extras "$@" > $out/trace.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python3 $root/bench.py --steps 50 --warmup 5 --full --no-cpu-baseline --no-extras "$@" > $out/trace.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_$c -o pmc -- python3 $root/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-roofline --no-extras --no-graph "$@" > $out/pmc_$c.log 2>&1
 done
