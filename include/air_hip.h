@@ -167,7 +167,9 @@ typedef struct {
     int32_t ksplit;                /* > 1: split K over grid.z; C receives `air_gemm_slabs()` slabs of
                                       [M,ldc] (plain stores, generic epilogue skipped)            */
     int32_t addend_slabs;          /* addend is that many [M,ldadd] slabs (0/1 = one)            */
-    int32_t i0;
+    int32_t i0;                    /* AIR_EPI_LSTM_BWD_TAIL: first row.  AIR_EPI_LSTM_FWD0 with A16, a bit set: bit 1 (value 2) = A16 is the
+                                      PADDED twin and lda ITS row stride (see A16 below); bit 0 (value 1) = with bit 1, stage the operands
+                                      through registers instead of by 16-byte LDS-DMA (gemm_xwx_glds_kernel).  0 = an ordinary twin */
     const float* p0; const float* p1; const float* p2; const float* p3;
     float* q0; float* q1; float* q2;
     /* optional (HOST pointer, read during the call): the step prologue of air_step_begin is run by
@@ -180,7 +182,20 @@ typedef struct {
      * fp32 A) are given and aligned to 16 bytes the operands are read as bf16 (half the bytes through the CU,
      * no conversion; row-major weights through the LDS transpose read).  C16 / q0_16 / q2_16: twins the epilogue
      * writes next to C / q0 / q2 for the next consumer (q2_16 of AIR_EPI_LSTM_BWD: pass it with the LAST
-     * accumulation into q2 only). */
+     * accumulation into q2 only).
+     * AIR_EPI_LSTM_FWD0 (its C, the raw x.Wx, has no consumer that wants a twin) REUSES two of these fields.  Both forms
+     * exist in the bf16-twin kernels only: precision 1, untransposed operands, B16p (16-byte aligned), R = N/4 a
+     * multiple of 8.  A descriptor that asks for one of them and does not meet this is REFUSED with AIR_EALIGN by
+     * air_gemm and by air_gemm_kernel_name -- never served by another kernel:
+     *   - with an fp32 A (A16 == NULL), C16 (nullable, 16-byte aligned) receives the PADDED bf16 twin of A as a side
+     *     output: M rows of ldp = K rounded up to a multiple of 8 elements, element (m, k) = bf16(A[m, k]) (RNE), the
+     *     columns K .. ldp - 1 zero -- every row starts 16-byte aligned although K % 8 != 0.  Also required: A 16-byte
+     *     aligned, lda and K multiples of 4;
+     *   - with A16 != NULL and i0 bit 1 (value 2) set, A16 IS such a padded twin and lda is ITS row stride, not A's (a
+     *     multiple of 8, >= K rounded up to 8; A16 16-byte aligned; the pad columns must be zero): K itself may be
+     *     ragged.  A must still be a valid pointer; it is not read.  C16 is ignored.
+     * Without i0 bit 1 an A16 is an ordinary twin (same leading dimension as A, K % 8 == 0 for the twin kernels).
+     * Results are bit-identical between all forms. */
     const uint16_t* A16; const uint16_t* B16;
     uint16_t* C16; uint16_t* q0_16; uint16_t* q2_16;
     /* PANEL-BLOCKED bf16 twin of an untransposed B = [K, N] (precision 1, nullable; air_panel_t below describes the

@@ -307,7 +307,7 @@ class AIRModel:
                  learning_rate=1e-3, gradient_clipping_norm=100.0, cnn=True, cnn_filters=8,
                  num_summary_images=60, train=False, reuse=False, scope="air",
                  annealing_schedules=None, seed=0, gemm_precision=None, backward="reference", noise_seed=None,
-                 bf16_twins=None, dp_exchange=None, xw_tile=None):
+                 bf16_twins=None, dp_exchange=None, xw_tile=None, xwx_twin_staging="lds_dma"):
         if cnn:
             # reference :510-533; every caller passes cnn=False (training.py:108, demo.py:24)
             raise NotImplementedError("cnn=True front-end is outside the accelerated hot path; pass cnn=False")
@@ -439,6 +439,13 @@ class AIRModel:
         # ONE rank -- all a 1-GPU box can give RCCL -- so that its captured form is exercised on hardware
         self._dp_force = os.environ.get("AIR_DP_FORCE") == "1"
         self._injected_noise = False
+        # how the twin-operand x.Wx launch stages its panels: "lds_dma" (gemm_xwx_glds_kernel) or "registers" (the same
+        # operands through VGPRs and ds_write, air_gemm_t.i0 bit 0): an A/B handle for the tools, results are bit-identical
+        if xwx_twin_staging not in ("lds_dma", "registers"):
+            raise ValueError("xwx_twin_staging must be 'lds_dma' or 'registers'")
+        self._xwx_twin_staging = xwx_twin_staging
+        self._graph_xwx = []
+        self._last_xwx_op = None
         self._graph = None
         self._dirty = True
         self._steps_executed = None
@@ -557,6 +564,7 @@ class AIRModel:
         self._zs16_pad = h16(N, B, self._zs_ld)
         self.gen_act16 = [h16(N, B, u) for u in self.vae_generative_units]
         self.images16 = None
+        self.images16p = None
         if self.train:
             self.d_genpre16 = h16(N, B, d)
             self.d_gen16 = [h16(N, B, u) for u in self.vae_generative_units]
@@ -567,6 +575,10 @@ class AIRModel:
             self.dgsum16 = h16(B, 4 * R)
             # twin of the image batch (the caller's fp32 tensor): written by the step prologue, read by the input-weight gradient
             self.images16 = h16(B, D)
+            # a SECOND twin of the batch with rows padded to a multiple of 8 elements (every row 16-byte aligned, pad
+            # columns zero): side output of the fp32-operand x.Wx launch, A operand of the x.Wx launches that follow it
+            # inside one captured replay (capture_graph)
+            self.images16p = h16(B, (D + 7) & ~7)
         if self.train:
             self.d_recon = f(B, D)
             self.d_genpre = f(N, B, d)
@@ -603,7 +615,8 @@ class AIRModel:
         return _Op("%s[%dx%dx%d%s]" % (tag, M, N, K, "t" if ta else ("n" + ("t" if tb else "n"))),
                    lambda s, g=g, fn=fn, keep=step_job: H.check(fn(C.byref(g), s), "air_gemm"),
                    nbytes=(2 if A16 is not None else 4) * M * K + (2 if (B16 is not None or B16p is not None) else 4) * K * N
-                   + 4 * M * N * (1 + extra) + (2 * M * N if C16 is not None else 0) + (4 * N if bias is not None else 0) + extra_bytes,
+                   + 4 * M * N * (1 + extra) + (0 if C16 is None else 2 * M * (((K + 7) & ~7) if epi == H.EPI_LSTM_FWD0 else N))
+                   + (4 * N if bias is not None else 0) + extra_bytes,
                    flops=2 * M * N * K, kernel=kbuf.value.decode())
 
     _KERNEL_OF = {"air_lstm_first_step": "lstm_first_step_kernel", "air_step_begin": "step_begin_kernel", "air_attend_fwd": "attend_fwd_kernel",
@@ -649,6 +662,7 @@ class AIRModel:
 
         NB = N * B
         fwd = []
+        self._xwx_twin_op = None
 
         def gemm(*args, **kw):
             fwd.append(self._gemm(*args, **kw))
@@ -672,7 +686,18 @@ class AIRModel:
             step0 = dict(bias=P["lstm_bias"], epi=H.EPI_LSTM_FWD0, q=(self.acts[0], self.c[1], self.h[1]),
                          extra_bytes=4 * B * R * 6, q2_16=o16(self.h16, 1), B16p=wx_pan,
                          B16=(Wx16 if (wx_pan is None and not st.wx_exclusive) else None))
-            fwd.append(self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R, tag="xWx+lstm0", **step0))
+            # (panel twin + train: the launch also leaves the padded bf16 twin of the batch behind -- air_gemm_t.C16 of this
+            # epilogue -- and a second op reads it in place of the fp32 batch: capture_graph decides where that is allowed)
+            # Only the bf16-twin kernel of this launch writes the twin, and only it has the twin-operand form (R % 8 == 0, a
+            # 16-byte aligned batch, ...: twin_rounds in csrc/air_gemm_bf16.hip).  The library is asked, not second-guessed:
+            # the plain descriptor is built first, and the twin is offered only where THAT dispatches to the twin kernel.
+            op0 = self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R, tag="xWx+lstm0", **step0)
+            if wx_pan is not None and self.train and op0.kernel.startswith("gemm_bf16tw_kernel<1, 1, false, %d, true," % H.EPI_LSTM_FWD0):
+                x16p = self.images16p
+                op0 = self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R, tag="xWx+lstm0", C16=x16p, **step0)
+                self._xwx_twin_op = self._gemm(imgs, Wx, self.xw, B, 4 * R, D, x16p.shape[1], 4 * R, 4 * R, tag="xWx16+lstm0",
+                                               A16=x16p, i0=(3 if self._xwx_twin_staging == "registers" else 2), **step0)
+            fwd.append(op0)
             step0["extra_bytes"] += noise_bytes
             self._begin_host = (0, self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R,
                                               tag="xWx+lstm0+step_begin", step_job=job, **step0))
@@ -1003,16 +1028,24 @@ class AIRModel:
         if self._twins and self.store.shadow_stale:
             self.store.refresh_shadow(self._stream())
 
-    def _run_forward(self, s, finalize=True):
+    def _run_forward(self, s, finalize=True, twin_x=False):
+        """twin_x: x.Wx reads the padded bf16 twin of the image batch.  Only capture_graph may ask for it, and only for a
+        step whose predecessor in the SAME replay ran the fp32-operand launch over the same, untouched batch."""
         self._fresh_shadow()
+        fwd = self._fwd
+        if twin_x:
+            if self._xwx_twin_op is None:
+                raise RuntimeError("this model has no twin-operand x.Wx launch")
+            fwd = [self._xwx_twin_op] + fwd[1:]
         if self._injected_noise:
             self._begin_sched_only(s)                # (parity tests: the schedules only, the noise buffers hold what was injected)
-            for op in self._fwd:
-                op(s)
+            run = list(fwd)
         else:
             hi, hop = self._begin_host               # the launch that carries the step prologue as extra workgroups
-            for i, op in enumerate(self._fwd):
-                (hop if i == hi else op)(s)
+            run = [(hop if i == hi else op) for i, op in enumerate(fwd)]
+        self._last_xwx_op = run[0]                   # (what capture_graph records: the op that WAS enqueued)
+        for op in run:
+            op(s)
         if finalize:
             self._finalize(s)
 
@@ -1144,14 +1177,25 @@ class AIRModel:
         self._wgrad_plain(s)
 
     def train_step_ops(self):
-        """The launches of one single-GPU train step, in order (bench / profiling tools)."""
+        """The launches of one single-GPU train step, in order (bench / profiling tools): the EAGER step, whose x.Wx reads
+        the caller's fp32 image batch.  Steps 1 .. G-1 of a captured G-step replay without a between_steps hook run the same
+        list with the twin-operand x.Wx launch (gemm_xwx_glds_kernel, captured_xwx_kernels()) in its first place."""
         hi, hop = self._begin_host
         return ([(hop if i == hi else op) for i, op in enumerate(self._fwd)] + [self._write_bwd_fin] + self._bwd[1:]
                 + [self._wgrad_fused] + self._optimizer_ops())
 
-    def _train_phase_a(self, s):
+    def captured_xwx_kernels(self):
+        """Kernel name of the x.Wx launch of every step of the captured replay, in order (None: no train graph): the names
+        of the ops that were enqueued under capture (captured_xwx_ops())."""
+        ops = self.captured_xwx_ops()
+        return None if ops is None else [op.kernel for op in ops]
+
+    def captured_xwx_ops(self):
+        return None if self._graph is None or not self.train else list(self._graph_xwx)
+
+    def _train_phase_a(self, s, twin_x=False):
         """step prologue + forward + loss + backward (+ weight grads) into the flat grad buffer"""
-        self._run_forward(s, finalize=False)
+        self._run_forward(s, finalize=False, twin_x=twin_x)
         self._run_backward(s, for_update=True, fused_finalize=True)
 
     def _train_phase_b(self, s):
@@ -1201,6 +1245,12 @@ class AIRModel:
                     self._dp_factors()["dwx"](s)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        # Step 0 of a replay reads the caller's fp32 image batch (the host may have rewritten it since the last replay) and
+        # leaves its padded bf16 twin behind; nothing inside the graph writes the batch unless a between_steps hook does, so
+        # the steps behind it read the twin: half the A bytes of x.Wx, both operands by LDS-DMA.  (Not where the x.Wx launch
+        # itself carries the step prologue -- max_steps == 1: that launch is the fp32-operand one.)
+        can_twin = between_steps is None and self._xwx_twin_op is not None and self._begin_host[0] != 0
+        xwx = []
         ga = torch.cuda.CUDAGraph()
         # (thread_local: RCCL's watchdog thread may touch the runtime while this thread captures)
         with torch.cuda.graph(ga, **({"capture_error_mode": "thread_local"} if dp else {})):
@@ -1208,7 +1258,9 @@ class AIRModel:
                 if between_steps is not None:
                     between_steps(i)
                 s = self._stream()
-                self._train_phase_a(s)
+                twin_x = i >= 1 and can_twin
+                self._train_phase_a(s, twin_x=twin_x)
+                xwx.append(self._last_xwx_op)
                 if not dp:
                     self._train_phase_b(s)
                 elif in_graph:
@@ -1224,6 +1276,7 @@ class AIRModel:
             with torch.cuda.graph(gb):
                 self._train_phase_b(self._stream())
         self._graph = (ga, gb)
+        self._graph_xwx = xwx
         self._graph_dp = (dp, in_graph)
         return self
 

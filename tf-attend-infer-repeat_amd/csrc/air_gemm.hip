@@ -36,6 +36,7 @@ namespace airg {
 int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb);
 int twin_launch(const Args& a, int tm, int tn, bool tb, dim3 grid, hipStream_t s);
 void twin_kernel_name(const Args& a, int tm, int tn, bool tb, char* buf, int n);
+bool fwd0_padded(const Args& a);
 int xw_tp_ok(const Args& a, int precision, bool ta, bool tb, int ksplit);
 int xw_tp_launch(const Args& a, int job_planes_hint, hipStream_t s);
 int xw_tp_columns(const Args& a);
@@ -880,6 +881,10 @@ int launch(const air_gemm_t* g, const Args& a0, hipStream_t s) {
     a.slab_stride = (long)a.M * a.ldc;
     // bf16 twins of the operands supplied and this (tile, epilogue, layout) exists as a twin kernel
     if (g->precision == 1 && !TA && twin_rounds(a, TM, TN, false, TB) > 0) return twin_launch(a, TM, TN, TB, grid, s);
+    // AIR_EPI_LSTM_FWD0's C16 is the padded image twin only the twin kernels write (air_hip.h): nobody else may be asked for it
+    if (a.epi == AIR_EPI_LSTM_FWD0 && a.C16) return AIR_EALIGN;
+    // ... and a PADDED A16 (i0 bit 1) redefines lda as the twin's stride: the kernels below would read the fp32 A with it
+    if (fwd0_padded(a)) return AIR_EALIGN;
     // the lean kernels are instantiated per epilogue; a fused epilogue exists for its one tile shape
     // (resolve_tile) -- any other combination would be a dispatch bug
     constexpr bool T14 = TM == 1 && TN == 4, T12 = TM == 1 && TN == 2, T11 = TM == 1 && TN == 1;
@@ -1035,6 +1040,8 @@ extern "C" int air_gemm_kernel_name(const air_gemm_t* g, char* buf, int n) {
         twin_kernel_name(a, tm, tn, tb, buf, n);
         return 0;
     }
+    // what only the twin kernels serve (launch<> refuses the same descriptors): the padded image twin, in or out
+    if (a.epi == AIR_EPI_LSTM_FWD0 && (a.C16 || fwd0_padded(a))) return AIR_EALIGN;
     if (g->precision == 1 && use_bf16_v2(a, ta, tb))
         snprintf(buf, n, "gemm_bf16v2_kernel<%d, %d, %s, %d>", tm, tn, tb ? "true" : "false", g->epi);
     else if (g->precision == 0 && use_bf16_v2(a, ta, tb)) {

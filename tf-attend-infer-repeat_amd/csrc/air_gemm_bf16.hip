@@ -20,7 +20,10 @@
 // The rounding is the RNE the other kernel applies on the way into LDS, accumulation order over k,
 // cross-wave reduction and epilogues are shared code (air_gemm_common.h): results are bit-identical to
 // the fp32-operand bf16 path (tests/test_gpu_kernels.py::test_gemm_bf16_twins_bit_identical).
-// A may stay fp32 (AF32: the hoisted x.Wx reads the caller's fp32 image batch).
+// A may stay fp32 (AF32: the hoisted x.Wx reads the caller's fp32 image batch).  That launch can leave a PADDED bf16
+// twin of the batch behind (row stride K rounded up to 8 elements: every row starts 16-byte aligned, pad columns
+// zero); the x.Wx launches that follow it over the same batch read the twin -- half the A bytes -- and fill both LDS
+// images by 16-byte LDS-DMA (gemm_xwx_glds_kernel below).
 #include "air_gemm_common.h"
 #include <atomic>
 #include <cstdlib>
@@ -103,10 +106,17 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
     constexpr int TBK_N = (R * BN * 8 + THREADS - 1) / THREADS;
     constexpr int TBN_N = (R * KB * (BN / 8) + THREADS - 1) / THREADS;
     constexpr int TBQ_N = (R * KB * 4 + THREADS - 1) / THREADS;           // QUAD: (image, k, gate) -> 8 bytes = 4 units
+    // x.Wx on the gate-interleaved PANEL twin: the tile's block is contiguous, so it travels in 16-byte pieces of two gates
+    // (half the load instructions, the same bytes in the same registers: piece i = vq[2 i], vq[2 i + 1]); wave-uniform
+    const bool quad16 = EPI_ == AIR_EPI_LSTM_FWD0 && pnl;
+    constexpr int TBQ16_N = (TBQ_N + 1) / 2;
     uint4 va[AF32 ? 1 : TA_N];
     float4 vaf[AF32 ? TA_N : 1];
     uint4 vb[QUAD ? 1 : (TB ? TBK_N : TBN_N)];
-    uint2 vq[QUAD ? TBQ_N : 1];
+    uint2 vq[QUAD ? 2 * TBQ16_N : 1];
+    // AF32 x.Wx: the workgroups of column panel 0 leave their rows behind as the padded bf16 twin (a.C16, row stride ldt)
+    const bool twin_out = AF32 && EPI_ == AIR_EPI_LSTM_FWD0 && a.C16 != nullptr && tile_n == 0;
+    const int ldt = (a.K + 7) & ~7;
 
     auto issue_loads = [&](int kr) __attribute__((always_inline)) {
         if (AF32) {
@@ -128,7 +138,16 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
                 va[i] = ldg16u(Ab, ((unsigned)gm * (unsigned)a.lda + (unsigned)gk) * 2u, ok);
             }
         }
-        if (QUAD) {
+        if (QUAD && quad16) {
+#pragma unroll
+            for (int i = 0; i < TBQ16_N; ++i) {
+                const int t = tid + THREADS * i;
+                const int gk = kr + (t >> 1);
+                const bool ok = (t < R * KB * 2) && n0 < a.gwidth && gk < kend;
+                const uint4 v = ldg16u(Bb, ((unsigned)(n0 >> 2) * pK16 + (unsigned)kr * 16u) * 2u + (unsigned)t * 16u, ok);
+                vq[2 * i] = make_uint2(v.x, v.y); vq[2 * i + 1] = make_uint2(v.z, v.w);
+            }
+        } else if (QUAD) {
 #pragma unroll
             for (int i = 0; i < TBQ_N; ++i) {
                 const int t = tid + THREADS * i;
@@ -169,7 +188,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
     // In-kernel stamps: the issue phase of the K = 256 kernels 0.84 -> 0.56 us, nothing at K = 784, and the in-graph
     // launch times did not move (the phase is bound by the CU's vector-memory path -- 64 B/clk, and a 16-column tile
     // uses 32 bytes of every 128-byte line of a row-major weight -- not by its ~15 VALU instructions per piece))
-    auto store_images = [&](int) __attribute__((always_inline)) {
+    auto store_images = [&](int kr) __attribute__((always_inline)) {
         if (AF32) {
 #pragma unroll
             for (int i = 0; i < TA_N; ++i) {
@@ -179,6 +198,11 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
                 w.x = pack_bf16(vaf[i].x, vaf[i].y); w.y = pack_bf16(vaf[i].z, vaf[i].w);
                 if (u < R * BM * 16)
                     *reinterpret_cast<uint2*>(&ImgA[(c * BM + row) * KB + (((hh >> 1) ^ (row & 7)) << 3) + (hh & 1) * 4]) = w;
+                if (twin_out) {                       // (block-uniform) columns K .. ldt - 1 were loaded as zeros: the pad
+                    const int gm = m0 + row, gk = kr + c * KB + hh * 4;
+                    if (u < R * BM * 16 && gm < a.M && gk < ldt)
+                        *reinterpret_cast<uint2*>(&a.C16[(size_t)gm * ldt + gk]) = w;
+                }
             }
         } else {
 #pragma unroll
@@ -188,7 +212,14 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
                 if (u < R * BM * 8) *reinterpret_cast<uint4*>(&ImgA[(c * BM + row) * KB + ((g ^ (row & 7)) << 3)]) = va[i];
             }
         }
-        if (QUAD) {
+        if (QUAD && quad16) {
+#pragma unroll
+            for (int i = 0; i < TBQ16_N; ++i) {
+                const int t = tid + THREADS * i;
+                if (t < R * KB * 2)                                                         // the same image, two gates a piece
+                    *reinterpret_cast<uint4*>(&ImgB[t * 8]) = make_uint4(vq[2 * i].x, vq[2 * i].y, vq[2 * i + 1].x, vq[2 * i + 1].y);
+            }
+        } else if (QUAD) {
 #pragma unroll
             for (int i = 0; i < TBQ_N; ++i) {
                 const int t = tid + THREADS * i;
@@ -425,6 +456,133 @@ __global__ __launch_bounds__(THREADS) void gemm_xw_tp_kernel(Args a)
                 Cz[(size_t)(m0 + wm + i * 16 + (lane >> 4) * 4 + q) * a.ldc + n0 + wn + j * 16 + (lane & 15)] = acc[i][j][q];
 }
 
+// ---------------------------------------------------------------------------
+// The hoisted x.Wx + first LSTM step over the PADDED bf16 twin of the image batch (a.A16, row stride a.lda a
+// multiple of 8 elements) and the gate-interleaved panel twin of Wx (a.B16p): the 16 x 16 tile, the 64-deep images,
+// the image -> wave map, the reduction and the epilogue of gemm_bf16tw_kernel<1, 1, false, AIR_EPI_LSTM_FWD0, .., R>,
+// with both LDS images filled by 16-byte LDS-DMA (global_load_lds_dwordx4: no staging VGPR, no ds_write pass).
+// An LDS-DMA wave instruction writes 64 x 16 bytes lane-linear from a wave-uniform base, so
+//   * B: the tile's panel block [k][gate][4 units] is contiguous in memory and its image is that block: piece t of a
+//     round goes to byte 16 t;
+//   * A: the image is [row][64 k] with the 16-byte slots of a row XOR-swizzled by row & 7.  Piece u = (image, row,
+//     slot g) is WRITTEN at byte 16 u and FETCHES slot g ^ (row & 7) of its row -- a permutation inside one 128-byte
+//     line, the same involution the fragment reads apply (tests/test_xwx_twin_swizzle.py);
+//   * a piece outside the matrix (rows >= M, k >= K) is not fetched: its lane writes the zeros itself (ds_write), so
+//     the images hold what register staging puts there.
+// One barrier per round; __syncthreads() waits for the fills (they count on vmcnt).
+// ---------------------------------------------------------------------------
+template <int R>
+__global__ __launch_bounds__(THREADS) void gemm_xwx_glds_kernel(Args a)
+{
+    using Cfg = TwCfg<1, 1, R>;
+    constexpr int BM = 16, BN = 16, KB = 64;
+    constexpr int EPI_ = AIR_EPI_LSTM_FWD0;
+    extern __shared__ __attribute__((aligned(16))) unsigned char Lds[];   // Cfg::BYTES
+    unsigned short* ImgA = reinterpret_cast<unsigned short*>(Lds);       // [R][16][64], slots swizzled by row
+    unsigned short* ImgB = ImgA + R * BM * KB;                           // [R][64][4 gates][4 units]
+    float* Red = reinterpret_cast<float*>(Lds);
+    typedef __attribute__((address_space(3))) unsigned char lds_u8;
+    typedef const __attribute__((address_space(1))) unsigned char glb_u8;
+
+    if ((int)blockIdx.z < a.job_on) {                    // the prologue's planes of workgroups (dispatched first)
+        const long plane = (long)gridDim.x * gridDim.y;
+        air_step_job_run(a.job, blockIdx.z * plane + (long)blockIdx.y * gridDim.x + blockIdx.x, plane * a.job_on);
+        return;
+    }
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int tile_m, tile_n;
+    xcd_tile(tile_m, tile_n);
+    const int m0 = tile_m * BM, n0 = tile_n * 4;
+    const int kbeg = 0, kend = a.K;                      // one slab (twin_rounds)
+
+    f32x4 acc[1][1];
+    acc[0][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    Pre<1, 1> pre;
+
+    const char* Ab = reinterpret_cast<const char*>(a.A16);
+    const char* Bb = reinterpret_cast<const char*>(a.B16p) + (size_t)(n0 >> 2) * (size_t)a.K * 32u;
+    constexpr int TA_N = R * BM * 8 / THREADS, TB_N = R * KB * 2 / THREADS;
+    static_assert((R * BM * 8) % THREADS == 0 && (R * KB * 2) % THREADS == 0, "whole passes of 16-byte pieces");
+    lds_u8* const lA = (lds_u8*)Lds;
+    lds_u8* const lB = lA + R * BM * KB * 2;
+    const uint4 zero4 = make_uint4(0u, 0u, 0u, 0u);
+    // a pass = 256 pieces = two images of A / 128 k of B; what a thread fetches differs from pass to pass by a constant
+    const int arow = (tid >> 3) & 15, asg = (tid & 7) ^ (arow & 7);       // (u / 8) % 16, and the slot FETCHED for slot u & 7
+    const int ka = (tid >> 7) * KB + asg * 8, kb = tid >> 1;              // this thread's k within a pass
+    const bool arow_ok = m0 + arow < a.M;
+    const int lim_a = arow_ok ? kend : 0, lim_b = n0 < a.gwidth ? kend : 0;
+    const char* const pa = Ab + ((size_t)(arow_ok ? m0 + arow : 0) * (size_t)a.lda + (size_t)ka) * 2u;
+    const char* const pb = Bb + tid * 16;
+    const int wbase = __builtin_amdgcn_readfirstlane(wave) * 1024;        // the wave's 64 x 16 bytes of a pass (scalar: it goes to M0)
+
+    // the zeros first, all of them, then the fills: a ds_write behind an LDS-DMA in flight would wait for it (vmcnt(0))
+    auto fill_images = [&](int kr) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < TA_N; ++i)
+            if (__builtin_expect(!(kr + 2 * KB * i + ka < lim_a), 0)) *reinterpret_cast<uint4*>(&ImgA[(tid + THREADS * i) * 8]) = zero4;
+#pragma unroll
+        for (int i = 0; i < TB_N; ++i)
+            if (__builtin_expect(!(kr + 2 * KB * i + kb < lim_b), 0)) *reinterpret_cast<uint4*>(&ImgB[(tid + THREADS * i) * 8]) = zero4;
+#pragma unroll
+        for (int i = 0; i < TA_N; ++i)
+            if (__builtin_expect(kr + 2 * KB * i + ka < lim_a, 1))
+                __builtin_amdgcn_global_load_lds((glb_u8*)(pa + (size_t)(kr + 2 * KB * i) * 2u), lA + wbase + THREADS * 16 * i, 16, 0, 0);
+#pragma unroll
+        for (int i = 0; i < TB_N; ++i)
+            if (__builtin_expect(kr + 2 * KB * i + kb < lim_b, 1))
+                __builtin_amdgcn_global_load_lds((glb_u8*)(pb + (size_t)(kr + 2 * KB * i) * 32u), lB + wbase + THREADS * 16 * i, 16, 0, 0);
+    };
+
+    AIR_STAMP(56);
+    fill_images(kbeg);
+    epilogue_prefetch<1, 1, EPI_>(a, pre, m0, n0, lane, wave);
+    AIR_STAMP(57);
+    for (int kr = kbeg; kr < kend; kr += R * KB) {
+        if (kr > kbeg) { __syncthreads(); fill_images(kr); }              // images of the previous round consumed
+        __syncthreads();
+        AIR_STAMP(58);
+        // ---- MFMAs: wave w owns the images whose index within the slab is w (mod 4), whatever R is
+        const int cfirst = (wave - ((kr - kbeg) / KB)) & 3;
+#pragma unroll
+        for (int cc = 0; cc < (R + 3) / 4; ++cc) {
+            const int c = cfirst + 4 * cc;
+            if (c < R && kr + c * KB < kend) {
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    const int slot = ks * 4 + (lane >> 4);
+                    const int row = lane & 15;
+                    const bf16x8 av = *reinterpret_cast<const bf16x8*>(&ImgA[(c * BM + row) * KB + ((slot ^ (row & 7)) << 3)]);
+                    const int il = lane & 15;
+                    const unsigned short* blk = &ImgB[(c * KB + ks * 32 + (lane >> 4) * 8 + (il >> 2)) * BN + (il & 3) * 4];
+                    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk));
+                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + 4 * BN));
+                    const bf16x8 bv = bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[0][0], 0, 0, 0);
+                }
+            }
+        }
+        if (R >= 40) break;                                               // (twin_rounds: 40 images are the whole contraction)
+    }
+    AIR_STAMP(59);
+    __syncthreads();                                                      // Red aliases the images
+    reduce_waves<1, 1>(acc, Red, lane, wave);
+    AIR_STAMP(60);
+    epilogue<1, 1, EPI_>(a, pre, Red, m0, n0, lane, wave);
+    AIR_STAMP(61);
+}
+
+template <int R>
+int launch_glds(const Args& a, dim3 grid, hipStream_t s) {
+    using Cfg = TwCfg<1, 1, R>;
+    auto kern = gemm_xwx_glds_kernel<R>;
+    const int rc = air_grant_lds(reinterpret_cast<const void*>(kern), Cfg::BYTES);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(THREADS), Cfg::BYTES, s, a);
+    AIR_CHECK_LAUNCH();
+    return 0;
+}
+
 template <int TM, int TN, bool TB, int EPI_, bool AF32, int R>
 int launch_one(const Args& a, dim3 grid, hipStream_t s) {
     using Cfg = TwCfg<TM, TN, R>;
@@ -442,6 +600,12 @@ int images_of(const Args& a) { return (a.kslab + 63) / 64; }
 
 namespace airg {
 
+// AIR_EPI_LSTM_FWD0 with A16 and air_gemm_t.i0 bit 1: A16 is the PADDED twin of the batch and lda ITS row stride, not A's --
+// no fp32-operand kernel may serve such a descriptor (air_gemm.hip refuses it where twin_rounds() is 0).  Bit 0 of i0
+// then keeps register staging; the launch and its reported name both ask here.
+bool fwd0_padded(const Args& a) { return a.epi == AIR_EPI_LSTM_FWD0 && a.A16 != nullptr && (a.i0 & 2) != 0; }
+bool fwd0_glds(const Args& a) { return fwd0_padded(a) && (a.i0 & 1) == 0; }
+
 // Which (tile, epilogue, layout) combinations exist as twin kernels, and with how many images per round.
 // Returns R (> 0) or 0 when this descriptor has to take the fp32-operand kernels.
 int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb) {
@@ -452,7 +616,12 @@ int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb) {
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const bool af32 = a.A16 == nullptr;
     // whole 16-byte pieces only: the ragged shapes keep the fp32-operand kernels
-    if (af32) { if (!al16(a.A) || (a.lda & 3) || (a.K & 3) || (a.kslab & 3)) return 0; }
+    // (the twin-A x.Wx may read a PADDED twin -- air_gemm_t.i0 bit 1 says so; without it A16 is an ordinary twin with the
+    // leading dimension of A.  K itself may then be ragged: the 16-byte piece that straddles it ends inside the row's zero
+    // pad -- lda >= K rounded up to 8 -- and the panel twin of B is addressed by the true K)
+    const bool padded = fwd0_padded(a);
+    if (af32) { if (!al16(a.A) || (a.lda & 3) || (a.K & 3) || (a.kslab & 3) || (a.epi == AIR_EPI_LSTM_FWD0 && !al16(a.C16))) return 0; }
+    else if (padded) { if (!al16(a.A16) || (a.lda & 7) || a.lda < ((a.K + 7) & ~7) || !pnl_tile || tb) return 0; }
     else if (!al16(a.A16) || (a.lda & 7) || (a.K & 7) || (a.kslab & 7)) return 0;
     if (pnl_tile) { if (!al16(a.B16p)) return 0; }
     else if (!al16(a.B16) || (a.ldb & 7)) return 0;
@@ -483,8 +652,15 @@ int twin_launch(const Args& a, int tm, int tn, bool tb, dim3 grid, hipStream_t s
     const int e = a.epi;
 #define TW(TM_, TN_, TB_, EPI__, AF_, R_) return launch_one<TM_, TN_, TB_, EPI__, AF_, R_>(a, grid, s)
     if (tm == 1 && tn == 1 && e == AIR_EPI_LSTM_FWD0) {
-        if (r == 40) { if (af32) TW(1, 1, false, AIR_EPI_LSTM_FWD0, true, 40); TW(1, 1, false, AIR_EPI_LSTM_FWD0, false, 40); }
+        // padded twin A: LDS-DMA staging unless air_gemm_t.i0 bit 0 keeps the register staging of the same operands (A/B arm)
+        const bool glds = fwd0_glds(a);
+        if (r == 40) {
+            if (af32) TW(1, 1, false, AIR_EPI_LSTM_FWD0, true, 40);
+            if (glds) return launch_glds<40>(a, grid, s);
+            TW(1, 1, false, AIR_EPI_LSTM_FWD0, false, 40);
+        }
         if (af32) TW(1, 1, false, AIR_EPI_LSTM_FWD0, true, 16);
+        if (glds) return launch_glds<16>(a, grid, s);
         TW(1, 1, false, AIR_EPI_LSTM_FWD0, false, 16);
     }
     if (tm == 1 && tn == 1) {
@@ -563,6 +739,10 @@ int xw_tp_launch(const Args& a0, int job_planes_hint, hipStream_t s) {
 void twin_kernel_name(const Args& a, int tm, int tn, bool tb, char* buf, int n) {
     if (tm == 1 && tn == 4 && (a.gwidth & 3) == 0) {
         snprintf(buf, n, "gemm_bf16tw_kernel<1, 1, false, %d, false, 4>", EPI_LSTM_FWD_Q);
+        return;
+    }
+    if (tm == 1 && tn == 1 && fwd0_glds(a)) {
+        snprintf(buf, n, "gemm_xwx_glds_kernel<%d>", twin_rounds(a, tm, tn, false, tb));
         return;
     }
     if (tm == 1 && tn == 1 && a.epi == AIR_EPI_LSTM_FWD0) {
