@@ -568,6 +568,59 @@ typedef struct {
 int air_summaries_count(int N, int max_digits);
 int air_summaries(const air_summaries_t* a, void* stream);
 
+/* ---- generation: scenes from the priors, or from latents the caller supplies (additive to ABI 5) -----------------
+ * The generative half of the reference's loop body with the posterior heads replaced by the priors: no image, no LSTM, no
+ * recognition network.  Three launches around the decoder GEMMs (air_gemm with the forward's descriptors: the generative
+ * layers, then gen_mean with AIR_ACT_SIGMOID_NOISE, vae.py:26-41):
+ *   air_philox_fill -> air_scene_records -> [air_gemm ...] -> air_render.
+ *
+ * air_scene_records: ONE launch writes the att records of all (step, image) pairs and the latents the first generative
+ * GEMM reads.  given == 0 (sample): the four sources are NOISE, eps_scale [N,B], eps_shift [N,B,2], eps_z [N,B,Z] ~ N(0,1)
+ * and u [N,B] ~ U[0,1), and
+ *   scale = sigmoid(SCALE_PM + sqrt(SCALE_PV) * eps)         (air_model.py:300-303 on the prior of :441-447)
+ *   shift = tanh(SHIFT_PM + sqrt(SHIFT_PV) * eps)            (:317-320, :460-466)
+ *   z_what = VAE_PM + sqrt(VAE_PV) * eps                     (vae.py:22-24 on the prior of air_model.py:479-485)
+ *   z_pres = round(sigmoid((PRIOR_LOG_ODDS + log(u + 1e-9) - log(1 - u + 1e-9)) / TEMPERATURE))
+ *            (concrete.py:20-27 on the prior the KL of air_model.py:398-407 is taken against, rounded as :389-390)
+ * with the prior parameters read from the live `dyn` slots.  given != 0: the sources ARE scales [N,B], shifts [N,B,2],
+ * latents [N,B,Z] and z_pres [N,B] (used as given: it may be relaxed); AIR_ATT_ZPRE is 0.  Either way the stopping sum is
+ * re-derived per image in step order (:409-427: S += 1 - z_pres; MASK_PREV / MASK = S < STOP_THRESHOLD before / after),
+ * AIR_ATT_ST_BACK is (1/s, -x/s, -y/s, 0) (:353-356), and AIR_ATT_ZPROB and the four KL slots are 0.
+ * z [N,B,ldz] (ldz >= Z; columns Z .. ldz-1 are written as 0) and its bf16 twin z16 (nullable, same stride). */
+#define AIR_MAX_STEPS 16
+typedef struct {
+    const float* scale_src;              /* [N,B]   eps_scale | scales   */
+    const float* shift_src;              /* [N,B,2] eps_shift | shifts   */
+    const float* z_src;                  /* [N,B,Z] eps_z     | latents  */
+    const float* pres_src;               /* [N,B]   u         | z_pres   */
+    const float* dyn;                    /* AIR_DYN_* device array       */
+    float* att;                          /* [N,B,AIR_ATT_STRIDE], 16-byte aligned */
+    float* z;                            /* [N,B,ldz]                    */
+    uint16_t* z16;                       /* bf16 twin of z (nullable)    */
+    int32_t B, N, Z, ldz, given;
+} air_scene_records_t;
+int air_scene_records(const air_scene_records_t* a, void* stream);
+
+/* air_render: the compose kernel without a loss -- canvas [B,C*C] = clip(sum_t [MASK_t] z_pres_t *
+ * transformer(window_t, theta_recon_t, [C,C]), 0, 1) in step order (air_model.py:351-366, 429-439, 582), num_digits [B] =
+ * sum_t MASK_t (:427), from the records `att` and the decoded windows vrec [N,B,w*w].  One workgroup per image; the
+ * per-pixel arithmetic IS air_write_fwd's (shared device code): on the same att / vrec the canvas equals its `recon` bit
+ * for bit.  N <= AIR_MAX_STEPS; the taps and windows of one image live in LDS (<= 160 KB: AIR_ELIMIT beyond). */
+typedef struct {
+    const float* vrec;                   /* [N,B,w*w]                    */
+    const float* att;                    /* [N,B,AIR_ATT_STRIDE]         */
+    float* canvas;                       /* [B,C*C]                      */
+    int32_t* num_digits;                 /* [B]                          */
+    int32_t B, N, C, w;
+} air_render_t;
+int air_render(const air_render_t* a, void* stream);
+
+/* normals[n_normal] ~ N(0,1), uniforms[n_uniform] ~ U[0,1) from the generator of air_step_begin, Philox4x32-10(key = seed,
+ * counter = (index, call)) under a salt of its own: no schedules, no global_step (a test model's never moves) -- the
+ * caller counts its calls.  The same (seed, call) gives the same numbers; either count may be 0, not both. */
+int air_philox_fill(float* normals, int64_t n_normal, float* uniforms, int64_t n_uniform,
+                    uint64_t seed, uint64_t call, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

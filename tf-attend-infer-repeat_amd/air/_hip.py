@@ -128,6 +128,18 @@ class Summaries(C.Structure):
                 ("out", _p), ("B", _i), ("N", _i), ("max_digits", _i)]
 
 
+class SceneRecords(C.Structure):
+    """air_scene_records_t: the four sources are noise (given = 0) or the caller's scales / shifts / latents / z_pres"""
+    _fields_ = [("scale_src", _p), ("shift_src", _p), ("z_src", _p), ("pres_src", _p), ("dyn", _p), ("att", _p),
+                ("z", _p), ("z16", _p), ("B", _i), ("N", _i), ("Z", _i), ("ldz", _i), ("given", _i)]
+
+
+class Render(C.Structure):
+    _fields_ = [("vrec", _p), ("att", _p), ("canvas", _p), ("num_digits", _p), ("B", _i), ("N", _i), ("C", _i), ("w", _i)]
+
+
+MAX_STEPS = 16
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -169,6 +181,9 @@ _SIGNATURES = {
     "air_batch_gather": (C.c_int, [_p, _p, _p, _p, _p, C.c_int, C.c_int, _p]),
     "air_summaries_count": (C.c_int, [C.c_int, C.c_int]),
     "air_summaries": (C.c_int, [C.POINTER(Summaries), _p]),
+    "air_scene_records": (C.c_int, [C.POINTER(SceneRecords), _p]),
+    "air_render": (C.c_int, [C.POINTER(Render), _p]),
+    "air_philox_fill": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.c_uint64, C.c_uint64, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -295,6 +295,28 @@ class _Op:
         self.fn(stream)
 
 
+class GeneratedScenes:
+    """What AIRModel.generate() / decode() return: device tensors, image-major like the rec_* attributes, all max_steps
+    steps (a step is an object of scene b while masks[b, t] == 1: the first num_digits[b] of them).  They are VIEWS of the
+    model's generation buffers: the next generate() / decode() call overwrites them."""
+    __slots__ = ("canvas", "num_digits", "scales", "shifts", "z_pres", "masks", "latents", "windows", "st_back")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw[k])
+
+    def st_back_matrices(self):
+        """[B, N, 2, 3] window -> canvas matrices (air_model.py:353-356), the form air.visualize draws boxes from"""
+        return _st_matrices(self.st_back)
+
+
+def _st_matrices(a):
+    """[..., 3] = (1/s, -x/s, -y/s) -> [..., 2, 3] axis-aligned spatial-transformer matrices"""
+    z = torch.zeros_like(a[..., 0])
+    return torch.stack([torch.stack([a[..., 0], z, a[..., 1]], -1),
+                        torch.stack([z, a[..., 0], a[..., 2]], -1)], -2)
+
+
 class AIRModel:
 
     def __init__(self, input_images, target_num_digits,
@@ -449,6 +471,9 @@ class AIRModel:
         self._graph = None
         self._dirty = True
         self._steps_executed = None
+        self._gen = None                          # buffers + launch lists of generate() / decode(), built at their first call
+        self._gen_calls = 0                       # the device RNG's call counter of generate() (never global_step)
+        self._gen_injected = False
         self._alloc()
         self._build_programs()
 
@@ -663,6 +688,8 @@ class AIRModel:
         NB = N * B
         fwd = []
         self._xwx_twin_op = None
+        if getattr(self, "_gen", None) is not None:
+            self._gen["ops"] = None             # (the generation launch list is rebuilt with these; its buffers stay)
 
         def gemm(*args, **kw):
             fwd.append(self._gemm(*args, **kw))
@@ -1344,6 +1371,140 @@ class AIRModel:
 
     __call__ = forward
 
+    # --------------------------------------------------------------- generation
+    # The generative half of the loop body (reference :288-439, 582; vae.py:26-41) with the posterior heads replaced by
+    # the priors: no image, no LSTM, no recognition network.  Own noise / record / output buffers, own RNG call counter:
+    # a forward() / training() result, the model's noise buffers, global_step, the schedules and a captured graph are not
+    # touched.  Launches: [air_philox_fill ->] air_scene_records -> the generative GEMMs and gen_mean with the forward's
+    # descriptors -> air_render (include/air_hip.h).
+    def _gen_state(self):
+        g = self._gen
+        if g is None:
+            dm, dv = self.store.dims, self.input_images.device
+            B, N = self.batch_size, self.max_steps
+            D, d, Z = dm["D"], dm["d"], dm["Z"]
+            f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dv)  # noqa: E731
+            h16 = lambda *s: (torch.zeros(*s, dtype=torch.int16, device=dv) if self._twins else None)  # noqa: E731
+            g = self._gen = dict(ops=None)
+            g["normals"], g["uniforms"] = f(N * B * (1 + 2 + Z + d)), f(N * B)          # the layout of _alloc's noise
+            o = 0
+            g["eps_scale"] = g["normals"][o:o + N * B].view(N, B, 1); o += N * B
+            g["eps_shift"] = g["normals"][o:o + 2 * N * B].view(N, B, 2); o += 2 * N * B
+            g["eps_z"] = g["normals"][o:o + N * B * Z].view(N, B, Z); o += N * B * Z
+            g["eps_x"] = g["normals"][o:o + N * B * d].view(N, B, d)
+            g["u"] = g["uniforms"].view(N, B)
+            # decode(): the caller's tensors, step-major
+            g["in_s"], g["in_xy"], g["in_z"], g["in_p"] = f(N, B), f(N, B, 2), f(N, B, Z), f(N, B)
+            g["att"] = f(N, B, H.ATT_STRIDE)
+            # (rows of Z elements: the operand layout of the forward's unfused first generative GEMM, lda = K = Z)
+            g["z"], g["z16"] = f(N, B, Z), h16(N, B, Z)
+            g["act"] = [f(N, B, u) for u in self.vae_generative_units]
+            g["act16"] = [h16(N, B, u) for u in self.vae_generative_units]
+            g["vrec"] = f(N, B, d)
+            g["canvas"] = f(B, D)
+            g["digits"] = torch.zeros(B, dtype=torch.int32, device=dv)
+        if g["ops"] is None:
+            g["ops"] = self._build_generate(g)
+        return g
+
+    def _build_generate(self, g):
+        """The generation launch lists (see _build_programs for the decoder's GEMM descriptors, which these repeat)."""
+        st, P, dm = self.store, self.store.P, self.store.dims
+        B, N, NB = self.batch_size, self.max_steps, self.max_steps * self.batch_size
+        d, Z = dm["d"], dm["Z"]
+        T = (lambda k: st.P16[k]) if self._twins else (lambda k: None)  # noqa: E731
+        TP = (lambda k: st.panel(k)) if self._use_panels else (lambda k: None)  # noqa: E731
+        gen_u = list(self.vae_generative_units)
+        ops = {}
+        for mode, srcs in (("sample", ("eps_scale", "eps_shift", "eps_z", "u")), ("given", ("in_s", "in_xy", "in_z", "in_p"))):
+            r = H.SceneRecords(*[_ptr(g[k]) for k in srcs], _ptr(self.dyn), _ptr(g["att"]), _ptr(g["z"]), _ptr(g["z16"]),
+                               B, N, Z, Z, 1 if mode == "given" else 0)
+            self._keep.append(r)
+            ops[mode] = self._call("air_scene_records", C.byref(r), nbytes=NB * (4 * (4 + 2 * Z) + 64), tag="scene_records_" + mode)
+            ops[mode].kernel = "scene_records_kernel"
+        dec = []
+        x, x16, k = g["z"], g["z16"], Z
+        for i, u in enumerate(gen_u):
+            dec.append(self._gemm(x, P["gen%d_w" % i], g["act"][i], NB, u, k, k, u, u,
+                                  bias=P["gen%d_b" % i], act=H.ACT_SOFTPLUS, tag="vae_gen",
+                                  A16=x16, B16=T("gen%d_w" % i), C16=g["act16"][i], B16p=TP("gen%d_w" % i)))
+            x, x16, k = g["act"][i], g["act16"][i], u
+        ops["decoder"] = dec
+        for name, sigma in (("out_noise", float(self.vae_likelihood_std)), ("out_mean", 0.0)):
+            ops[name] = self._gemm(x, P["out_w"], g["vrec"], NB, d, k, k, d, d, bias=P["out_b"],
+                                   act=H.ACT_SIGMOID_NOISE, aux=g["eps_x"], ldaux=d, aux_scale=sigma, tag="vae_out",
+                                   A16=x16, B16=T("out_w"), B16p=TP("out_w"))
+        rd = H.Render(_ptr(g["vrec"]), _ptr(g["att"]), _ptr(g["canvas"]), _ptr(g["digits"]), B, N,
+                      self.canvas_size, self.windows_size)
+        self._keep.append(rd)
+        ops["render"] = self._call("air_render", C.byref(rd), nbytes=NB * (d * 4 + 64) + B * dm["D"] * 4, tag="render")
+        ops["render"].kernel = "render_kernel"
+        return ops
+
+    def generate_ops(self, likelihood_noise=False, given=False, fill=True):
+        """The launches of one generate() (given=False) or decode() call, in order (profiling tools)."""
+        g = self._gen_state()
+        o = g["ops"]
+        ops = [self._gen_fill_op()] if fill else []
+        return ops + [o["given" if given else "sample"]] + o["decoder"] + [o["out_noise" if likelihood_noise else "out_mean"], o["render"]]
+
+    def _gen_fill_op(self):
+        g, seed, call = self._gen, self._seed, self._gen_calls
+        op = self._call("air_philox_fill", _ptr(g["normals"]), g["normals"].numel(), _ptr(g["uniforms"]), g["uniforms"].numel(),
+                        C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(call),
+                        nbytes=4 * (g["normals"].numel() + g["uniforms"].numel()), tag="philox_fill")
+        op.kernel = "philox_fill_kernel"
+        return op
+
+    def _gen_run(self, given, likelihood_noise, needs_noise):
+        g = self._gen_state()
+        self._fresh_shadow()
+        s = self._stream()
+        fill = needs_noise and not self._gen_injected
+        for op in self.generate_ops(likelihood_noise, given, fill):
+            op(s)
+        if fill:
+            self._gen_calls += 1
+        self._gen_injected = False
+        a = g["att"]
+        return GeneratedScenes(canvas=g["canvas"], num_digits=g["digits"],
+                               scales=a[:, :, H.ATT_S:H.ATT_S + 1].transpose(0, 1), shifts=a[:, :, H.ATT_X:H.ATT_Y + 1].transpose(0, 1),
+                               z_pres=a[:, :, H.ATT_Z].t(), masks=a[:, :, H.ATT_MASK].t(), latents=g["z"].transpose(0, 1),
+                               windows=g["vrec"].transpose(0, 1), st_back=a[:, :, H.ATT_ST_BACK:H.ATT_ST_BACK + 3].transpose(0, 1))
+
+    def set_generate_noise(self, noise):
+        """Injects eps_scale [N,B,1], eps_shift [N,B,2], eps_z [N,B,Z], eps_x [N,B,d], u [N,B] (the dict of set_noise) for
+        ONE generate() / decode() call; the device RNG is back after it."""
+        g = self._gen_state()
+        for k in ("eps_scale", "eps_shift", "eps_z", "eps_x", "u"):
+            g[k].copy_(torch.as_tensor(np.asarray(noise[k]), dtype=torch.float32).reshape(g[k].shape))
+        self._gen_injected = True
+
+    def generate(self, likelihood_noise=False):
+        """Draws batch_size scenes from the model's priors and renders them: z_pres from the Concrete prior (rounded, as at
+        test time), scale / shift / z_what from their Gaussian priors -- all read from the live dynamic scalars, so
+        set_dynamic() and annealed values apply --, the stopping rule of the loop, the decoder as forward() runs it and the
+        compose kernel's canvas.  likelihood_noise=False renders the decoder's mean image, True adds vae_likelihood_std
+        noise before the sigmoid (vae.py:36-41).  Noise comes from the device Philox stream keyed by (seed, number of
+        earlier drawing calls): the same seed and call index give the same scenes, successive calls differ.  Works on train
+        and test models; returns a GeneratedScenes.  No gradients flow through it."""
+        return self._gen_run(False, bool(likelihood_noise), True)
+
+    def decode(self, latents, scales, shifts, z_pres, likelihood_noise=False):
+        """Renders the scenes described by the caller's DEVICE tensors latents [B,N,Z], scales [B,N,1] (or [B,N]), shifts
+        [B,N,2] and z_pres [B,N] (used as given -- it may be relaxed; the masks are re-derived by the stopping rule), the
+        way generate() renders its own.  likelihood_noise=True draws eps_x (or takes set_generate_noise's)."""
+        g = self._gen_state()
+        B, N, Z = self.batch_size, self.max_steps, self.vae_latent_dimensions
+        for name, t, shape, dst in (("latents", latents, (B, N, Z), g["in_z"]), ("scales", scales, (B, N, 1), g["in_s"]),
+                                    ("shifts", shifts, (B, N, 2), g["in_xy"]), ("z_pres", z_pres, (B, N, 1), g["in_p"])):
+            if not (torch.is_tensor(t) and t.is_cuda):
+                raise H.AirHipError("%s must be a CUDA/HIP device tensor: this path has no CPU fallback" % name)
+            if t.dtype != torch.float32 or t.numel() != B * N * shape[2] or tuple(t.shape[:2]) != (B, N):
+                raise ValueError("%s must be float32 %r" % (name, shape))
+            dst.copy_(t.reshape(shape).transpose(0, 1).reshape(dst.shape))
+        return self._gen_run(True, bool(likelihood_noise), bool(likelihood_noise))
+
     # ------------------------------------------------------------------ outputs
     def _ensure(self):
         if self._dirty:
@@ -1415,10 +1576,7 @@ class AIRModel:
 
     @property
     def rec_st_back(self):
-        a = self._stack(self.att[:, :, H.ATT_ST_BACK:H.ATT_ST_BACK + 3])        # [B,T',3] = 1/s, -x/s, -y/s
-        z = torch.zeros_like(a[..., 0])
-        return torch.stack([torch.stack([a[..., 0], z, a[..., 1]], -1),
-                            torch.stack([z, a[..., 0], a[..., 2]], -1)], -2)
+        return _st_matrices(self._stack(self.att[:, :, H.ATT_ST_BACK:H.ATT_ST_BACK + 3]))   # [B,T',3] = 1/s, -x/s, -y/s
 
     def state_dict(self):
         return self.store.state_dict()

@@ -41,28 +41,46 @@ def draw_colored_bounding_boxes(images, boxes, steps):
     return torch.stack(channels, dim=3)
 
 
-def visualize_reconstructions(original, reconstruction, st_back, steps, canvas_size, windows_size, max_steps, zoom=2):
-    """air_model.py:211-267.  original / reconstruction [n, C*C], st_back [n, T', 2, 3], steps [n]
-    -> [n, zoom*C, 2*zoom*C + 4, 3] float in [0, 1]: original with boxes | white stripe | reconstruction
-    with boxes."""
-    n, C, w, Z = original.shape[0], canvas_size, windows_size, zoom * canvas_size
-    large_o = resize_bilinear_tf1(original.reshape(n, C, C).float(), Z, Z)
-    large_r = resize_bilinear_tf1(reconstruction.reshape(n, C, C).float(), Z, Z)
+def attention_boxes(st_back, canvas_size, windows_size, max_steps, zoom=2):
+    """st_back [n, T', 2, 3] window -> canvas matrices -> [n, max_steps, zoom*C, zoom*C] in {0, 1}: the one-pixel frame of
+    every step's attention window, rasterised through the spatial transformer (air_model.py:226-254)."""
+    n, w, Z = st_back.shape[0], windows_size, zoom * canvas_size
     # pad the ST matrices to max_steps (fewer steps may have been executed globally, :226-231)
     T = st_back.shape[1]
     if T < max_steps:
         st_back = torch.cat([st_back, torch.zeros(n, max_steps - T, 2, 3, device=st_back.device)], dim=1)
     # a window-sized frame with a one-pixel border (tf.image.draw_bounding_boxes with box [0,0,1,1])
-    frame = torch.zeros(w, w, device=original.device)
+    frame = torch.zeros(w, w, device=st_back.device)
     frame[0, :] = 1.0; frame[-1, :] = 1.0; frame[:, 0] = 1.0; frame[:, -1] = 1.0
     frames = frame.expand(n * max_steps, w, w).contiguous()
     boxes = transformer(frames.unsqueeze(3), st_back.reshape(n * max_steps, 6).contiguous(), [Z, Z])
     boxes = boxes.reshape(n, max_steps, Z, Z).clamp(0.0, 1.0)
-    boxes = (boxes > 0.01).float()                                       # sharpen the borders :250-254
+    return (boxes > 0.01).float()                                        # sharpen the borders :250-254
+
+
+def visualize_reconstructions(original, reconstruction, st_back, steps, canvas_size, windows_size, max_steps, zoom=2):
+    """air_model.py:211-267.  original / reconstruction [n, C*C], st_back [n, T', 2, 3], steps [n]
+    -> [n, zoom*C, 2*zoom*C + 4, 3] float in [0, 1]: original with boxes | white stripe | reconstruction
+    with boxes."""
+    n, C, Z = original.shape[0], canvas_size, zoom * canvas_size
+    large_o = resize_bilinear_tf1(original.reshape(n, C, C).float(), Z, Z)
+    large_r = resize_bilinear_tf1(reconstruction.reshape(n, C, C).float(), Z, Z)
+    boxes = attention_boxes(st_back, canvas_size, windows_size, max_steps, zoom)
     left = draw_colored_bounding_boxes(large_o, boxes, steps)
     right = draw_colored_bounding_boxes(large_r, boxes, steps)
     stripe = torch.ones(n, Z, 4, 3, device=original.device)
     return torch.cat([left, stripe, right], dim=2)
+
+
+def visualize_scenes(canvas, st_back, steps, canvas_size, windows_size, max_steps, zoom=2):
+    """Generated scenes (AIRModel.generate): canvas [n, C*C], st_back [n, N, 2, 3], steps [n] object counts
+    -> [n, zoom*C, 2*zoom*C + 4, 3]: the scene | white stripe | the scene with the attention boxes of its objects."""
+    n, C, Z = canvas.shape[0], canvas_size, zoom * canvas_size
+    large = resize_bilinear_tf1(canvas.reshape(n, C, C).float(), Z, Z)
+    boxes = attention_boxes(st_back, canvas_size, windows_size, max_steps, zoom)
+    plain = torch.stack([large, large, large], dim=3)
+    stripe = torch.ones(n, Z, 4, 3, device=canvas.device)
+    return torch.cat([plain, stripe, draw_colored_bounding_boxes(large, boxes, steps)], dim=2)
 
 
 def save_image_grid(images, path, columns=10, pad=2):

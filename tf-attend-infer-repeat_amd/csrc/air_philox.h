@@ -1,6 +1,7 @@
 // Step prologue shared by step_begin_kernel and the GEMM kernels (which can carry it as extra
 // workgroups of the hoisted x.Wx launch): annealing schedules (air_model.py:94-121) + Philox4x32-10
-// noise keyed by (index, global_step).
+// noise keyed by (index, global_step).  The generator itself (air_philox_quad) also serves air_philox_fill
+// (air_generate.hip), keyed by (index, call counter).
 #pragma once
 #include "air_common.h"
 
@@ -40,6 +41,32 @@ __device__ __forceinline__ float air_eval_schedule(const air_schedule_t& s, int 
     return v;
 }
 
+// Quad q of a noise plane: four numbers from Philox4x32-10(key = (k0, k1), counter = (q, c2, c3)) -- normals for
+// q < quads_n (elements 4q .. 4q+3 of `normals`), uniforms behind them.  Shared by the step prologue (c2 = global_step) and
+// air_philox_fill (c2 = the caller's call counter, another c3).
+__device__ __forceinline__ void air_philox_quad(long q, long quads_n, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                                float* normals, long n_normal, float* uniforms, long n_uniform) {
+    uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), c2, c3};
+    air_philox4x32_10(c, k0, k1);
+    float v[4];
+    if (q < quads_n) {
+        // Box-Muller on two pairs, on the hardware transcendentals: v_log_f32 (2^-23-level relative error away from 1),
+        // v_sin_f32 / v_cos_f32 take their argument in REVOLUTIONS, i.e. the uniform itself -- no 2*pi range reduction.
+        // (The library sinf / cosf / logf cost ~400 instructions per quad: at the 128x128 configuration the noise planes
+        // -- 1.07 M normals per step -- were ~20 us of the x.Wx launch that carries them.  The reference's RNG ops are
+        // unseeded; only the distribution matters, tests/test_gpu_kernels.py::test_step_begin_schedule_and_noise.)
+        const float r0 = sqrtf(-2.0f * __logf(air_u01_open_low(c[0]))), a0 = air_u01_half_open(c[1]);
+        const float r1 = sqrtf(-2.0f * __logf(air_u01_open_low(c[2]))), a1 = air_u01_half_open(c[3]);
+        v[0] = r0 * __builtin_amdgcn_cosf(a0); v[1] = r0 * __builtin_amdgcn_sinf(a0);
+        v[2] = r1 * __builtin_amdgcn_cosf(a1); v[3] = r1 * __builtin_amdgcn_sinf(a1);
+        const long base = q * 4;
+        for (int k = 0; k < 4; ++k) if (base + k < n_normal) normals[base + k] = v[k];
+    } else {
+        const long base = (q - quads_n) * 4;
+        for (int k = 0; k < 4; ++k) if (base + k < n_uniform) uniforms[base + k] = air_u01_half_open(c[k]);
+    }
+}
+
 // workgroup `wg` of `nwg` (256 threads each) of the job
 __device__ __forceinline__ void air_step_job_run(const AirStepJob& j, long wg, long nwg) {
     const int step = j.istate[AIR_IST_GLOBAL_STEP];
@@ -58,24 +85,6 @@ __device__ __forceinline__ void air_step_job_run(const AirStepJob& j, long wg, l
                 for (int k = 0; k < 4; ++k) if (base + k < j.twin_n) j.twin_dst[base + k] = air_bf16_of(j.twin_src[base + k]);
             continue;
         }
-        uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)step, 0x41495221u};
-        air_philox4x32_10(c, j.seed_lo, j.seed_hi);
-        float v[4];
-        if (q < quads_n) {
-            // Box-Muller on two pairs, on the hardware transcendentals: v_log_f32 (2^-23-level relative error away from 1),
-            // v_sin_f32 / v_cos_f32 take their argument in REVOLUTIONS, i.e. the uniform itself -- no 2*pi range reduction.
-            // (The library sinf / cosf / logf cost ~400 instructions per quad: at the 128x128 configuration the noise planes
-            // -- 1.07 M normals per step -- were ~20 us of the x.Wx launch that carries them.  The reference's RNG ops are
-            // unseeded; only the distribution matters, tests/test_gpu_kernels.py::test_step_begin_schedule_and_noise.)
-            const float r0 = sqrtf(-2.0f * __logf(air_u01_open_low(c[0]))), a0 = air_u01_half_open(c[1]);
-            const float r1 = sqrtf(-2.0f * __logf(air_u01_open_low(c[2]))), a1 = air_u01_half_open(c[3]);
-            v[0] = r0 * __builtin_amdgcn_cosf(a0); v[1] = r0 * __builtin_amdgcn_sinf(a0);
-            v[2] = r1 * __builtin_amdgcn_cosf(a1); v[3] = r1 * __builtin_amdgcn_sinf(a1);
-            const long base = q * 4;
-            for (int k = 0; k < 4; ++k) if (base + k < j.n_normal) j.normals[base + k] = v[k];
-        } else {
-            const long base = (q - quads_n) * 4;
-            for (int k = 0; k < 4; ++k) if (base + k < j.n_uniform) j.uniforms[base + k] = air_u01_half_open(c[k]);
-        }
+        air_philox_quad(q, quads_n, (uint32_t)step, 0x41495221u, j.seed_lo, j.seed_hi, j.normals, j.n_normal, j.uniforms, j.n_uniform);
     }
 }

@@ -80,14 +80,7 @@ __device__ __forceinline__ float gauss_kl_term(float plv, float lv, float var, f
 // left is the scalar stopping sum S, which block (b, t) re-derives from the
 // z_pres of the earlier steps with the identical op sequence (bitwise equal).
 // ---------------------------------------------------------------------------
-constexpr int MAX_STEPS = 16;
-
-// concrete.py:20-27 + air_model.py:385-390: pre-sigmoid sample and z_pres
-__device__ __forceinline__ float concrete_presigmoid(float lo, float u, float T) {
-    const float noise = logf(u + AIR_EPS) - logf((1.0f - u) + AIR_EPS);
-    return (lo + noise) / T;
-}
-
+// (MAX_STEPS, concrete_presigmoid: air_sampler_common.h)
 __global__ __launch_bounds__(THREADS) void attend_fwd_kernel(air_attend_fwd_t a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -422,7 +415,7 @@ __global__ __launch_bounds__(THREADS) void attend_bwd_kernel(air_attend_bwd_t a)
 // that latency.  ONE workgroup of 1024 threads per image.  (An image as 2 or 4 workgroups -- 256 workgroups at B = 64,
 // the per-image sums finished by the next launch, bit-identical -- was built and measured in round 4: 7.7 us as one
 // workgroup, 8.5 in 4 bands, 7.7 in 2; 31 -> 35.5 us at 128 x 128: every band repeats the set-up loads.  Removed.)
-constexpr int CF_THREADS = 1024;
+// (CF_THREADS and the staging / per-pixel code shared with air_render: air_sampler_common.h)
 
 // LONGEST-FIRST ORDER of the (image, step) items for the graph-order write backward (air_write_fwd_t.wb_order), computed
 // by ONE extra workgroup of the compose launch.  Why: the backward's workgroups differ by two orders of magnitude in work
@@ -537,19 +530,7 @@ __global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
             if (lane == 0) sh_kl[t] = 0.5f * klt;
         }
     }
-    for (int it = tid; it < N * C; it += NT) {
-        const int t = it / C, j = it % C;
-        const float* at = a.att + ((size_t)t * B + b) * AIR_ATT_STRIDE;
-        // theta_recon :353-356
-        const float s = at[AIR_ATT_S], x = at[AIR_ATT_X], y = at[AIR_ATT_Y];
-        const float ia = 1.0f / s, bx = (-x) / s, by = (-y) / s;
-        sh_tx[it] = axis_tap(j, C, w, ia, bx);
-        sh_ty[it] = axis_tap(j, C, w, ia, by);
-    }
-    for (int it = tid; it < N * w * w; it += NT) {
-        const int t = it / (w * w);
-        sh_win[it] = a.vrec[((size_t)t * B + b) * w * w + (it - t * w * w)];
-    }
+    compose_stage(a.att, a.vrec, b, B, N, C, w, tid, NT, sh_tx, sh_ty, sh_win);
     if (tid < N) {
         // one thread per step fetches its record (six independent loads); thread 0 below then sums from LDS -- as a loop
         // of conditional loads on one thread it was a dozen memory round trips in a row
@@ -594,15 +575,7 @@ __global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
 #pragma unroll
             for (int q = 1; q < XPRE; ++q) x = (k == q) ? xs[q] : x;
         } else x = a.images[base + p];
-        float R = 0.0f;                                             // running_recon :552
-        for (int t = 0; t < N; ++t) {
-            if (!sh_act[t]) continue;                               // where(active, z*w, 0) :433-439
-            const Tap tx = sh_tx[(size_t)t * C + j], ty = sh_ty[(size_t)t * C + i];
-            const float* win = sh_win + (size_t)t * w * w;
-            const float wr = bilinear4(tx, ty, win[ty.i0 * w + tx.i0], win[ty.i1 * w + tx.i0],
-                                       win[ty.i0 * w + tx.i1], win[ty.i1 * w + tx.i1]);
-            R = R + sh_z[t] * wr;
-        }
+        const float R = compose_pixel(sh_act, sh_z, sh_tx, sh_ty, sh_win, N, C, w, i, j);
         i += di; j += dj;
         if (j >= C) { j -= C; ++i; }
         const float r = fmaxf(fminf(R, 1.0f), 0.0f);                // clipped_rec :582

@@ -1,7 +1,8 @@
-// Shared pieces of the two sampler translation units (air_sampler.hip: the glimpse read, the heads around it, compose, the
+// Shared pieces of the sampler translation units (air_sampler.hip: the glimpse read, the heads around it, compose, the
 // generic forward; air_sampler_write_bwd.hip: the write backward in its three orders, the generic backward, the lane-order
-// probe): the per-axis tap of the axis-aligned transformer, the reference's 4-product expression and the coordinate
-// gradient in the saved graph's op order.
+// probe; air_generate.hip: the records of generated scenes and the render-only compose): the per-axis tap of the
+// axis-aligned transformer, the reference's 4-product expression, the coordinate gradient in the saved graph's op order,
+// the Concrete pre-sigmoid sample, and the staging / per-pixel code of compose.
 #pragma once
 #include "air_common.h"
 #include <cstdio>
@@ -61,6 +62,52 @@ __device__ __forceinline__ void graph_dxy(float g, float Ia, float Ib, float Ic,
     const float dY = ((-(tx.w0 * ga) + tx.w0 * gb) + -(tx.w1 * gc)) + tx.w1 * gd;
     dxs = (dX / 2.0f) * cx;
     dys = (dY / 2.0f) * cx;
+}
+
+constexpr int MAX_STEPS = AIR_MAX_STEPS;     // the per-image records of the attend / compose / render kernels
+
+// concrete.py:20-27 + air_model.py:385-390: pre-sigmoid sample and z_pres
+__device__ __forceinline__ float concrete_presigmoid(float lo, float u, float T) {
+    const float noise = logf(u + AIR_EPS) - logf((1.0f - u) + AIR_EPS);
+    return (lo + noise) / T;
+}
+
+// ---- compose, the part air_write_fwd and air_render share: one workgroup per image, CF_THREADS threads ----------------
+constexpr int CF_THREADS = 1024;
+
+// taps of theta_recon (air_model.py:353-356) for every (step, canvas column / row) and the windows of all N steps of image
+// b into LDS: sh_tx / sh_ty [N][C], sh_win [N][w*w]
+__device__ __forceinline__ void compose_stage(const float* att, const float* vrec, int b, int B, int N,
+                                              int C, int w, int tid, int nthreads, Tap* sh_tx, Tap* sh_ty, float* sh_win) {
+    for (int it = tid; it < N * C; it += nthreads) {
+        const int t = it / C, j = it % C;
+        const float* at = att + ((size_t)t * B + b) * AIR_ATT_STRIDE;
+        // theta_recon :353-356
+        const float s = at[AIR_ATT_S], x = at[AIR_ATT_X], y = at[AIR_ATT_Y];
+        const float ia = 1.0f / s, bx = (-x) / s, by = (-y) / s;
+        sh_tx[it] = axis_tap(j, C, w, ia, bx);
+        sh_ty[it] = axis_tap(j, C, w, ia, by);
+    }
+    for (int it = tid; it < N * w * w; it += nthreads) {
+        const int t = it / (w * w);
+        sh_win[it] = vrec[((size_t)t * B + b) * w * w + (it - t * w * w)];
+    }
+}
+
+// running_recon of canvas pixel (i, j) (:552, :429-439): the z-scaled window -> canvas taps of the active steps, summed in
+// step order
+__device__ __forceinline__ float compose_pixel(const int* sh_act, const float* sh_z, const Tap* sh_tx, const Tap* sh_ty,
+                                               const float* sh_win, int N, int C, int w, int i, int j) {
+    float R = 0.0f;                                                 // running_recon :552
+    for (int t = 0; t < N; ++t) {
+        if (!sh_act[t]) continue;                                   // where(active, z*w, 0) :433-439
+        const Tap tx = sh_tx[(size_t)t * C + j], ty = sh_ty[(size_t)t * C + i];
+        const float* win = sh_win + (size_t)t * w * w;
+        const float wr = bilinear4(tx, ty, win[ty.i0 * w + tx.i0], win[ty.i1 * w + tx.i0],
+                                   win[ty.i0 * w + tx.i1], win[ty.i1 * w + tx.i1]);
+        R = R + sh_z[t] * wr;
+    }
+    return R;
 }
 
 template <typename K>

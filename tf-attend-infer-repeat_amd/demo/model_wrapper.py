@@ -5,6 +5,9 @@ lists (digit counts, [s, x, y] positions, reconstructions, attention windows, la
 The reference feeds a placeholder through a session; here the images are copied into the model's
 resident input buffer (its batch size is fixed at construction), in chunks, padded with blank
 canvases, and the outputs are read back once per chunk.
+
+`ModelWrapper(model).generate(n)` has no counterpart in the reference: n scenes drawn from the model's priors and
+rendered on the device (AIRModel.generate), as the same kind of per-scene lists.
 """
 import numpy as np
 import torch
@@ -50,4 +53,26 @@ class ModelWrapper:
             out[3].extend(wins[i, :c] if c else none for i, c in enumerate(counts))
             out[4].extend(lats[i, :c] if c else none for i, c in enumerate(counts))
             out[5].extend(loss)
+        return out
+
+    def generate(self, n, likelihood_noise=False):
+        """n scenes from the model's priors: (object counts, [n_i, 3] (s, x, y) rows, [C, C] canvases, [n_i, w, w] windows,
+        [n_i, Z] latents) -- one entry per scene, n_i = its object count; batches of the model's size, the last one cut."""
+        m, B, cs, ws = self.model, self.model.batch_size, self.canvas_size, self.window_size
+        out = ([], [], [], [], [])
+        none = np.array([])
+        for lo in range(0, n, B):
+            k = min(B, n - lo)
+            sc = m.generate(likelihood_noise=likelihood_noise)
+            counts = sc.num_digits[:k].cpu().numpy().astype(int)
+            sxy = torch.cat([sc.scales[:k], sc.shifts[:k]], dim=2).cpu().numpy()                # [k, N, 3]
+            wins = sc.windows[:k].cpu().numpy().reshape(k, -1, ws, ws)
+            lats = sc.latents[:k].cpu().numpy()
+            cans = sc.canvas[:k].cpu().numpy().reshape(k, cs, cs)
+            # the stopping rule makes the active steps a prefix: the first `count` steps are the objects
+            out[0].extend(int(c) for c in counts)
+            out[1].extend(sxy[i, :c] if c else none for i, c in enumerate(counts))
+            out[2].extend(cans)
+            out[3].extend(wins[i, :c] if c else none for i, c in enumerate(counts))
+            out[4].extend(lats[i, :c] if c else none for i, c in enumerate(counts))
         return out
