@@ -319,7 +319,11 @@ int air_transformer_bwd(const float* U, const float* theta, const float* d_out, 
  * hid [N,B,HT] = ReLU hidden activations of the 5 heads, concatenated in the order
  * scale/mean, scale/log_variance, shift/mean, shift/log_variance, z_pres/log_odds
  * with widths Hs,Hs,Hh,Hh,Hz (HT = 2Hs+2Hh+Hz).  wout [7][wout_ld] holds one row
- * per output unit, bout [7]. */
+ * per output unit, bout [7].
+ * wout_ld is the row stride of wout in floats: wout_ld >= max(Hs, Hh, Hz), AIR_EINVAL otherwise (air_attend_fwd,
+ * air_attend_bwd and air_heads_out_wgrad alike).  It may be padded beyond the widest head: the pad is copied with the
+ * rows but never enters a product, whatever it holds.  air_attend_fwd keeps all 7 * wout_ld floats in LDS next to
+ * 17 * HT + 8 * w + ~40 floats and, for C * C <= 2560, the canvas: AIR_ELIMIT beyond 160 KB. */
 typedef struct {
     const float* hid; const float* wout; const float* bout;
     const float* canvas;                 /* input_images [B,C*C]            */

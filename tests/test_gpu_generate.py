@@ -185,11 +185,59 @@ def test_decode_bf16_against_fp32_decode(am, train):
     assert H.ATT_STRIDE == 16
 
 
-@pytest.mark.parametrize("Cc", [50, 128])
-def test_render_equals_compose_bit_for_bit(am, Cc):
+def _scene_records_given(H, scales, shifts, latents, z_pres, dyn):
+    """air_scene_records(given = 1): att [N,B,16] from the caller's scales [N,B], shifts [N,B,2], latents [N,B,Z], z_pres [N,B]"""
+    N, B, Z = latents.shape
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    att = torch.full((N, B, H.ATT_STRIDE), float("nan"), device="cuda")
+    z = torch.full((N, B, Z), float("nan"), device="cuda")
+    a = H.SceneRecords(p(scales), p(shifts), p(latents), p(z_pres), p(dyn), p(att), p(z), None, B, N, Z, Z, 1)
+    H.check(H.lib().air_scene_records(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "air_scene_records")
+    return att
+
+
+@pytest.mark.parametrize("Cc,N", [pytest.param(50, 5, id="50"), pytest.param(128, 5, id="128"),
+                                  pytest.param(50, 16, id="50-16-steps-given-records")])
+def test_render_equals_compose_bit_for_bit(am, Cc, N):
     H = sys.modules["air._hip"]
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)  # noqa: E731
+    if N == 16:
+        # all 16 steps the records of the two kernels hold, without a model: records from air_scene_records on scales,
+        # shifts and (relaxed) z_pres given by the caller -- image 0 alive through all 16 steps, 1 stops at step 0, 2 at
+        # step 7, 3 at step 15 -- and random windows; air_write_fwd and air_render on the same att / vrec
+        B, w, Z = 4, 28, 3
+        rng = np.random.RandomState(16)
+        z_pres = rng.uniform(0.97, 0.999, (N, B)).astype(np.float32)
+        z_pres[0, 1] = z_pres[7, 2] = z_pres[15, 3] = 0.004
+        t_ = lambda a: torch.tensor(a.astype(np.float32), device="cuda")  # noqa: E731
+        dyn = np.zeros(H.DYN_COUNT, np.float32)
+        dyn[H.DYN_STOP_THRESHOLD], dyn[H.DYN_GRAD_SCALE], dyn[H.DYN_VAE_PV] = 0.99, 1.0 / B, 1.0
+        dyn_d = t_(dyn)
+        att = _scene_records_given(H, t_(rng.uniform(0.2, 0.95, (N, B))), t_(rng.uniform(-0.8, 0.8, (N, B, 2))),
+                                   t_(rng.standard_normal((N, B, Z))), t_(z_pres), dyn_d)
+        vrec = t_(rng.uniform(0.0, 0.4, (N, B, w * w)))
+        images, _ = blob_canvases(B, Cc, 2, seed=3)
+        recon, rec_loss, run_loss, loss_item = (torch.full(s, float("nan"), device="cuda") for s in ((B, Cc * Cc), (B,), (B,), (B,)))
+        run_digits = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+        ml, img_d = torch.zeros(N, B, 2 * Z, device="cuda"), torch.tensor(images, device="cuda")
+        att_w = att.clone()
+        wf = H.WriteFwd(p(vrec), p(ml), p(img_d), p(dyn_d), p(att_w), p(recon), p(rec_loss), None, p(run_loss), p(run_digits),
+                        p(loss_item), B, N, Cc, w, Z, None)
+        H.check(H.lib().air_write_fwd(C.byref(wf), stream()), "air_write_fwd")
+        canvas = torch.full((B, Cc * Cc), -1.0, device="cuda")
+        digits = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+        a = H.Render(p(vrec), p(att), p(canvas), p(digits), B, N, Cc, w)
+        H.check(H.lib().air_render(C.byref(a), stream()), "air_render")
+        torch.cuda.synchronize()
+        assert digits.tolist() == [16, 0, 7, 15]                  # the stopping sum of air_scene_records, in step order
+        assert torch.equal(att[:, :, H.ATT_MASK].sum(0).to(torch.int32), digits)
+        assert torch.equal(digits, run_digits)
+        assert torch.equal(canvas, recon)
+        assert float(canvas[0].max()) == 1.0 and not bool(canvas[1].any()) and float(canvas.min()) == 0.0
+        return
     hp = dict(HP, canvas_size=Cc, max_steps=5)
-    B, N, w = 16, 5, hp["windows_size"]
+    B, w = 16, hp["windows_size"]
     images, _ = blob_canvases(B, Cc, hp["max_digits"], seed=3)
     model = _model(am, B, hp=hp, images=images)
     model.load_state_dict(ao.init_params(hp, 0))
@@ -200,9 +248,8 @@ def test_render_equals_compose_bit_for_bit(am, Cc):
     torch.cuda.synchronize()
     canvas = torch.full((B, Cc * Cc), -1.0, device="cuda")
     digits = torch.full((B,), -1, dtype=torch.int32, device="cuda")
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     a = H.Render(p(model.vrec), p(model.att), p(canvas), p(digits), B, N, Cc, w)
-    H.check(H.lib().air_render(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "air_render")
+    H.check(H.lib().air_render(C.byref(a), stream()), "air_render")
     torch.cuda.synchronize()
     print("C = %d: active (image, step) pairs %d of %d" % (Cc, int(model.rec_num_digits.sum()), B * N))
     assert int(model.rec_num_digits.max()) >= 2              # overlapping windows: the step-order sum is exercised

@@ -817,7 +817,8 @@ def _write_theta(s, x, y):
 
 
 @pytest.mark.parametrize("literal,order", [(2, "sequential"), (4, "carried16")])
-@pytest.mark.parametrize("Cc,w,N,B", [(50, 28, 3, 6), (71, 28, 2, 5), (128, 28, 5, 4), (128, 20, 2, 3), (50, 32, 2, 3), (40, 9, 2, 4)])
+@pytest.mark.parametrize("Cc,w,N,B", [(50, 28, 3, 6), (71, 28, 2, 5), (128, 28, 5, 4), (128, 20, 2, 3), (50, 32, 2, 3), (40, 9, 2, 4),
+                                      (50, 28, 16, 2), (40, 9, 16, 3)])       # ... and the 16 steps the records hold
 def test_write_bwd_graph_order_matches_oracle_all_canvas_sizes(H, Cc, w, N, B, literal, order):
     """air_write_bwd(literal=2) -- backward="reference" -- against oracle.transformer_backward
     (pinned to the reference's executed graph, transformer.py:56-117 under tf.gradients) on random inputs, and

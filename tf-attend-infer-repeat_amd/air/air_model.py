@@ -317,6 +317,55 @@ def _st_matrices(a):
                         torch.stack([z, a[..., 0], a[..., 2]], -1)], -2)
 
 
+LDS_LIMIT = 160 * 1024      # bytes of LDS a workgroup may hold on gfx950 (air_grant_lds, csrc/air_common.h: AIR_ELIMIT beyond)
+
+
+def step_lds_bytes(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, literals=()):
+    """Dynamic LDS, in bytes, of every launch of the step whose need grows with the hyper-parameters: [(launch, bytes)].
+    Each line restates the C++ function that sizes the launch (quoted above it): change them together.  `literals`: the
+    air_write_bwd_t.literal values of the sampler-backward orders a train model runs (none for a test model)."""
+    N, C, w = max_steps, canvas_size, windows_size
+    HT = 2 * Hs + 2 * Hh + Hz
+    MAX_STEPS = H.MAX_STEPS
+    r4 = lambda n: (n + 3) & ~3  # noqa: E731
+    # air_sampler.hip  attend_canvas_floats(C): C * C <= 10 * THREADS ? C * C : 0                          (THREADS = 256)
+    canvas = C * C if C * C <= 10 * 256 else 0
+    need = [
+        # air_sampler.hip  attend_smem(C, w, HT, wout_ld):
+        #   (16 + MAX_STEPS + 8 * w + 4 + ((HT + 3) & ~3) + 7 * wout_ld + MAX_STEPS * HT + attend_canvas_floats(C)) * 4
+        ("air_attend_fwd", (16 + MAX_STEPS + 8 * w + 4 + r4(HT) + 7 * wout_ld + MAX_STEPS * HT + canvas) * 4),
+        # air_sampler.hip  write_smem(N, C, w): (16 + 7 * MAX_STEPS + N * (8 * C + w * w)) * 4
+        #   (with wb_order at least WB_ORDER_MAX * 4 = 16 KB: never the binding term)
+        ("air_write_fwd", (16 + 7 * MAX_STEPS + N * (8 * C + w * w)) * 4),
+        # air_generate.hip  render_smem(N, C, w): (2 * MAX_STEPS + N * (8 * C + w * w)) * 4
+        ("air_render", (2 * MAX_STEPS + N * (8 * C + w * w)) * 4),
+    ]
+    if literals:
+        # air_sampler.hip  attend_bwd_smem(C, w): (24 + 8 * w + w + 4 + attend_canvas_floats(C)) * 4
+        need.append(("air_attend_bwd", (24 + 8 * w + w + 4 + canvas) * 4))
+    for lit in sorted(set(literals)):
+        if lit >= 2:
+            # air_sampler_write_bwd.hip  write_bwd_graph_smem(C, w, allph):
+            #   (136 + 8 * C + ((C + 3) & ~3) + 8 * C + ((8 * w + 3) & ~3) + ((w * w + 3) & ~3) + (allph ? 5 : 1) * ((C * C + 3) & ~3)) * 4
+            #   allph = write_bwd_graph_smem(C, w, true) <= 80 * 1024                                     (air_write_bwd)
+            graph = lambda allph: (136 + 8 * C + r4(C) + 8 * C + r4(8 * w) + r4(w * w) + (5 if allph else 1) * r4(C * C)) * 4  # noqa: E731
+            need.append(("air_write_bwd (literal %d)" % lit, graph(graph(True) <= 80 * 1024)))
+        else:
+            # air_sampler_write_bwd.hip  write_bwd_smem(C, w): (64 + 8 * C + C + 8 * w + w * w + C * w + C * C) * 4
+            need.append(("air_write_bwd (literal 0)", (64 + 8 * C + C + 8 * w + w * w + C * w + C * C) * 4))
+    return need
+
+
+def check_step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, literals=()):
+    """NotImplementedError when a launch of the step would need more LDS than a workgroup can hold"""
+    for launch, nbytes in step_lds_bytes(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, literals):
+        if nbytes > LDS_LIMIT:
+            raise NotImplementedError(
+                "canvas_size = %d with max_steps = %d and windows_size = %d exceeds the HIP path's limits: %s would need %d bytes of "
+                "LDS per workgroup, a workgroup holds %d (the taps and windows of all steps of an image, or a whole canvas, "
+                "live in LDS) -- reduce canvas_size or max_steps" % (canvas_size, max_steps, windows_size, launch, nbytes, LDS_LIMIT))
+
+
 class AIRModel:
 
     def __init__(self, input_images, target_num_digits,
@@ -340,7 +389,8 @@ class AIRModel:
         self.target_num_digits = target_num_digits
         self.batch_size = int(input_images.shape[0])
         # the shape limits of the kernels, checked HERE with the limit in the message (a caller never meets them as an
-        # error code of a launch): include/air_hip.h
+        # error code of a launch): include/air_hip.h.  The LDS each launch needs follows below, once the backward order is
+        # known (check_step_lds)
         limits = (("max_steps", max_steps, 16, "the per-image records of the compose / attend kernels hold 16 steps"),
                   ("windows_size", windows_size, 32, "the sampler backward gives every glimpse pixel a thread of a 1024-thread workgroup"),
                   ("len(vae_recognition_units) + len(vae_generative_units)", len(vae_recognition_units) + len(vae_generative_units), 10,
@@ -415,6 +465,8 @@ class AIRModel:
         # the rounding the fp32-operand kernels apply on the way into LDS).  bf16_twins=False keeps fp32 operands.
         self._twins = (True if bf16_twins is None else bool(bf16_twins)) and self._prec == 1
         self._xw_tile_arg = xw_tile
+        # (before the variables exist: a refused shape leaves no variable scope behind)
+        self._check_lds((self._schedule[:2] if self._schedule else (backward,)) if train else ())
 
         dev = input_images.device
         if tuple(input_images.shape) != (self.batch_size, canvas_size * canvas_size) or \
@@ -1004,9 +1056,15 @@ class AIRModel:
         self._schedule = None                     # an explicit order ends a schedule
         self._set_order(backward)
 
+    def _check_lds(self, orders):
+        Hs, Hh, Hz = self.scale_hidden_units, self.shift_hidden_units, self.z_pres_hidden_units
+        check_step_lds(self.max_steps, self.canvas_size, self.windows_size, Hs, Hh, Hz, max(Hs, Hh, Hz),
+                       [self._ORDERS[o] for o in orders])
+
     def _set_order(self, backward):
         if backward == self.backward:
             return False
+        self._check_lds((backward,))
         self.release_graph()
         self.backward = backward
         self._literal = self._ORDERS[backward]

@@ -347,6 +347,7 @@ extern "C" int air_colsum(const air_colsum_t* probs, int count, void* stream) {
 extern "C" int air_heads_out_wgrad(const float* d_out7, const float* hid, float* dwout, float* dbout,
                                    int rows, int Hs, int Hh, int Hz, int wout_ld, void* stream) {
     if (!d_out7 || !hid || !dwout || !dbout || rows <= 0 || Hs <= 0 || Hh <= 0 || Hz <= 0) return AIR_EINVAL;
+    if (wout_ld < Hs || wout_ld < Hh || wout_ld < Hz) return AIR_EINVAL;       // a row holds its head's whole hidden segment
     hipLaunchKernelGGL(heads_out_wgrad_kernel, dim3(7), dim3(THREADS), 0, air_stream(stream),
                        d_out7, hid, dwout, dbout, rows, Hs, Hh, Hz, wout_ld);
     AIR_CHECK_LAUNCH();

@@ -597,9 +597,12 @@ __global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
 
 // the canvas is staged in LDS only when one prefetch pass covers it (PF * THREADS floats, see the kernels)
 size_t attend_canvas_floats(int C) { return (size_t)C * C <= 10 * (size_t)THREADS ? (size_t)C * C : 0; }
-size_t attend_smem(int C, int w, int HT) {
-    return (16 + MAX_STEPS + 8 * w + 4 + ((HT + 3) & ~3) + 7 * (size_t)HT + MAX_STEPS * (size_t)HT + attend_canvas_floats(C)) * sizeof(float);
+// (sh_wout is [7][wout_ld]: the caller's row stride, which may be padded beyond the widest head)
+size_t attend_smem(int C, int w, int HT, int wout_ld) {
+    return (16 + MAX_STEPS + 8 * w + 4 + ((HT + 3) & ~3) + 7 * (size_t)wout_ld + MAX_STEPS * (size_t)HT + attend_canvas_floats(C)) * sizeof(float);
 }
+// a row of wout holds the hidden segment of its unit's head: the stride must cover the widest head
+bool wout_ld_ok(int wout_ld, int Hs, int Hh, int Hz) { return wout_ld >= Hs && wout_ld >= Hh && wout_ld >= Hz; }
 size_t attend_bwd_smem(int C, int w) {
     return (24 + 8 * w + w + 4 + attend_canvas_floats(C)) * sizeof(float);
 }
@@ -623,8 +626,9 @@ extern "C" int air_attend_fwd(const air_attend_fwd_t* a, void* stream) {
         !a->dyn || !a->out7 || !a->att || !a->window)
         return AIR_EINVAL;
     if (a->B <= 0 || a->N <= 0 || a->C < 2 || a->w < 2 || a->Hs <= 0 || a->Hh <= 0 || a->Hz <= 0) return AIR_EINVAL;
+    if (!wout_ld_ok(a->wout_ld, a->Hs, a->Hh, a->Hz)) return AIR_EINVAL;
     if (a->w > 64 || a->N > MAX_STEPS) return AIR_ELIMIT;
-    const size_t lds = attend_smem(a->C, a->w, 2 * a->Hs + 2 * a->Hh + a->Hz);
+    const size_t lds = attend_smem(a->C, a->w, 2 * a->Hs + 2 * a->Hh + a->Hz, a->wout_ld);
     int rc = ensure_lds(attend_fwd_kernel, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(attend_fwd_kernel, dim3(a->B, a->N), dim3(THREADS), lds, air_stream(stream), *a);
@@ -637,6 +641,7 @@ extern "C" int air_attend_bwd(const air_attend_bwd_t* a, void* stream) {
         !a->att || !a->d_window || !a->d_sxy_write || !a->d_hid || !a->d_out7)
         return AIR_EINVAL;
     if (a->B <= 0 || a->N <= 0 || a->C < 2 || a->w < 2 || a->Hs <= 0 || a->Hh <= 0 || a->Hz <= 0) return AIR_EINVAL;
+    if (!wout_ld_ok(a->wout_ld, a->Hs, a->Hh, a->Hz)) return AIR_EINVAL;
     if (a->w > 64) return AIR_ELIMIT;
     const size_t lds = attend_bwd_smem(a->C, a->w);
     int rc = ensure_lds(attend_bwd_kernel, lds);
