@@ -37,8 +37,9 @@ extern "C" {
  *    (air_step_job_t.ad_*, air_adam_clip_step_blocks), the banded compose (air_write_fwd_t.rec_part / bands,
  *    air_finalize_parts, air_write_bwd_t.fin_rec_part ..), air_adam_clip_step_factored; added: `literal` 3 / 4 of air_write_bwd, air_shuffle_batch_*
  * 5: added air_shuffle_batch_dequeue_many, air_batch_gather, air_summaries; removed `literal` 1 and 3 of the sampler
- *    backward (backward="taps" / "reference_blocked") */
-#define AIR_ABI_VERSION 5
+ *    backward (backward="taps" / "reference_blocked")
+ * 6: added air_step_lds (the dynamic LDS of the sampler launches, answered by the functions that size them) */
+#define AIR_ABI_VERSION 6
 
 #define AIR_EINVAL   (-1)   /* bad dimension / null pointer            */
 #define AIR_ELIMIT   (-2)   /* size exceeds what the kernel supports    */
@@ -624,6 +625,17 @@ int air_render(const air_render_t* a, void* stream);
  * caller counts its calls.  The same (seed, call) gives the same numbers; either count may be 0, not both. */
 int air_philox_fill(float* normals, int64_t n_normal, float* uniforms, int64_t n_uniform,
                     uint64_t seed, uint64_t call, void* stream);
+
+/* Dynamic LDS, in bytes per workgroup, of the launches of a step whose need grows with the hyper-parameters, from the
+ * functions the entry points themselves size their launches with (no GPU is touched): N steps, a C x C canvas, w x w
+ * windows, head widths Hs / Hh / Hz, wout_ld the row stride of wout (>= the widest head).  write_bwd_exact: literal 0 of
+ * air_write_bwd; write_bwd_graph: literals 2 and 4, with as many tap phases resident as the entry point would choose.
+ * limit: what a workgroup may hold -- an entry point answers AIR_ELIMIT beyond it.  AIR_EINVAL: null out, a size < 1,
+ * wout_ld below a head width. */
+typedef struct {
+    int64_t attend_fwd, attend_bwd, write_fwd, render, write_bwd_exact, write_bwd_graph, limit;
+} air_step_lds_t;
+int air_step_lds(int N, int C, int w, int Hs, int Hh, int Hz, int wout_ld, air_step_lds_t* out);
 
 #ifdef __cplusplus
 }

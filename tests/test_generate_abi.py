@@ -37,7 +37,7 @@ def test_generation_entry_points_are_exported_and_bound(H):
         assert name in H.EXPORTED_SYMBOLS
         fn = getattr(H.lib(), name)
         assert fn.restype is C.c_int and fn.argtypes is not None
-    assert H.lib().air_abi_version() == 5                    # additive: the version does not move
+    assert H.lib().air_abi_version() == H.ABI_VERSION == 6
 
 
 def test_descriptor_layout_matches_c(H, tmp_path):

@@ -389,17 +389,13 @@ def test_inference_graph_replay_equals_eager(am):
     assert float(inf.loss) != l0
 
 
-def test_first_lstm_step_in_the_xwx_launch_matches_the_default_path(am, monkeypatch):
-    """AIR_STEP0_FUSION=1 (x.Wx un-split with the zero-state first LSTM step in its epilogue, AIR_EPI_LSTM_FWD0)
+def test_first_lstm_step_in_the_xwx_launch_matches_the_default_path(am):
+    """AIRModel(step0_fusion=True) (x.Wx un-split with the zero-state first LSTM step in its epilogue, AIR_EPI_LSTM_FWD0)
     gives the same forward as the default split-K product + pointwise first step, up to the summation order
     of the K = 2500 contraction."""
     outs = {}
     for fused in (False, True):
-        if fused:
-            monkeypatch.setenv("AIR_STEP0_FUSION", "1")
-        else:
-            monkeypatch.delenv("AIR_STEP0_FUSION", raising=False)
-        model, *_ = _make(am, 16, True, blank=True)
+        model, *_ = _make(am, 16, True, blank=True, step0_fusion=(True if fused else None))
         assert model._fuse_step0 == fused
         model.forward()
         torch.cuda.synchronize()

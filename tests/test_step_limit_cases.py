@@ -86,3 +86,14 @@ def test_constructor_lds_arithmetic():
     am.check_step_lds(3, 200, 32, 64, 64, 64, 64)
     with pytest.raises(NotImplementedError, match="air_write_bwd"):
         am.check_step_lds(3, 200, 32, 64, 64, 64, 64, (2,))
+    # the query itself: the same figure serves literals 2 and 4; a null `out`, a non-positive size and a row stride of wout
+    # below a head width are AIR_EINVAL
+    assert dict(am.step_lds_bytes(16, 50, 28, 64, 64, 64, 64, (4,)))["air_write_bwd (literal 4)"] == need["air_write_bwd (literal 2)"]
+    import ctypes as C
+    lib, out, good = H.lib(), H.StepLds(), (16, 50, 28, 64, 64, 64, 64)
+    assert lib.air_step_lds(*good, C.byref(out)) == 0 and out.limit == 160 * 1024
+    assert lib.air_step_lds(*good, None) == -1
+    for i in range(7):
+        for bad in (0, -1):
+            assert lib.air_step_lds(*(good[:i] + (bad,) + good[i + 1:]), C.byref(out)) == -1, (i, bad)
+    assert lib.air_step_lds(16, 50, 28, 64, 65, 64, 64, C.byref(out)) == -1

@@ -118,3 +118,28 @@ def test_model_tf_checkpoint_roundtrip(tmp_path):
     for k, v in m.variables.items():
         assert torch.equal(v, before[k]), k
     assert torch.equal(m.store.m, mm) and torch.equal(m.store.v, vv) and int(m.global_step) == 3
+
+
+@pytest.mark.gpu
+def test_bundle_with_one_adam_slot_of_a_variable_is_refused_before_anything_is_written(tmp_path):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    from air import air_model as am
+    from oracle import air_oracle as ao
+    am.reset_default_graph()
+    m = am.AIRModel(torch.zeros(4, 2500, device="cuda"), None, cnn=False, train=True, **dict(ao.TRAINING_HP))
+    shapes = {k: tuple(v.shape) for k, v in m.store.variables.items()}
+    tensors = tfc.model_to_tensors(m.state_dict(), shapes)
+    lone = [k for k in tensors if k.endswith("rnn/bias/Adam_1")]
+    assert len(lone) == 1
+    del tensors[lone[0]]
+    prefix = str(tmp_path / "air-model-half")
+    tfc.save_checkpoint(prefix, tensors)
+    m.store.initialize(7)
+    m.store.m.fill_(0.5)
+    m.store.istate[0] = 11
+    params, slots = m.store.params.clone(), m.store.m.clone()
+    with pytest.raises(ValueError, match="only one of the two Adam slots"):
+        m.load_tf_checkpoint(prefix)
+    assert torch.equal(m.store.params, params) and torch.equal(m.store.m, slots) and int(m.global_step) == 11

@@ -15,7 +15,7 @@ import torch  # noqa: F401  -- FIRST: torch brings its own libamdhip64; loading 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AIR_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libair_hip.so")   # override: A/B builds in tools/
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 # enums (keep in sync with include/air_hip.h)
 DYN_PRIOR_LOG_ODDS, DYN_TEMPERATURE, DYN_STOP_THRESHOLD, DYN_LEARNING_RATE, DYN_CLIP_NORM = 0, 1, 2, 3, 4
@@ -140,6 +140,13 @@ class Render(C.Structure):
 
 MAX_STEPS = 16
 
+
+class StepLds(C.Structure):
+    """air_step_lds_t: dynamic LDS per workgroup, in bytes, of the sampler launches of a step, and the limit"""
+    _fields_ = [(k, C.c_int64) for k in ("attend_fwd", "attend_bwd", "write_fwd", "render", "write_bwd_exact",
+                                         "write_bwd_graph", "limit")]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -184,6 +191,7 @@ _SIGNATURES = {
     "air_scene_records": (C.c_int, [C.POINTER(SceneRecords), _p]),
     "air_render": (C.c_int, [C.POINTER(Render), _p]),
     "air_philox_fill": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.c_uint64, C.c_uint64, _p]),
+    "air_step_lds": (C.c_int, [C.c_int] * 7 + [C.POINTER(StepLds)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -124,8 +124,7 @@ class VariableStore:
         # panels (the four gates of four units in 32 contiguous bytes per row), in two pieces (Wx rows, Wh rows).
         # Maintained by Adam next to the row-major shadow (which the transposed data-gradient products keep reading);
         # Wx has no other reader than the hoisted x.Wx, so its row-major shadow is dropped ("exclusive") unless the
-        # canvas is large (the throughput tiling of D > 4096 reads row-major lines) or the first-step fusion is off.
-        self.fuse_step0 = os.environ.get("AIR_STEP0_FUSION", "1") != "0"
+        # canvas is large (the throughput tiling of D > 4096 reads row-major lines) or the shape cannot fuse the first step.
         pan, poff = [], 0
         self.panel_off = {}
 
@@ -139,7 +138,7 @@ class VariableStore:
         o = self.offsets["lstm_kernel"]
         # (its one reader is the x.Wx launch that also runs the first step -- which needs D % 4 == 0 and R % 4 == 0: a shape that
         # cannot fuse keeps the row-major shadow of Wx; the throughput tiling of a large canvas reads row-major lines: no panel)
-        if self.fuse_step0 and D <= 4096 and D % 4 == 0 and R % 4 == 0:
+        if D <= 4096 and D % 4 == 0 and R % 4 == 0:
             add_panel("Wx", o, D, 4 * R, True, exclusive=True)
         add_panel("Wh", o + D * 4 * R, R, 4 * R, True)
         for k, shp in fused.items():
@@ -317,53 +316,45 @@ def _st_matrices(a):
                         torch.stack([z, a[..., 0], a[..., 2]], -1)], -2)
 
 
-LDS_LIMIT = 160 * 1024      # bytes of LDS a workgroup may hold on gfx950 (air_grant_lds, csrc/air_common.h: AIR_ELIMIT beyond)
+def _step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld):
+    """air_step_lds_t of these hyper-parameters: the library's own sizing functions answer (no GPU is touched)"""
+    lds = H.StepLds()
+    H.check(H.lib().air_step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, C.byref(lds)), "air_step_lds")
+    return lds
 
 
 def step_lds_bytes(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, literals=()):
-    """Dynamic LDS, in bytes, of every launch of the step whose need grows with the hyper-parameters: [(launch, bytes)].
-    Each line restates the C++ function that sizes the launch (quoted above it): change them together.  `literals`: the
+    """Dynamic LDS, in bytes, of every launch of the step whose need grows with the hyper-parameters: [(launch, bytes)],
+    as the functions that size the launches give it (air_step_lds, csrc/air_sampler_common.h).  `literals`: the
     air_write_bwd_t.literal values of the sampler-backward orders a train model runs (none for a test model)."""
-    N, C, w = max_steps, canvas_size, windows_size
-    HT = 2 * Hs + 2 * Hh + Hz
-    MAX_STEPS = H.MAX_STEPS
-    r4 = lambda n: (n + 3) & ~3  # noqa: E731
-    # air_sampler.hip  attend_canvas_floats(C): C * C <= 10 * THREADS ? C * C : 0                          (THREADS = 256)
-    canvas = C * C if C * C <= 10 * 256 else 0
-    need = [
-        # air_sampler.hip  attend_smem(C, w, HT, wout_ld):
-        #   (16 + MAX_STEPS + 8 * w + 4 + ((HT + 3) & ~3) + 7 * wout_ld + MAX_STEPS * HT + attend_canvas_floats(C)) * 4
-        ("air_attend_fwd", (16 + MAX_STEPS + 8 * w + 4 + r4(HT) + 7 * wout_ld + MAX_STEPS * HT + canvas) * 4),
-        # air_sampler.hip  write_smem(N, C, w): (16 + 7 * MAX_STEPS + N * (8 * C + w * w)) * 4
-        #   (with wb_order at least WB_ORDER_MAX * 4 = 16 KB: never the binding term)
-        ("air_write_fwd", (16 + 7 * MAX_STEPS + N * (8 * C + w * w)) * 4),
-        # air_generate.hip  render_smem(N, C, w): (2 * MAX_STEPS + N * (8 * C + w * w)) * 4
-        ("air_render", (2 * MAX_STEPS + N * (8 * C + w * w)) * 4),
-    ]
+    lds = _step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld)
+    need = [("air_attend_fwd", lds.attend_fwd), ("air_write_fwd", lds.write_fwd), ("air_render", lds.render)]
     if literals:
-        # air_sampler.hip  attend_bwd_smem(C, w): (24 + 8 * w + w + 4 + attend_canvas_floats(C)) * 4
-        need.append(("air_attend_bwd", (24 + 8 * w + w + 4 + canvas) * 4))
+        need.append(("air_attend_bwd", lds.attend_bwd))
     for lit in sorted(set(literals)):
-        if lit >= 2:
-            # air_sampler_write_bwd.hip  write_bwd_graph_smem(C, w, allph):
-            #   (136 + 8 * C + ((C + 3) & ~3) + 8 * C + ((8 * w + 3) & ~3) + ((w * w + 3) & ~3) + (allph ? 5 : 1) * ((C * C + 3) & ~3)) * 4
-            #   allph = write_bwd_graph_smem(C, w, true) <= 80 * 1024                                     (air_write_bwd)
-            graph = lambda allph: (136 + 8 * C + r4(C) + 8 * C + r4(8 * w) + r4(w * w) + (5 if allph else 1) * r4(C * C)) * 4  # noqa: E731
-            need.append(("air_write_bwd (literal %d)" % lit, graph(graph(True) <= 80 * 1024)))
-        else:
-            # air_sampler_write_bwd.hip  write_bwd_smem(C, w): (64 + 8 * C + C + 8 * w + w * w + C * w + C * C) * 4
-            need.append(("air_write_bwd (literal 0)", (64 + 8 * C + C + 8 * w + w * w + C * w + C * C) * 4))
+        need.append(("air_write_bwd (literal %d)" % lit, lds.write_bwd_graph) if lit >= 2 else
+                    ("air_write_bwd (literal 0)", lds.write_bwd_exact))
     return need
 
 
 def check_step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, literals=()):
     """NotImplementedError when a launch of the step would need more LDS than a workgroup can hold"""
+    limit = _step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld).limit
     for launch, nbytes in step_lds_bytes(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, literals):
-        if nbytes > LDS_LIMIT:
+        if nbytes > limit:
             raise NotImplementedError(
                 "canvas_size = %d with max_steps = %d and windows_size = %d exceeds the HIP path's limits: %s would need %d bytes of "
                 "LDS per workgroup, a workgroup holds %d (the taps and windows of all steps of an image, or a whole canvas, "
-                "live in LDS) -- reduce canvas_size or max_steps" % (canvas_size, max_steps, windows_size, launch, nbytes, LDS_LIMIT))
+                "live in LDS) -- reduce canvas_size or max_steps" % (canvas_size, max_steps, windows_size, launch, nbytes, limit))
+
+
+def _carve_noise(normals, uniforms, N, B, Z, d):
+    """(eps_scale [N,B,1], eps_shift [N,B,2], eps_z [N,B,Z], eps_x [N,B,d], u [N,B]): views of one normals / uniforms pair
+    (one contiguous buffer each: one Philox launch fills them)"""
+    sizes = (N * B, 2 * N * B, N * B * Z, N * B * d)
+    assert normals.numel() == sum(sizes) and uniforms.numel() == N * B
+    es, exy, ez, ex = torch.split(normals, sizes)
+    return es.view(N, B, 1), exy.view(N, B, 2), ez.view(N, B, Z), ex.view(N, B, d), uniforms.view(N, B)
 
 
 class AIRModel:
@@ -378,7 +369,7 @@ class AIRModel:
                  learning_rate=1e-3, gradient_clipping_norm=100.0, cnn=True, cnn_filters=8,
                  num_summary_images=60, train=False, reuse=False, scope="air",
                  annealing_schedules=None, seed=0, gemm_precision=None, backward="reference", noise_seed=None,
-                 bf16_twins=None, dp_exchange=None, xw_tile=None, xwx_twin_staging="lds_dma"):
+                 bf16_twins=None, dp_exchange=None, xw_tile=None, xwx_twin_staging="lds_dma", step0_fusion=None):
         if cnn:
             # reference :510-533; every caller passes cnn=False (training.py:108, demo.py:24)
             raise NotImplementedError("cnn=True front-end is outside the accelerated hot path; pass cnn=False")
@@ -465,6 +456,7 @@ class AIRModel:
         # the rounding the fp32-operand kernels apply on the way into LDS).  bf16_twins=False keeps fp32 operands.
         self._twins = (True if bf16_twins is None else bool(bf16_twins)) and self._prec == 1
         self._xw_tile_arg = xw_tile
+        self._step0_fusion_arg = step0_fusion
         # (before the variables exist: a refused shape leaves no variable scope behind)
         self._check_lds((self._schedule[:2] if self._schedule else (backward,)) if train else ())
 
@@ -571,15 +563,9 @@ class AIRModel:
         self.sched = torch.from_numpy(arr.view(np.uint8).copy()).to(dv)
 
         # noise: normals then uniforms, one contiguous buffer each (one Philox launch)
-        n_norm = N * B * (1 + 2 + Z + d)
-        self.normals = f(n_norm)
+        self.normals = f(N * B * (1 + 2 + Z + d))
         self.uniforms = f(N * B)
-        o = 0
-        self.eps_scale = self.normals[o:o + N * B].view(N, B, 1); o += N * B
-        self.eps_shift = self.normals[o:o + 2 * N * B].view(N, B, 2); o += 2 * N * B
-        self.eps_z = self.normals[o:o + N * B * Z].view(N, B, Z); o += N * B * Z
-        self.eps_x = self.normals[o:o + N * B * d].view(N, B, d)
-        self.u = self.uniforms.view(N, B)
+        self.eps_scale, self.eps_shift, self.eps_z, self.eps_x, self.u = _carve_noise(self.normals, self.uniforms, N, B, Z, d)
 
         # per-image results of the compose kernel (no running state lives across kernels any more)
         self.run_loss = f(B)
@@ -604,10 +590,9 @@ class AIRModel:
         # split-K product + the pointwise first step, which is why round 2 kept it off.  On the gate-interleaved PANEL twin
         # (VariableStore.panels) the tile's rows are 32 contiguous bytes: default for the bf16 path now (and for its
         # twins-off form, so that the two stay bit-identical); the fp32 path keeps the split-K product.
-        # AIR_STEP0_FUSION=0 / 1 forces it off / on.
-        env0 = os.environ.get("AIR_STEP0_FUSION")
-        want0 = (env0 == "1") if env0 in ("0", "1") else (self._prec == 1 and D <= 4096)
-        self._fuse_step0 = want0 and self.store.fuse_step0 and R % 4 == 0 and D % 4 == 0 and xw_tile is None
+        # AIRModel(step0_fusion=False / True) forces it off / on, where the shape allows it.
+        want0 = (self._prec == 1 and D <= 4096) if self._step0_fusion_arg is None else bool(self._step0_fusion_arg)
+        self._fuse_step0 = want0 and R % 4 == 0 and D % 4 == 0 and xw_tile is None
         self._xw_slabs = 1 if self._fuse_step0 else self.lib.air_gemm_slabs(D, self._xw_ksplit)
         self.xw = f(self._xw_slabs, B, 4 * R)            # x.Wx (split-K slabs when not fused)
         self.gates_pre = f(B, 4 * R)
@@ -700,20 +685,40 @@ class AIRModel:
                   "air_attend_bwd": "attend_bwd_kernel", "air_write_fwd": "write_fwd_kernel<1024>",
                   "air_write_bwd": "write_bwd_kernel", "air_finalize": "finalize_kernel",
                   "air_grad_sqnorm": "grad_sqnorm_kernel", "air_adam_clip_step": "adam_clip_kernel",
-                  "air_vae_bottleneck_fwd": "bottleneck_fwd_kernel<256>", "air_vae_bottleneck_bwd": "bottleneck_bwd_kernel<256>"}
+                  "air_adam_clip_step_panels": "adam_panels_kernel", "air_scene_records": "scene_records_kernel",
+                  "air_render": "render_kernel", "air_philox_fill": "philox_fill_kernel"}
 
     def _call(self, name, *args, nbytes=0, flops=0, tag=None):
         fn = getattr(self.lib, name)
         kernel = self._KERNEL_OF.get(name)
         if name == "air_lstm_first_step":                    # instantiated per slab count: <4> in the train step, <0> = run-time count
             kernel = "lstm_first_step_kernel<%d>" % (4 if args[1] == 4 else 0)
-        if name in ("air_vae_bottleneck_fwd", "air_vae_bottleneck_bwd"):   # instantiated per operand form (bf16 twins or fp32)
-            kernel = ("bottleneck_%s_kernel<256, %s>" % (name[-3:], "true" if self._twins else "false") if self._prec == 1
-                      else "bottleneck_%s_f32_kernel<256>" % name[-3:])
+        if name in ("air_vae_bottleneck_fwd", "air_vae_bottleneck_bwd"):   # (bf16 path only) instantiated per operand form: bf16 twins or fp32 operands
+            kernel = "bottleneck_%s_kernel<256, %s>" % (name[-3:], "true" if self._twins else "false")
         if name == "air_wgrad_grouped":
             kernel = "wgrad_grouped_bf16_kernel" if self._prec else "wgrad_grouped_kernel"
         return _Op(tag or name, lambda s, fn=fn, args=args, name=name: H.check(fn(*args, s), name),
                    nbytes=nbytes, flops=flops, kernel=kernel)
+
+    def _generative_ops(self, x, x16, k, act, act16, out, eps_x, aux_scale, first=0):
+        """The generative layers from index `first` on and gen_mean (vae.py:26-41), reading x [N*B, k] (twin x16): softplus
+        layers into act[i] / act16[i], then sigmoid(. + aux_scale * eps_x) into out.  The forward and the generation
+        lists are built from this one set of descriptors."""
+        st, P, tw = self.store, self.store.P, self._twins
+        T = (lambda name: st.P16[name]) if tw else (lambda name: None)  # noqa: E731
+        TP = (lambda name: st.panel(name)) if tw else (lambda name: None)  # noqa: E731
+        NB, d = self.max_steps * self.batch_size, st.dims["d"]
+        ops = []
+        for i in range(first, len(self.vae_generative_units)):
+            u = self.vae_generative_units[i]
+            ops.append(self._gemm(x, P["gen%d_w" % i], act[i], NB, u, k, k, u, u,
+                                  bias=P["gen%d_b" % i], act=H.ACT_SOFTPLUS, tag="vae_gen",
+                                  A16=x16, B16=T("gen%d_w" % i), C16=act16[i], B16p=TP("gen%d_w" % i)))
+            x, x16, k = act[i], act16[i], u
+        ops.append(self._gemm(x, P["out_w"], out, NB, d, k, k, d, d, bias=P["out_b"],
+                              act=H.ACT_SIGMOID_NOISE, aux=eps_x, ldaux=d, aux_scale=aux_scale, tag="vae_out",
+                              A16=x16, B16=T("out_w"), B16p=TP("out_w")))
+        return ops
 
     def _build_programs(self):
         st, P, G = self.store, self.store.P, self.store.G
@@ -728,10 +733,8 @@ class AIRModel:
         tw = self._twins
         P16 = st.P16
         T = (lambda k: P16[k]) if tw else (lambda k: None)  # noqa: E731
-        # panel-blocked twins (forward products only; AIR_NO_PANELS=1 keeps every product on the row-major shadow)
-        use_pan = tw and os.environ.get("AIR_NO_PANELS") != "1"
-        TP = (lambda k: st.panel(k)) if use_pan else (lambda k: None)  # noqa: E731
-        self._use_panels = use_pan
+        # panel-blocked twins (forward products only; None for a matrix the store built no panel of: row-major shadow)
+        TP = (lambda k: st.panel(k)) if tw else (lambda k: None)  # noqa: E731
         Wx16, Wh16 = (P16["lstm_kernel"][:D], P16["lstm_kernel"][D:]) if tw else (None, None)
         o16 = lambda t, i=None: (None if t is None else (t if i is None else t[i]))  # noqa: E731
         imgs = self.input_images
@@ -740,7 +743,7 @@ class AIRModel:
         NB = N * B
         fwd = []
         self._xwx_twin_op = None
-        if getattr(self, "_gen", None) is not None:
+        if self._gen is not None:
             self._gen["ops"] = None             # (the generation launch list is rebuilt with these; its buffers stay)
 
         def gemm(*args, **kw):
@@ -751,13 +754,13 @@ class AIRModel:
                         self._seed, _ptr(imgs if self.images16 is not None else None), _ptr(self.images16),
                         imgs.numel() if self.images16 is not None else 0)
         noise_bytes = 4 * (self.normals.numel() + self.uniforms.numel())
-        if tw and st.wx_exclusive and not (self._fuse_step0 and use_pan):
+        if tw and st.wx_exclusive and not self._fuse_step0:
             # the store keeps ONLY the panel twin of Wx (VariableStore: "exclusive"), and this model cannot read it: its
             # largest operand is converted from fp32 inside the kernel -- correct, and a silent perf cliff otherwise
             import warnings
             warnings.warn("AIRModel(scope=%r): bf16 twins are on but x.Wx reads the fp32 Wx (the scope's store maintains only the "
-                          "panel twin of Wx; this model does not fuse the first step / use panels: D %% 4 = %d, xw_tile / "
-                          "AIR_NO_PANELS / AIR_STEP0_FUSION set?)" % (self.scope, D % 4), RuntimeWarning, stacklevel=3)
+                          "panel twin of Wx; this model does not fuse the first step: xw_tile or step0_fusion=False given?)"
+                          % self.scope, RuntimeWarning, stacklevel=3)
         if self._fuse_step0:
             # the first step rides in the x.Wx launch: h_0 = c_0 = 0 (zero_state, :540), so its gates are x.Wx + b
             # (twins: the panel twin of Wx is the ONLY bf16 form of Wx that is maintained when the store made it exclusive)
@@ -802,7 +805,7 @@ class AIRModel:
                            extra_bytes=4 * B * R * 7, tag="lstm_fwd",
                            A16=o16(self.h16, t), B16=Wh16, q2_16=o16(self.h16, t + 1), B16p=TP("Wh"))
             gemm(self.h[t], Wh, self.gates_pre, B, 4 * R, R, R, 4 * R, 4 * R, **lstm_kw)
-            if t == 1 and self._fuse_step0 and use_pan:
+            if t == 1 and self._fuse_step0 and tw:
                 # With the first step fused into it, x.Wx is ONE round of 160 KB of LDS per workgroup: prologue workgroups in
                 # that launch would each take a whole CU.  The LSTM steps read neither the noise, nor dyn, nor the image
                 # twin (their first consumer is attend_fwd): the prologue rides in the first of them instead (16 KB of LDS)
@@ -829,45 +832,32 @@ class AIRModel:
         # bf16 path: on.  fp32 path (the parity precision): OFF -- its exact-fp32 form is 3e-6 from the two launches (another
         # fp32 order of a K = 256 sum) and saves 7 us, but over 32 seeds x 60 k iterations 4 runs never separate one count
         # class with it against 0 of 32 with two launches (profiles/r04_seed_sweep_fp32_bottleneck_*, r05_sweep_fp32_bottleneck_*).
-        # AIR_BOTTLENECK_FUSION=0 / 1 forces it off / on (AIR_NO_BOTTLENECK_FUSION=1: the older spelling of off).
-        env_b = os.environ.get("AIR_BOTTLENECK_FUSION")
-        nofuse = ((env_b == "0") if env_b in ("0", "1") else self._prec == 0) or os.environ.get("AIR_NO_BOTTLENECK_FUSION") == "1"
-        # (fp32 path: the exact-fp32 form of the kernel, 2 Z <= 104)
-        fuse_f = (not nofuse and len(gen_u) >= 1 and k == 256 and Z <= (64 if self._prec == 1 else 52) and Z % 2 == 0
-                  and gen_u[0] % 4 == 0)
-        first_gen = 0
+        # (the library keeps the exact-fp32 form of the two kernels, air_bottleneck_*_t.exact_fp32 = 1: the model does not use it)
+        fuse = self._prec == 1
+        fuse_f = fuse and len(gen_u) >= 1 and k == 256 and Z <= 64 and Z % 2 == 0 and gen_u[0] % 4 == 0
         self._zs_fused = fuse_f
         if fuse_f:
             self.zs = self._zs_pad[:, :, :Z]                 # (the sample lives in the padded rows)
             bf = H.BottleneckFwd(_ptr(x), _ptr(P["ml_w"]), _ptr(P["ml_b"]), _ptr(self.eps_z), _ptr(P["gen0_w"]),
                                  _ptr(P["gen0_b"]), _ptr(self.ml), _ptr(self._zs_pad), _ptr(self.gen_act[0]), NB, k, Z, gen_u[0], k,
                                  _ptr(self._zs16_pad), _ptr(self.gen_act16[0]), _ptr(x16), _ptr(T("ml_w")), _ptr(T("gen0_w")),
-                                 0 if self._prec == 1 else 1, self._zs_ld)
+                                 0, self._zs_ld)
             keep.append(bf)
             fwd.append(self._call("air_vae_bottleneck_fwd", C.byref(bf),
                                   nbytes=4 * (NB * (k + 4 * Z + gen_u[0]) + k * 2 * Z + Z * gen_u[0]),
                                   flops=2 * NB * (k * 2 * Z + Z * gen_u[0]), tag="vae_bottleneck"))
-            x, x16, k, first_gen = self.gen_act[0], self.gen_act16[0], gen_u[0], 1
+            fwd += self._generative_ops(self.gen_act[0], self.gen_act16[0], gen_u[0], self.gen_act, self.gen_act16, self.vrec,
+                                        self.eps_x, float(self.vae_likelihood_std), first=1)
         else:
             fwd.append(self._gemm(x, P["ml_w"], self.ml, NB, 2 * Z, k, k, 2 * Z, 2 * Z, bias=P["ml_b"],
                                   epi=H.EPI_REPARAM_FWD, p=(self.eps_z,), q=(self.zs,),
                                   extra_bytes=8 * NB * Z, tag="ml_reparam", q0_16=self.zs16))
-            x, x16, k = self.zs, self.zs16, Z
-        for i in range(first_gen, len(gen_u)):
-            u = gen_u[i]
-            fwd.append(self._gemm(x, P["gen%d_w" % i], self.gen_act[i], NB, u, k, k, u, u,
-                                  bias=P["gen%d_b" % i], act=H.ACT_SOFTPLUS, tag="vae_gen",
-                                  A16=x16, B16=T("gen%d_w" % i), C16=self.gen_act16[i], B16p=TP("gen%d_w" % i)))
-            x, x16, k = self.gen_act[i], self.gen_act16[i], u
-        fwd.append(self._gemm(x, P["out_w"], self.vrec, NB, d, k, k, d, d, bias=P["out_b"],
-                              act=H.ACT_SIGMOID_NOISE, aux=self.eps_x, ldaux=d,
-                              aux_scale=float(self.vae_likelihood_std), tag="vae_out", A16=x16, B16=T("out_w"), B16p=TP("out_w")))
+            fwd += self._generative_ops(self.zs, self.zs16, Z, self.gen_act, self.gen_act16, self.vrec,
+                                        self.eps_x, float(self.vae_likelihood_std))
         # more (image, step) items than CUs: the graph-order write backward takes them longest first (one extra workgroup of
-        # the compose launch sorts them; air_write_fwd_t.wb_order).  AIR_WB_ORDER=0 / 1 forces it off / on.
-        env_o = os.environ.get("AIR_WB_ORDER")
-        want_o = (env_o == "1") if env_o in ("0", "1") else (NB > 256)
+        # the compose launch sorts them; air_write_fwd_t.wb_order)
         self._wb_order = (torch.arange(NB, dtype=torch.int32, device=imgs.device)
-                          if (want_o and self.train and self._literal >= 2 and NB <= 4096) else None)
+                          if (self.train and self._literal >= 2 and 256 < NB <= 4096) else None)
         wf = H.WriteFwd(_ptr(self.vrec), _ptr(self.ml), _ptr(imgs), _ptr(self.dyn), _ptr(self.att),
                         _ptr(self._recon), _ptr(self._rec_loss), _ptr(self.d_recon if self.train else None),
                         _ptr(self.run_loss), _ptr(self.run_digits), _ptr(self._loss_item), B, N, Cc, w, Z, _ptr(self._wb_order))
@@ -948,15 +938,14 @@ class AIRModel:
                                   aux=self.gen_act[i], ldaux=u, actgrad=H.GRAD_SOFTPLUS, tag="dgrad_gen",
                                   A16=dy16, B16=T(wname), C16=self.d_gen16[i]))
             dy, dy16, n_out, wname = self.d_gen[i], self.d_gen16[i], u, "gen%d_w" % i
-        fuse_b = (not nofuse and len(gen_u) >= 1 and len(rec_u) >= 1 and gen_u[0] == 256
-                  and Z <= 64 and Z % 2 == 0)
+        fuse_b = fuse and len(gen_u) >= 1 and len(rec_u) >= 1 and gen_u[0] == 256 and Z <= 64 and Z % 2 == 0
         last_rec = len(rec_u)
         if fuse_b:
             # d_gen[0] -> d_z -> (d_mean | d_lv) -> d_rec[last] in ONE launch (vae.py:22-24 and the KL, backwards)
             bb = H.BottleneckBwd(_ptr(dy), _ptr(P["gen0_w"]), _ptr(self.ml), _ptr(self.eps_z), _ptr(self.att), _ptr(self.dyn),
                                  _ptr(P["ml_w"]), _ptr(self.rec_act[-1]), _ptr(self.d_ml), _ptr(self.d_rec[-1]),
                                  NB, rec_u[-1], Z, gen_u[0], _ptr(self.d_ml16), _ptr(self.d_rec16[-1]),
-                                 _ptr(dy16), _ptr(T("gen0_w")), _ptr(T("ml_w")), 0 if self._prec == 1 else 1)
+                                 _ptr(dy16), _ptr(T("gen0_w")), _ptr(T("ml_w")), 0)
             keep.append(bb)
             bwd.append(self._call("air_vae_bottleneck_bwd", C.byref(bb),
                                   nbytes=4 * (NB * (gen_u[0] + 5 * Z + 2 * rec_u[-1]) + Z * gen_u[0] + rec_u[-1] * 2 * Z),
@@ -992,20 +981,15 @@ class AIRModel:
                               extra_bytes=4 * B * R * 15, tag="dh_heads", A16=self.d_hid16, B16=T("whid"),
                               q0_16=o16(self.dgates16, tl), q2_16=(self.dgsum16 if N == 1 else None)))
         # back-propagation through time: the only sequential part of the backward
-        for t in reversed(range(N)):
-            last = (t == N - 1)
-            dc_cur, dc_nxt = self.dc[t % 2], self.dc[(t + 1) % 2]
-            if last:
-                continue
-            else:
-                # d h'[t] = heads[t] + dgates[t+1] . Wh^T, LSTM pointwise backward fused in the epilogue
-                bwd.append(self._gemm(self.dgates[t + 1], Wh, self.dh_cur, B, R, 4 * R, 4 * R, 4 * R, R, tb=1,
-                                      addend=self.dh_heads[t], ldadd=R, epi=H.EPI_LSTM_BWD,
-                                      p=(self.acts[t], self.c[t], self.c[t + 1], dc_nxt),
-                                      q=(self.dgates[t], dc_cur, self.dgsum), i0=1,
-                                      extra_bytes=4 * B * R * 15, tag="bptt_lstm_bwd",
-                                      A16=o16(self.dgates16, t + 1), B16=Wh16, q0_16=o16(self.dgates16, t),
-                                      q2_16=(self.dgsum16 if t == 0 else None)))
+        for t in reversed(range(N - 1)):
+            # d h'[t] = heads[t] + dgates[t+1] . Wh^T, LSTM pointwise backward fused in the epilogue
+            bwd.append(self._gemm(self.dgates[t + 1], Wh, self.dh_cur, B, R, 4 * R, 4 * R, 4 * R, R, tb=1,
+                                  addend=self.dh_heads[t], ldadd=R, epi=H.EPI_LSTM_BWD,
+                                  p=(self.acts[t], self.c[t], self.c[t + 1], self.dc[(t + 1) % 2]),
+                                  q=(self.dgates[t], self.dc[t % 2], self.dgsum), i0=1,
+                                  extra_bytes=4 * B * R * 15, tag="bptt_lstm_bwd",
+                                  A16=o16(self.dgates16, t + 1), B16=Wh16, q0_16=o16(self.dgates16, t),
+                                  q2_16=(self.dgsum16 if t == 0 else None)))
         self._bwd = bwd
 
         # weight + bias grads of all variables: ONE grouped launch (weights are shared across the
@@ -1113,6 +1097,12 @@ class AIRModel:
         if self._twins and self.store.shadow_stale:
             self.store.refresh_shadow(self._stream())
 
+    def _fwd_with_prologue(self, fwd=None):
+        """the forward list (self._fwd, or the variant of it given) with the launch that carries the step prologue
+        (schedules + Philox noise, as extra workgroups) in the place of its plain form"""
+        hi, hop = self._begin_host
+        return [(hop if i == hi else op) for i, op in enumerate(self._fwd if fwd is None else fwd)]
+
     def _run_forward(self, s, finalize=True, twin_x=False):
         """twin_x: x.Wx reads the padded bf16 twin of the image batch.  Only capture_graph may ask for it, and only for a
         step whose predecessor in the SAME replay ran the fp32-operand launch over the same, untouched batch."""
@@ -1126,8 +1116,7 @@ class AIRModel:
             self._begin_sched_only(s)                # (parity tests: the schedules only, the noise buffers hold what was injected)
             run = list(fwd)
         else:
-            hi, hop = self._begin_host               # the launch that carries the step prologue as extra workgroups
-            run = [(hop if i == hi else op) for i, op in enumerate(fwd)]
+            run = self._fwd_with_prologue(fwd)
         self._last_xwx_op = run[0]                   # (what capture_graph records: the op that WAS enqueued)
         for op in run:
             op(s)
@@ -1182,13 +1171,12 @@ class AIRModel:
             st = self.store
             fused = not self._dp()
             npart = self._wgrad_blocks if fused else self.lib.air_optim_num_partials(st.n)
-            if self._twins and len(st.panels) and os.environ.get("AIR_NO_PANELS") != "1":
+            if self._twins and len(st.panels):
                 # (with the panels whether or not THIS model reads them: another model on the scope may)
                 adam = self._call("air_adam_clip_step_panels", _ptr(st.params), _ptr(st.grads), _ptr(st.m), _ptr(st.v),
                                   st.n, _ptr(st.partials), npart, _ptr(self.dyn), _ptr(st.istate), 1.0 / world,
                                   0.9, 0.999, 1e-8, _ptr(st.params16), st.panels, len(st.panels), _ptr(st.params16p),
                                   _ptr(st.gnorm), nbytes=30 * st.n, tag="adam_clip")
-                adam.kernel = "adam_panels_kernel"
             else:
                 adam = self._call("air_adam_clip_step", _ptr(st.params), _ptr(st.grads), _ptr(st.m), _ptr(st.v),
                                   st.n, _ptr(st.partials), npart, _ptr(self.dyn), _ptr(st.istate), 1.0 / world,
@@ -1265,9 +1253,7 @@ class AIRModel:
         """The launches of one single-GPU train step, in order (bench / profiling tools): the EAGER step, whose x.Wx reads
         the caller's fp32 image batch.  Steps 1 .. G-1 of a captured G-step replay without a between_steps hook run the same
         list with the twin-operand x.Wx launch (gemm_xwx_glds_kernel, captured_xwx_kernels()) in its first place."""
-        hi, hop = self._begin_host
-        return ([(hop if i == hi else op) for i, op in enumerate(self._fwd)] + [self._write_bwd_fin] + self._bwd[1:]
-                + [self._wgrad_fused] + self._optimizer_ops())
+        return self._fwd_with_prologue() + [self._write_bwd_fin] + self._bwd[1:] + [self._wgrad_fused] + self._optimizer_ops()
 
     def captured_xwx_kernels(self):
         """Kernel name of the x.Wx launch of every step of the captured replay, in order (None: no train graph): the names
@@ -1444,13 +1430,8 @@ class AIRModel:
             f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dv)  # noqa: E731
             h16 = lambda *s: (torch.zeros(*s, dtype=torch.int16, device=dv) if self._twins else None)  # noqa: E731
             g = self._gen = dict(ops=None)
-            g["normals"], g["uniforms"] = f(N * B * (1 + 2 + Z + d)), f(N * B)          # the layout of _alloc's noise
-            o = 0
-            g["eps_scale"] = g["normals"][o:o + N * B].view(N, B, 1); o += N * B
-            g["eps_shift"] = g["normals"][o:o + 2 * N * B].view(N, B, 2); o += 2 * N * B
-            g["eps_z"] = g["normals"][o:o + N * B * Z].view(N, B, Z); o += N * B * Z
-            g["eps_x"] = g["normals"][o:o + N * B * d].view(N, B, d)
-            g["u"] = g["uniforms"].view(N, B)
+            g["normals"], g["uniforms"] = f(N * B * (1 + 2 + Z + d)), f(N * B)
+            g["eps_scale"], g["eps_shift"], g["eps_z"], g["eps_x"], g["u"] = _carve_noise(g["normals"], g["uniforms"], N, B, Z, d)
             # decode(): the caller's tensors, step-major
             g["in_s"], g["in_xy"], g["in_z"], g["in_p"] = f(N, B), f(N, B, 2), f(N, B, Z), f(N, B)
             g["att"] = f(N, B, H.ATT_STRIDE)
@@ -1466,37 +1447,23 @@ class AIRModel:
         return g
 
     def _build_generate(self, g):
-        """The generation launch lists (see _build_programs for the decoder's GEMM descriptors, which these repeat)."""
-        st, P, dm = self.store, self.store.P, self.store.dims
+        """The generation launch lists; the decoder's GEMMs are the forward's (_generative_ops) on the generation buffers."""
+        dm = self.store.dims
         B, N, NB = self.batch_size, self.max_steps, self.max_steps * self.batch_size
         d, Z = dm["d"], dm["Z"]
-        T = (lambda k: st.P16[k]) if self._twins else (lambda k: None)  # noqa: E731
-        TP = (lambda k: st.panel(k)) if self._use_panels else (lambda k: None)  # noqa: E731
-        gen_u = list(self.vae_generative_units)
         ops = {}
         for mode, srcs in (("sample", ("eps_scale", "eps_shift", "eps_z", "u")), ("given", ("in_s", "in_xy", "in_z", "in_p"))):
             r = H.SceneRecords(*[_ptr(g[k]) for k in srcs], _ptr(self.dyn), _ptr(g["att"]), _ptr(g["z"]), _ptr(g["z16"]),
                                B, N, Z, Z, 1 if mode == "given" else 0)
             self._keep.append(r)
             ops[mode] = self._call("air_scene_records", C.byref(r), nbytes=NB * (4 * (4 + 2 * Z) + 64), tag="scene_records_" + mode)
-            ops[mode].kernel = "scene_records_kernel"
-        dec = []
-        x, x16, k = g["z"], g["z16"], Z
-        for i, u in enumerate(gen_u):
-            dec.append(self._gemm(x, P["gen%d_w" % i], g["act"][i], NB, u, k, k, u, u,
-                                  bias=P["gen%d_b" % i], act=H.ACT_SOFTPLUS, tag="vae_gen",
-                                  A16=x16, B16=T("gen%d_w" % i), C16=g["act16"][i], B16p=TP("gen%d_w" % i)))
-            x, x16, k = g["act"][i], g["act16"][i], u
-        ops["decoder"] = dec
         for name, sigma in (("out_noise", float(self.vae_likelihood_std)), ("out_mean", 0.0)):
-            ops[name] = self._gemm(x, P["out_w"], g["vrec"], NB, d, k, k, d, d, bias=P["out_b"],
-                                   act=H.ACT_SIGMOID_NOISE, aux=g["eps_x"], ldaux=d, aux_scale=sigma, tag="vae_out",
-                                   A16=x16, B16=T("out_w"), B16p=TP("out_w"))
+            dec = self._generative_ops(g["z"], g["z16"], Z, g["act"], g["act16"], g["vrec"], g["eps_x"], sigma)
+            ops["decoder"], ops[name] = dec[:-1], dec[-1]          # (the layers' descriptors do not depend on sigma)
         rd = H.Render(_ptr(g["vrec"]), _ptr(g["att"]), _ptr(g["canvas"]), _ptr(g["digits"]), B, N,
                       self.canvas_size, self.windows_size)
         self._keep.append(rd)
         ops["render"] = self._call("air_render", C.byref(rd), nbytes=NB * (d * 4 + 64) + B * dm["D"] * 4, tag="render")
-        ops["render"].kernel = "render_kernel"
         return ops
 
     def generate_ops(self, likelihood_noise=False, given=False, fill=True):
@@ -1508,11 +1475,9 @@ class AIRModel:
 
     def _gen_fill_op(self):
         g, seed, call = self._gen, self._seed, self._gen_calls
-        op = self._call("air_philox_fill", _ptr(g["normals"]), g["normals"].numel(), _ptr(g["uniforms"]), g["uniforms"].numel(),
-                        C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(call),
-                        nbytes=4 * (g["normals"].numel() + g["uniforms"].numel()), tag="philox_fill")
-        op.kernel = "philox_fill_kernel"
-        return op
+        return self._call("air_philox_fill", _ptr(g["normals"]), g["normals"].numel(), _ptr(g["uniforms"]), g["uniforms"].numel(),
+                          C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(call),
+                          nbytes=4 * (g["normals"].numel() + g["uniforms"].numel()), tag="philox_fill")
 
     def _gen_run(self, given, likelihood_noise, needs_noise):
         g = self._gen_state()
@@ -1644,31 +1609,16 @@ class AIRModel:
         with the reference graph's variable names (what tf.train.Saver writes at training.py:203-207),
         Adam slots included -- restorable by the reference's demo.py:33 / training.py."""
         import tf_checkpoint as tfc
-        st = self.store
-        sd = {k: v.detach().cpu().contiguous().numpy() for k, v in st.variables.items()}
-        for k in st.variables:
-            sd[k + "/Adam"] = st.adam_m[k].detach().cpu().contiguous().numpy()
-            sd[k + "/Adam_1"] = st.adam_v[k].detach().cpu().contiguous().numpy()
-        sd["global_step"] = int(st.istate[H.IST_GLOBAL_STEP])
-        shapes = {k: tuple(v.shape) for k, v in st.variables.items()}
-        return tfc.save_checkpoint(prefix, tfc.model_to_tensors(sd, shapes))
+        shapes = {k: tuple(v.shape) for k, v in self.store.variables.items()}
+        return tfc.save_checkpoint(prefix, tfc.model_to_tensors(self.store.state_dict(), shapes))
 
     def load_tf_checkpoint(self, prefix, verify=True):
         """Restores variables (and Adam slots / global_step when present) from a TensorFlow bundle
-        written by the reference (`model/air-model`, `air_results/model/air-model-<step>`)."""
+        written by the reference (`model/air-model`, `air_results/model/air-model-<step>`).  The bundle goes through
+        load_state_dict: it is validated before anything is written, so a malformed one -- a variable missing, only one of
+        a variable's two Adam slots -- is refused with the model's state untouched."""
         import tf_checkpoint as tfc
-        st = self.store
-        sd = tfc.tensors_to_state_dict(tfc.load_checkpoint(prefix, verify))
-        for k, v in st.variables.items():
-            v.copy_(torch.from_numpy(np.asarray(sd[k], np.float32)).reshape(v.shape))
-            if k + "/Adam" in sd:
-                st.adam_m[k].copy_(torch.from_numpy(np.asarray(sd[k + "/Adam"], np.float32)).reshape(v.shape))
-                st.adam_v[k].copy_(torch.from_numpy(np.asarray(sd[k + "/Adam_1"], np.float32)).reshape(v.shape))
-        if "global_step" in sd:
-            st.istate[H.IST_GLOBAL_STEP] = int(sd["global_step"])
-        st.touch()
-        self._dirty = True
-        self._host_step = None
+        self.load_state_dict(tfc.tensors_to_state_dict(tfc.load_checkpoint(prefix, verify)))
         return self
 
     def load_state_dict(self, sd, strict=True, load_optimizer=True):

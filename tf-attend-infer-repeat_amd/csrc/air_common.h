@@ -26,10 +26,11 @@ static inline hipStream_t air_stream(void* s) { return reinterpret_cast<hipStrea
 // driver call returned, so a reader that finds it may launch; two threads racing on the same (function, device) both
 // make the call, which is idempotent.  A full row or a device index beyond the table is an error, not a silent
 // per-launch driver call.
+constexpr size_t AIR_LDS_LIMIT = 160 * 1024;     // bytes of LDS a workgroup may hold on gfx950
 static inline int air_grant_lds(const void* fn, size_t bytes) {
     constexpr int MAX_DEV = 32, SLOTS = 64;
     static std::atomic<const void*> granted[MAX_DEV][SLOTS];
-    if (bytes > 160 * 1024) return AIR_ELIMIT;
+    if (bytes > AIR_LDS_LIMIT) return AIR_ELIMIT;
     if (bytes <= 48 * 1024) return 0;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) dev = 0;
@@ -40,7 +41,7 @@ static inline int air_grant_lds(const void* fn, size_t bytes) {
         if (g == fn) return 0;
         if (!g) break;                                   // slots fill front to back and are never cleared
     }
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AIR_LDS_LIMIT);
     if (e != hipSuccess) return (int)e;
     for (int i = 0; i < SLOTS; ++i) {
         const void* expect = nullptr;

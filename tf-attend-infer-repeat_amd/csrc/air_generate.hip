@@ -121,8 +121,6 @@ __global__ __launch_bounds__(CF_THREADS) void render_kernel(air_render_t a)
     }
 }
 
-size_t render_smem(int N, int C, int w) { return (2 * MAX_STEPS + (size_t)N * (8 * (size_t)C + (size_t)w * w)) * sizeof(float); }
-
 }  // namespace
 
 extern "C" int air_philox_fill(float* normals, int64_t n_normal, float* uniforms, int64_t n_uniform,

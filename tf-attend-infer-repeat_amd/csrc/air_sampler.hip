@@ -595,18 +595,8 @@ __global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
     }
 }
 
-// the canvas is staged in LDS only when one prefetch pass covers it (PF * THREADS floats, see the kernels)
-size_t attend_canvas_floats(int C) { return (size_t)C * C <= 10 * (size_t)THREADS ? (size_t)C * C : 0; }
-// (sh_wout is [7][wout_ld]: the caller's row stride, which may be padded beyond the widest head)
-size_t attend_smem(int C, int w, int HT, int wout_ld) {
-    return (16 + MAX_STEPS + 8 * w + 4 + ((HT + 3) & ~3) + 7 * (size_t)wout_ld + MAX_STEPS * (size_t)HT + attend_canvas_floats(C)) * sizeof(float);
-}
 // a row of wout holds the hidden segment of its unit's head: the stride must cover the widest head
 bool wout_ld_ok(int wout_ld, int Hs, int Hh, int Hz) { return wout_ld >= Hs && wout_ld >= Hh && wout_ld >= Hz; }
-size_t attend_bwd_smem(int C, int w) {
-    return (24 + 8 * w + w + 4 + attend_canvas_floats(C)) * sizeof(float);
-}
-size_t write_smem(int N, int C, int w) { return (16 + 7 * MAX_STEPS + (size_t)N * (8 * C + (size_t)w * w)) * sizeof(float); }
 
 }  // namespace
 
@@ -669,5 +659,18 @@ extern "C" int air_write_fwd(const air_write_fwd_t* a, void* stream) {
         hipLaunchKernelGGL((write_fwd_kernel<CF_THREADS>), dim3(a->B + extra), dim3(CF_THREADS), lds, air_stream(stream), *a);
     }
     AIR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int air_step_lds(int N, int C, int w, int Hs, int Hh, int Hz, int wout_ld, air_step_lds_t* out) {
+    if (!out || N <= 0 || C <= 0 || w <= 0 || Hs <= 0 || Hh <= 0 || Hz <= 0) return AIR_EINVAL;
+    if (!wout_ld_ok(wout_ld, Hs, Hh, Hz)) return AIR_EINVAL;
+    out->attend_fwd = (int64_t)attend_smem(C, w, 2 * Hs + 2 * Hh + Hz, wout_ld);
+    out->attend_bwd = (int64_t)attend_bwd_smem(C, w);
+    out->write_fwd = (int64_t)write_smem(N, C, w);
+    out->render = (int64_t)render_smem(N, C, w);
+    out->write_bwd_exact = (int64_t)write_bwd_smem(C, w);
+    out->write_bwd_graph = (int64_t)write_bwd_graph_smem(C, w, write_bwd_graph_allph(C, w));
+    out->limit = (int64_t)AIR_LDS_LIMIT;
     return 0;
 }

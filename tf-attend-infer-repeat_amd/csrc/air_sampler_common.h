@@ -113,4 +113,29 @@ __device__ __forceinline__ float compose_pixel(const int* sh_act, const float* s
 template <typename K>
 int ensure_lds(K kernel, size_t bytes) { return air_grant_lds(reinterpret_cast<const void*>(kernel), bytes); }
 
+// ---- dynamic LDS of the sampler launches, in bytes: what the entry points size their launches with, and what air_step_lds
+// answers (the host asks; it does not restate these) --------------------------------------------------------------------
+// the canvas is staged in LDS only when one prefetch pass covers it (PF * THREADS floats, see the attend kernels)
+inline size_t attend_canvas_floats(int C) { return (size_t)C * C <= 10 * (size_t)THREADS ? (size_t)C * C : 0; }
+// air_attend_fwd (sh_wout is [7][wout_ld]: the caller's row stride, which may be padded beyond the widest head)
+inline size_t attend_smem(int C, int w, int HT, int wout_ld) {
+    return (16 + MAX_STEPS + 8 * w + 4 + ((HT + 3) & ~3) + 7 * (size_t)wout_ld + MAX_STEPS * (size_t)HT + attend_canvas_floats(C)) * sizeof(float);
+}
+// air_attend_bwd
+inline size_t attend_bwd_smem(int C, int w) {
+    return (24 + 8 * w + w + 4 + attend_canvas_floats(C)) * sizeof(float);
+}
+// air_write_fwd (with wb_order at least the sort's 16 KB: never the binding term)
+inline size_t write_smem(int N, int C, int w) { return (16 + 7 * MAX_STEPS + (size_t)N * (8 * C + (size_t)w * w)) * sizeof(float); }
+// air_render
+inline size_t render_smem(int N, int C, int w) { return (2 * MAX_STEPS + (size_t)N * (8 * (size_t)C + (size_t)w * w)) * sizeof(float); }
+// air_write_bwd, literals 2 and 4: all four taps' terms resident (allph) when they fit next to a second workgroup's share of the LDS
+inline size_t write_bwd_graph_smem(int C, int w, bool allph) {
+    return (136 + 8 * C + ((C + 3) & ~3) + 8 * C + ((8 * w + 3) & ~3) + (((size_t)w * w + 3) & ~3) +
+            (allph ? 5 : 1) * (((size_t)C * C + 3) & ~3)) * sizeof(float);
+}
+inline bool write_bwd_graph_allph(int C, int w) { return write_bwd_graph_smem(C, w, true) <= 80 * 1024; }
+// air_write_bwd, literal 0
+inline size_t write_bwd_smem(int C, int w) { return (64 + 8 * C + C + 8 * w + (size_t)w * w + (size_t)C * w + (size_t)C * C) * sizeof(float); }
+
 }  // namespace
