@@ -106,6 +106,10 @@ enum {
  * Replaces tf.matmul + BiasAdd + Relu/Softplus/Sigmoid nodes of
  * layers.fully_connected (air_model.py:292-316, 374-376; vae.py:13-34), the
  * BasicLSTMCell MatMul (:286) and their MatMul_grad nodes.
+ * Leading dimensions may be padded; one below the row it strides is AIR_EINVAL: lda < K (M with transA), ldb < N (K with
+ * transB), ldc < N (2N for AIR_EPI_REPARAM_BWD, which writes 2N columns), and ldadd / ldaux < N when that operand is given.
+ * (lda of the padded-A16 form of AIR_EPI_LSTM_FWD0 is the twin's stride and has its own rule, see A16 below.)
+ * Pad columns are never read into the result and never written.
  * precision: 0 = exact-fp32 MFMA (v_mfma_f32_16x16x4_f32);
  *            1 = bf16 operands, fp32 accumulate (v_mfma_f32_16x16x32_bf16). */
 enum {

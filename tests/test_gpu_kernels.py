@@ -289,9 +289,11 @@ def _gemm_struct(H, A, B, Cc, M, N, K, lda, ldb, ldc, prec, **kw):
 
 
 @pytest.mark.parametrize("prec", [0, 1])
-@pytest.mark.parametrize("tile", [(1, 1), (1, 2), (1, 4), (2, 2), (2, 4), (4, 1), (4, 2)])
+@pytest.mark.parametrize("tile", [(1, 1), (1, 2), (1, 4), (2, 2), (2, 4), (4, 1), (4, 2), (4, 4)])
 @pytest.mark.parametrize("ta,tb", [(0, 0), (0, 1), (1, 0)])
 def test_gemm_explicit_tiles(H, tile, ta, tb, prec):
+    """Every tile of the FALLBACK kernels (gemm_f32_kernel / gemm_bf16_kernel) at one ragged shape: K = 333 is odd, so no case
+    here reaches a lean kernel.  Those and the twin kernels are forced through every tile in tests/test_gpu_gemm_edges.py."""
     rng = np.random.RandomState(7)
     M, N, K = 70, 150, 333
     A = rng.uniform(-1, 1, (K, M) if ta else (M, K)).astype(np.float32)

@@ -1065,6 +1065,15 @@ static int fill_args(const air_gemm_t* g, Args& a) {
     if (g->epi < AIR_EPI_GENERIC || g->epi > AIR_EPI_LSTM_FWD0) return AIR_EINVAL;
     if (g->ksplit > 1 && g->epi != AIR_EPI_GENERIC) return AIR_EINVAL;
     if (g->addend_slabs > 8) return AIR_ELIMIT;
+    // a leading dimension below the row width the kernels index makes rows overlap (ldc: the workgroups then race on C).
+    // The padded-A16 form of AIR_EPI_LSTM_FWD0 redefines lda as the twin's stride: twin_rounds checks that one.
+    // AIR_EPI_REPARAM_BWD writes d_mean | d_log_var, 2N columns per row of C.
+    const bool lda_is_twins = g->epi == AIR_EPI_LSTM_FWD0 && g->A16 && (g->i0 & 2);
+    if (!lda_is_twins && g->lda < (g->transA ? g->M : g->K)) return AIR_EINVAL;
+    if (g->ldb < (g->transB ? g->K : g->N)) return AIR_EINVAL;
+    if (g->ldc < (g->epi == AIR_EPI_REPARAM_BWD ? 2 * g->N : g->N)) return AIR_EINVAL;
+    if (g->addend && g->ldadd < g->N) return AIR_EINVAL;
+    if (g->aux && g->ldaux < g->N) return AIR_EINVAL;
     a.A = g->A; a.B = g->B; a.C = g->C;
     a.M = g->M; a.N = g->N; a.K = g->K; a.lda = g->lda; a.ldb = g->ldb; a.ldc = g->ldc;
     a.gstride = 16; a.gwidth = g->N;
