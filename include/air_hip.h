@@ -12,7 +12,7 @@
  *   - every pointer is a CALLER-OWNED DEVICE pointer, contiguous row-major fp32
  *     unless stated; the library never allocates or frees, keeps no state but two per-device caches (the LDS grant of a
  *     kernel function, the lane-order probe below), is re-entrant, and does not synchronise -- with ONE exception: the
- *     first EAGER air_write_bwd(literal 2) / air_transformer_bwd of a process on a device probes the lane order of the LDS
+ *     first EAGER air_write_bwd(literal 2) / air_transformer_bwd / air_transformer_nc_bwd of a process on a device probes the lane order of the LDS
  *     atomic pipe (one tiny kernel, an 8-byte copy back, one stream synchronise).  Under stream capture nothing is probed:
  *     a capture-first caller takes the register-chain accumulator (same bits, slower; a message on stderr).  Every other
  *     call is hipGraph-capture safe from the first call;
@@ -313,6 +313,37 @@ int air_transformer_fwd(const float* U, const float* theta, float* out,
  * Hi*Wi <= ~20 000 (U and d_U of one image live in LDS). */
 int air_transformer_bwd(const float* U, const float* theta, const float* d_out, float* d_U, float* d_theta,
                         int B, int Hi, int Wi, int Ho, int Wo, void* stream);
+
+/* ---- spatial transformer on multi-channel inputs, several transforms per image (transformer.py:18-175 with
+ * num_channels = C, and batch_transformer :178-195) -----------------------------
+ * U [B,Hi,Wi,C], channels innermost and contiguous as the reference lays it out; theta [B*T,2,3]; out [B*T,Ho,Wo,C].
+ * Row b*T+t samples image b with theta[b*T+t]: T = 1 is transformer, T > 1 is batch_transformer, whose tf.gather copy of
+ * the input (:193-194) is never made.  Any C >= 1, T >= 1.
+ * The tap coordinates and the four weights of an output pixel are computed once, in the op sequence of
+ * air_transformer_fwd (indices clipped before the weights, no contraction); every channel then gets
+ * ((wa*Ia + wb*Ib) + wc*Ic) + wd*Id.  Channel c of `out` is BIT-IDENTICAL to air_transformer_fwd on the channel-c plane.
+ * 16-byte loads and stores when C % 4 == 0 and U / out are 16-byte aligned, scalar ones otherwise. */
+int air_transformer_nc_fwd(const float* U, const float* theta, float* out,
+                           int B, int T, int Hi, int Wi, int C, int Ho, int Wo, void* stream);
+/* its gradient: d_U [B,Hi,Wi,C] and / or d_theta [B*T,2,3] (either may be NULL) from d_out [B*T,Ho,Wo,C].
+ *   d_U, T = 1: im_flat is [B*H*W, C] (:100) and the four Gather gradients carry rows of C values into ONE
+ *        UnsortedSegmentSum: per channel, one fp32 accumulator per input pixel that receives its a-terms in output-pixel
+ *        order, then b, c, d.  Channel c of d_U is BIT-IDENTICAL to air_transformer_bwd on plane c, and so to the executed
+ *        reference graph.
+ *   d_U, T > 1: the gradient of the tf.gather replication is one more sequential UnsortedSegmentSum over the rows: each
+ *        row's d_U is first completed from zero as above, then d_U[b] = ((row b*T+0) + row b*T+1) + ... in fp32,
+ *        ascending t.  NOT one accumulator carried across the transforms (the two orders differ in the last bits).
+ *   d_theta: the weights are shared by the channels, so the graph reduces g*I over the channel axis before the AddN legs:
+ *        ga = sum_c g_c*Ia_c in fp32 in ascending c, starting from the c = 0 product (gb, gc, gd alike); then the
+ *        dX / dY / truediv / mul sequence and the contraction with (x_t, y_t, 1) of air_transformer_bwd -- at C = 1 the same
+ *        bits, and like it equal to the graph up to the reduction order of that one contraction.
+ * Deterministic: no global atomics.  Hi*Wi keeps the bound of air_transformer_bwd (~20 000 pixels: AIR_ELIMIT beyond, when a
+ * single channel's planes cannot fit); the channels are taken in groups whose planes fit the LDS at once, one wave per
+ * channel, so any C works.  AIR_EINVAL: a null U / theta / d_out, both outputs null, a size < 1.  Both are answered on the
+ * host before any launch.  The lane-order probe and its behaviour under stream capture are air_transformer_bwd's. */
+int air_transformer_nc_bwd(const float* U, const float* theta, const float* d_out,
+                           float* d_U /*nullable*/, float* d_theta /*nullable*/,
+                           int B, int T, int Hi, int Wi, int C, int Ho, int Wo, void* stream);
 
 /* ---- "attend": heads output layer + sampling + KLs + stop logic + ST read -----
  * air_model.py:288-333 (scale/shift heads, theta, transformer canvas->window) and

@@ -49,6 +49,47 @@ __global__ __launch_bounds__(THREADS) void transformer_fwd_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// generic transformer on [B,Hi,Wi,C] inputs, T transforms per image (transformer.py:18-175, batch_transformer :178-195
+// without its tf.gather copy of the input: row b*T+t samples image b).  A work item is one output pixel and one group of
+// four channels: the taps and weights of the pixel by generic_tap -- the op sequence of transformer_fwd_kernel -- then the
+// 4-product / add_n per channel, so channel c carries the bits air_transformer_fwd gives on the channel-c plane.  The
+// channels of a tap are contiguous: 16-byte loads and stores when C % 4 == 0 (and U / out are 16-byte aligned: `vec`),
+// scalar ones otherwise; neighbouring threads take neighbouring groups, i.e. neighbouring addresses of `out`.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(THREADS) void transformer_nc_fwd_kernel(
+    const float* __restrict__ U, const float* __restrict__ theta, float* __restrict__ out,
+    long total, int T, int Hi, int Wi, int C, int Ho, int Wo, int vec)
+{
+    const int G = (C + 3) >> 2, NO = Ho * Wo;
+    for (long q = (long)blockIdx.x * THREADS + threadIdx.x; q < total; q += (long)gridDim.x * THREADS) {
+        const int c0 = (int)(q % G) * 4;
+        const long pix = q / G;                                  // (row, output pixel)
+        const long row = pix / NO;
+        const int r = (int)(pix % NO);
+        float th[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) th[k] = theta[(size_t)row * 6 + k];
+        const GenTap t = generic_tap(th, r / Wo, r % Wo, Hi, Wi, Ho, Wo);
+        const Tap tx{t.wx0, t.wx1, 0, 0}, ty{t.wy0, t.wy1, 0, 0};
+        const float* img = U + (size_t)(row / T) * Hi * Wi * C + c0;
+        const float* pa = img + (size_t)(t.y0 * Wi + t.x0) * C;
+        const float* pb = img + (size_t)(t.y1 * Wi + t.x0) * C;
+        const float* pc = img + (size_t)(t.y0 * Wi + t.x1) * C;
+        const float* pd = img + (size_t)(t.y1 * Wi + t.x1) * C;
+        float* dst = out + (size_t)pix * C + c0;
+        if (vec) {
+            const float4 Ia = *reinterpret_cast<const float4*>(pa), Ib = *reinterpret_cast<const float4*>(pb);
+            const float4 Ic = *reinterpret_cast<const float4*>(pc), Id = *reinterpret_cast<const float4*>(pd);
+            *reinterpret_cast<float4*>(dst) = make_float4(bilinear4(tx, ty, Ia.x, Ib.x, Ic.x, Id.x), bilinear4(tx, ty, Ia.y, Ib.y, Ic.y, Id.y),
+                                                          bilinear4(tx, ty, Ia.z, Ib.z, Ic.z, Id.z), bilinear4(tx, ty, Ia.w, Ib.w, Ic.w, Id.w));
+        } else {
+            const int n = min(4, C - c0);
+            for (int k = 0; k < n; ++k) dst[k] = bilinear4(tx, ty, pa[k], pb[k], pc[k], pd[k]);
+        }
+    }
+}
+
 // head index -> (offset, width) inside the concatenated hidden vector
 struct HeadSeg { int off[5]; int wid[5]; };
 __device__ __forceinline__ HeadSeg head_segments(int Hs, int Hh, int Hz) {
@@ -607,6 +648,20 @@ extern "C" int air_transformer_fwd(const float* U, const float* theta, float* ou
     const int blocks = (int)((total + THREADS - 1) / THREADS < 2048 ? (total + THREADS - 1) / THREADS : 2048);
     hipLaunchKernelGGL(transformer_fwd_kernel, dim3(blocks), dim3(THREADS), 0, air_stream(stream),
                        U, theta, out, B, Hi, Wi, Ho, Wo);
+    AIR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int air_transformer_nc_fwd(const float* U, const float* theta, float* out,
+                                      int B, int T, int Hi, int Wi, int C, int Ho, int Wo, void* stream) {
+    if (!U || !theta || !out || B <= 0 || T <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || Ho <= 0 || Wo <= 0) return AIR_EINVAL;
+    // what the kernel indexes with an int: one image's pixels, one row's output pixels, the rows
+    if ((long)Hi * Wi > INT32_MAX || (long)Ho * Wo > INT32_MAX || (long)B * T > INT32_MAX) return AIR_ELIMIT;
+    const long total = (long)B * T * Ho * Wo * ((C + 3) >> 2);
+    const int blocks = (int)((total + THREADS - 1) / THREADS < 2048 ? (total + THREADS - 1) / THREADS : 2048);
+    const int vec = C % 4 == 0 && ((uintptr_t)U | (uintptr_t)out) % 16 == 0;
+    hipLaunchKernelGGL(transformer_nc_fwd_kernel, dim3(blocks), dim3(THREADS), 0, air_stream(stream),
+                       U, theta, out, total, T, Hi, Wi, C, Ho, Wo, vec);
     AIR_CHECK_LAUNCH();
     return 0;
 }

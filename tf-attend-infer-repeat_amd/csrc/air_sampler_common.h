@@ -1,8 +1,8 @@
 // Shared pieces of the sampler translation units (air_sampler.hip: the glimpse read, the heads around it, compose, the
 // generic forward; air_sampler_write_bwd.hip: the write backward in its three orders, the generic backward, the lane-order
 // probe; air_generate.hip: the records of generated scenes and the render-only compose): the per-axis tap of the
-// axis-aligned transformer, the reference's 4-product expression, the coordinate gradient in the saved graph's op order,
-// the Concrete pre-sigmoid sample, and the staging / per-pixel code of compose.
+// axis-aligned transformer and the tap of the generic one, the reference's 4-product expression, the coordinate gradient
+// in the saved graph's op order, the Concrete pre-sigmoid sample, and the staging / per-pixel code of compose.
 #pragma once
 #include "air_common.h"
 #include <cstdio>
@@ -44,6 +44,25 @@ __device__ __forceinline__ float bilinear4(const Tap& tx, const Tap& ty,
     const float wc = tx.w1 * ty.w0;
     const float wd = tx.w1 * ty.w1;
     return ((wa * Ia + wb * Ib) + wc * Ic) + wd * Id;
+}
+
+// one output pixel of the generic transformer (any theta), transformer.py:75-87,108-115,138-163: the meshgrid point, the
+// source coordinates, the clipped corners and the per-axis weights taken from the CLIPPED corners
+struct GenTap { float wx0, wx1, wy0, wy1; int x0, x1, y0, y1; float xt, yt; };
+__device__ __forceinline__ GenTap generic_tap(const float* th, int i, int j, int Hi, int Wi, int Ho, int Wo) {
+    GenTap t;
+    t.xt = (Wo > 1) ? (-1.0f + (2.0f / (float)(Wo - 1)) * (float)j) : -1.0f;
+    t.yt = (Ho > 1) ? (-1.0f + (2.0f / (float)(Ho - 1)) * (float)i) : -1.0f;
+    const float xs = (th[0] * t.xt + th[1] * t.yt) + th[2] * 1.0f;
+    const float ys = (th[3] * t.xt + th[4] * t.yt) + th[5] * 1.0f;
+    const float X = ((xs + 1.0f) * ((float)Wi - 1.001f)) / 2.0f;
+    const float Y = ((ys + 1.0f) * ((float)Hi - 1.001f)) / 2.0f;
+    const float fx = floorf(X), fy = floorf(Y);
+    const float x0 = fminf(fmaxf(fx, 0.f), (float)(Wi - 1)), x1 = fminf(fmaxf(fx + 1.f, 0.f), (float)(Wi - 1));
+    const float y0 = fminf(fmaxf(fy, 0.f), (float)(Hi - 1)), y1 = fminf(fmaxf(fy + 1.f, 0.f), (float)(Hi - 1));
+    t.wx0 = x1 - X; t.wx1 = X - x0; t.wy0 = y1 - Y; t.wy1 = Y - y0;
+    t.x0 = (int)x0; t.x1 = (int)x1; t.y0 = (int)y0; t.y1 = (int)y1;
+    return t;
 }
 
 // Gradient of one output pixel wrt its source coordinates (X, Y) in the op order of the reference's SAVED graph

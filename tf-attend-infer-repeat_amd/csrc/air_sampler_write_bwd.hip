@@ -1,8 +1,8 @@
 // The write backward of the AIR loop (window <- d loss / d canvas; air_model.py:351-366 under tf.gradients,
 // transformer.py:56-171): the exact adjoint, the op order of the reference's saved graph (the default: one sequential fp32
 // accumulator per window pixel, on the LDS atomic pipe for the four corner slots) and the carried order; the backward of the
-// generic transformer; the probe of the LDS atomic pipe's lane order that the graph order rests on.  Shared geometry:
-// air_sampler_common.h.
+// generic transformer, for one channel and for [B,H,W,C] inputs with several transforms per image; the probe of the LDS
+// atomic pipe's lane order that the graph order rests on.  Shared geometry: air_sampler_common.h.
 #include "air_sampler_common.h"
 
 AIR_STAMPS_READER(air_debug_stamps_wb)
@@ -48,23 +48,6 @@ __device__ __forceinline__ void lds_fadd(float* p, float v) {
 //     wave's instructions in program order (tools/exp/lds_atomic_order.hip), i.e. exactly the scatter
 //     order of the reference's CPU kernel.  One workgroup per image; U and d U live in LDS.
 // ---------------------------------------------------------------------------
-struct GenTap { float wx0, wx1, wy0, wy1; int x0, x1, y0, y1; float xt, yt; };
-__device__ __forceinline__ GenTap generic_tap(const float* th, int i, int j, int Hi, int Wi, int Ho, int Wo) {
-    GenTap t;
-    t.xt = (Wo > 1) ? (-1.0f + (2.0f / (float)(Wo - 1)) * (float)j) : -1.0f;
-    t.yt = (Ho > 1) ? (-1.0f + (2.0f / (float)(Ho - 1)) * (float)i) : -1.0f;
-    const float xs = (th[0] * t.xt + th[1] * t.yt) + th[2] * 1.0f;
-    const float ys = (th[3] * t.xt + th[4] * t.yt) + th[5] * 1.0f;
-    const float X = ((xs + 1.0f) * ((float)Wi - 1.001f)) / 2.0f;
-    const float Y = ((ys + 1.0f) * ((float)Hi - 1.001f)) / 2.0f;
-    const float fx = floorf(X), fy = floorf(Y);
-    const float x0 = fminf(fmaxf(fx, 0.f), (float)(Wi - 1)), x1 = fminf(fmaxf(fx + 1.f, 0.f), (float)(Wi - 1));
-    const float y0 = fminf(fmaxf(fy, 0.f), (float)(Hi - 1)), y1 = fminf(fmaxf(fy + 1.f, 0.f), (float)(Hi - 1));
-    t.wx0 = x1 - X; t.wx1 = X - x0; t.wy0 = y1 - Y; t.wy1 = Y - y0;
-    t.x0 = (int)x0; t.x1 = (int)x1; t.y0 = (int)y0; t.y1 = (int)y1;
-    return t;
-}
-
 __global__ __launch_bounds__(THREADS) void transformer_bwd_kernel(
     const float* __restrict__ U, const float* __restrict__ theta, const float* __restrict__ d_out,
     float* __restrict__ d_U, float* __restrict__ d_theta, int Hi, int Wi, int Ho, int Wo, int lds_ordered)
@@ -131,6 +114,138 @@ __global__ __launch_bounds__(THREADS) void transformer_bwd_kernel(
         __syncthreads();
         float* dst = d_U + (size_t)b * NI;
         for (int p = tid; p < NI; p += THREADS) dst[p] = sh_dU[p];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// generic transformer backward on [B,Hi,Wi,C] inputs with T transforms per image (air_transformer_nc_bwd): what
+// tf.gradients builds for transformer.py:18-175 and, T > 1, for batch_transformer (:178-195).  One launch, two kinds
+// of workgroup:
+//   * d U, one workgroup per (image, group of up to NC_WAVES channels).  im_flat is [B*H*W, C] and the Gather gradients
+//     carry rows of C values into the UnsortedSegmentSum, so a channel is the single-channel stream above on its own
+//     plane: wave k of the workgroup walks the 4*Ho*Wo terms of channel c0 + k into that channel's plane of LDS -- the
+//     waves that sit idle in transformer_bwd_kernel -- and a plane only ever sees the adds of one wave, in program
+//     order.  The tf.gather of batch_transformer has one more UnsortedSegmentSum as its gradient, over the rows of an
+//     image in ascending order: every transform's d U is completed from zero, then added to the image's, t = 0, 1, ...
+//     (NOT one accumulator carried across the transforms);
+//   * d theta, one workgroup per row.  The weights are shared by the channels: the graph reduces g * I over the channel
+//     axis (ascending c, from the c = 0 product) before the AddN legs; from there on the arithmetic and the reduction
+//     of transformer_bwd_kernel, so at C = 1 the same bits.  U comes from memory: C contiguous floats per tap.
+// ---------------------------------------------------------------------------
+constexpr int NC_WAVES = THREADS / 64;
+__device__ __forceinline__ void transformer_nc_dtheta(
+    const float* __restrict__ img, const float* __restrict__ theta_row, const float* __restrict__ g, float* __restrict__ d_theta_row,
+    int Hi, int Wi, int C, int Ho, int Wo, float* sh_red)
+{
+    const int tid = threadIdx.x, NO = Ho * Wo;
+    float th[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) th[k] = theta_row[k];
+    float s6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int p = tid; p < NO; p += THREADS) {
+        const GenTap t = generic_tap(th, p / Wo, p % Wo, Hi, Wi, Ho, Wo);
+        const float* pa = img + (size_t)(t.y0 * Wi + t.x0) * C;
+        const float* pb = img + (size_t)(t.y1 * Wi + t.x0) * C;
+        const float* pc = img + (size_t)(t.y0 * Wi + t.x1) * C;
+        const float* pd = img + (size_t)(t.y1 * Wi + t.x1) * C;
+        const float* gp = g + (size_t)p * C;
+        // Sum over the channel axis of mul_10..13_grad's products (the weights broadcast over it)
+        float ga = gp[0] * pa[0], gb = gp[0] * pb[0], gc = gp[0] * pc[0], gd = gp[0] * pd[0];
+        for (int c = 1; c < C; ++c) {
+            const float gv = gp[c];
+            ga = ga + gv * pa[c]; gb = gb + gv * pb[c]; gc = gc + gv * pc[c]; gd = gd + gv * pd[c];
+        }
+        const float dX = ((-(ga * t.wy0) + -(gb * t.wy1)) + gc * t.wy0) + gd * t.wy1;
+        const float dY = ((-(t.wx0 * ga) + t.wx0 * gb) + -(t.wx1 * gc)) + t.wx1 * gd;
+        const float gX = (dX / 2.0f) * ((float)Wi - 1.001f);
+        const float gY = (dY / 2.0f) * ((float)Hi - 1.001f);
+        s6[0] += gX * t.xt; s6[1] += gX * t.yt; s6[2] += gX;
+        s6[3] += gY * t.xt; s6[4] += gY * t.yt; s6[5] += gY;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const float v = air_block_sum_256(s6[k], sh_red + 4 * k);
+        if (tid == 0) d_theta_row[k] = v;
+    }
+}
+
+__device__ __forceinline__ void transformer_nc_du(
+    const float* __restrict__ theta, const float* __restrict__ d_out, float* __restrict__ d_U,
+    int b, int c0, int ncg, int T, int Hi, int Wi, int C, int Ho, int Wo, int lds_ordered, float* sh_dU /* [ncg][NIp] */)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int NI = Hi * Wi, NIp = (NI + 3) & ~3, NO = Ho * Wo;
+    for (int i = tid; i < ncg * NIp; i += THREADS) sh_dU[i] = 0.0f;
+    float* dst = d_U + (size_t)b * NI * C + c0;
+    for (int t = 0; t < T; ++t) {
+        __syncthreads();
+        if (wave < ncg) {
+            const size_t row = (size_t)b * T + t;
+            float th[6];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) th[k] = theta[row * 6 + k];
+            const float* g = d_out + row * NO * C + c0 + wave;         // this wave's channel, stride C
+            float* plane = sh_dU + wave * NIp;
+            if (!lds_ordered) {
+                // fallback for a part whose LDS atomics do not apply lanes in ascending order (lds_order_probe): ONE lane per
+                // channel walks the terms -- slow, but the reference's scatter order by construction
+                if (lane == 0)
+                    for (int ph = 0; ph < 4; ++ph)
+                        for (int p = 0; p < NO; ++p) {
+                            const GenTap tp = generic_tap(th, p / Wo, p % Wo, Hi, Wi, Ho, Wo);
+                            const float wgt = ((ph & 2) ? tp.wx1 : tp.wx0) * ((ph & 1) ? tp.wy1 : tp.wy0);
+                            const int idx = ((ph & 1) ? tp.y1 : tp.y0) * Wi + ((ph & 2) ? tp.x1 : tp.x0);
+                            plane[idx] = plane[idx] + wgt * g[(size_t)p * C];
+                        }
+            } else {
+                // the gradient of the next 64 terms is loaded ahead of this instruction's adds (the index wraps into the next
+                // tap's first pixels; past the last tap it re-reads them and the value is dropped)
+                float gcur = lane < NO ? g[(size_t)lane * C] : 0.0f;
+                for (int ph = 0; ph < 4; ++ph)
+                    for (int p0 = 0; p0 < NO; p0 += 64) {
+                        const int p = p0 + lane, pn = (p0 + 64 < NO ? p0 + 64 : 0) + lane;
+                        const float gnext = pn < NO ? g[(size_t)pn * C] : 0.0f;
+                        if (p < NO) {
+                            const GenTap tp = generic_tap(th, p / Wo, p % Wo, Hi, Wi, Ho, Wo);
+                            const float wgt = ((ph & 2) ? tp.wx1 : tp.wx0) * ((ph & 1) ? tp.wy1 : tp.wy0);   // wa, wb, wc, wd
+                            const int idx = ((ph & 1) ? tp.y1 : tp.y0) * Wi + ((ph & 2) ? tp.x1 : tp.x0);
+                            lds_fadd(plane + idx, wgt * gcur);
+                        }
+                        gcur = gnext;
+                    }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+        }
+        __syncthreads();
+        // this transform's d U leaves the planes (and leaves them zero for the next one): a thread owns its elements of the
+        // image's d U over all t, the sum over the rows runs in ascending t
+        for (int i = tid; i < NI * ncg; i += THREADS) {
+            const int p = i / ncg, k = i - p * ncg;
+            float* src = sh_dU + k * NIp + p;
+            const float v = *src;
+            *src = 0.0f;
+            float* d = dst + (size_t)p * C + k;
+            *d = t == 0 ? v : *d + v;
+        }
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void transformer_nc_bwd_kernel(
+    const float* __restrict__ U, const float* __restrict__ theta, const float* __restrict__ d_out,
+    float* __restrict__ d_U, float* __restrict__ d_theta, int T, int Hi, int Wi, int C, int Ho, int Wo,
+    int cg, int ngroups, int lds_ordered)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    // per image: `ngroups` channel groups of d U (none without d_U), then the T rows of d theta (none without d_theta)
+    const int per = ngroups + (d_theta ? T : 0);
+    const int b = blockIdx.x / per, y = blockIdx.x - b * per;
+    if (y < ngroups) {
+        const int c0 = y * cg;
+        transformer_nc_du(theta, d_out, d_U, b, c0, min(cg, C - c0), T, Hi, Wi, C, Ho, Wo, lds_ordered, smem + 32);
+    } else {
+        const size_t row = (size_t)b * T + (y - ngroups);
+        transformer_nc_dtheta(U + (size_t)b * Hi * Wi * C, theta + row * 6, d_out + row * Ho * Wo * C, d_theta + row * 6,
+                              Hi, Wi, C, Ho, Wo, smem);
     }
 }
 
@@ -1164,6 +1279,30 @@ extern "C" int air_transformer_bwd(const float* U, const float* theta, const flo
     if (rc) return rc;
     hipLaunchKernelGGL(transformer_bwd_kernel, dim3(B), dim3(THREADS), lds, air_stream(stream),
                        U, theta, d_out, d_U, d_theta, Hi, Wi, Ho, Wo, d_U ? lds_ordered(air_stream(stream)) : 1);
+    AIR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int air_transformer_nc_bwd(const float* U, const float* theta, const float* d_out, float* d_U, float* d_theta,
+                                      int B, int T, int Hi, int Wi, int C, int Ho, int Wo, void* stream) {
+    if (!U || !theta || !d_out || (!d_U && !d_theta) || B <= 0 || T <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || Ho <= 0 || Wo <= 0)
+        return AIR_EINVAL;
+    // the bound of air_transformer_bwd on one channel's planes
+    const size_t NIp = ((size_t)Hi * Wi + 3) & ~(size_t)3;
+    if ((40 + 2 * NIp) * sizeof(float) > AIR_LDS_LIMIT) return AIR_ELIMIT;
+    if ((long)Ho * Wo > INT32_MAX || (long)B * T > INT32_MAX) return AIR_ELIMIT;       // what the kernel indexes with an int
+    // channels per d U workgroup: one per wave, as many as have their plane in LDS at once
+    const size_t fit = (AIR_LDS_LIMIT / sizeof(float) - 32) / NIp;
+    int cg = C < NC_WAVES ? C : NC_WAVES;
+    if ((size_t)cg > fit) cg = (int)fit;                       // (fit >= 2 under the bound above)
+    const int ngroups = d_U ? (C + cg - 1) / cg : 0;
+    const long blocks = (long)B * ((long)ngroups + (d_theta ? T : 0));
+    if (blocks > INT32_MAX) return AIR_ELIMIT;
+    const size_t lds = (32 + (d_U ? (size_t)cg * NIp : 0)) * sizeof(float);
+    int rc = ensure_lds(transformer_nc_bwd_kernel, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(transformer_nc_bwd_kernel, dim3((unsigned)blocks), dim3(THREADS), lds, air_stream(stream),
+                       U, theta, d_out, d_U, d_theta, T, Hi, Wi, C, Ho, Wo, cg, ngroups, d_U ? lds_ordered(air_stream(stream)) : 1);
     AIR_CHECK_LAUNCH();
     return 0;
 }
