@@ -215,7 +215,9 @@ typedef struct {
 /* number of K-slabs a ksplit request produces for contraction depth K */
 int air_gemm_slabs(int K, int ksplit);
 int air_gemm(const air_gemm_t* g, void* stream);
-/* name of the kernel function `g` dispatches to, as rocprofv3 prints it (profiling aid) */
+/* name of the kernel function `g` dispatches to, as rocprofv3 prints it.  Host-only, and the SAME decision as the launch:
+ * both read one dispatch plan, so a descriptor air_gemm refuses (AIR_EINVAL / AIR_EALIGN / AIR_ELIMIT) gets that code here
+ * instead of a name, and a name returned here is the kernel air_gemm launches */
 int air_gemm_kernel_name(const air_gemm_t* g, char* buf, int n);
 
 /* dst[i] = bf16(src[i]), round to nearest even: the twin of an array whose producer could not write it (the flat

@@ -3,6 +3,9 @@ code, so with made-up pointers of the right alignment every case is asked which 
 GPU suite from testing only the fallback kernels: a case that drifts to another family, tile or epilogue fails HERE."""
 import collections
 import ctypes as C
+import json
+import os
+import sys
 
 import pytest
 
@@ -10,6 +13,7 @@ import gemm_edge_cases as gec
 from air import _hip as H
 
 BASE = 1 << 20                                   # made-up addresses, 1 MiB apart: every operand 256-byte aligned before its offset
+NAMES_JSON = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_edge_kernel_names.json")
 
 
 def _name(c):
@@ -162,7 +166,71 @@ def test_leading_dimension_checks_follow_the_epilogue():
     assert H.lib().air_gemm_kernel_name(C.byref(g), buf, 128) == -1
 
 
+def _fwd0(prec, K, lda, **more):
+    g = H.Gemm()
+    g.A, g.B, g.C, g.q0, g.q1, g.q2 = (BASE * i for i in range(1, 7))
+    g.M, g.N, g.K, g.lda, g.ldb, g.ldc, g.epi, g.precision = 17, 32, K, lda, 32, 32, H.EPI_LSTM_FWD0, prec
+    for k, v in more.items():
+        setattr(g, k, v)
+    return g
+
+
+def _tp(N, ksplit):
+    g = H.Gemm()
+    g.A, g.B, g.C, g.B16 = (BASE * i for i in range(1, 5))
+    g.M, g.N, g.K, g.lda, g.ldb, g.ldc, g.precision, g.tile_m, g.tile_n, g.ksplit = 64, N, 128, 128, N, N, 1, 8, 4, ksplit
+    return g
+
+
+def _tiled(tile, job=False):
+    g = H.Gemm()
+    g.A, g.B, g.C = (BASE * i for i in range(1, 4))
+    g.M, g.N, g.K, g.lda, g.ldb, g.ldc, g.tile_m, g.tile_n = 17, 32, 64, 64, 32, 32, tile[0], tile[1]
+    if job:
+        g.step_job = C.pointer(H.StepJob(dyn=4 * BASE, istate=5 * BASE))
+    return g
+
+
+REFUSED = [
+    # the four-unit column map of AIR_EPI_LSTM_FWD0 only exists in the lean kernels: odd K keeps a descriptor out of them
+    ("fwd0 odd K fp32", _fwd0(0, 21, 21), -3),
+    ("fwd0 odd K bf16", _fwd0(1, 21, 21), -3),
+    # C16 of AIR_EPI_LSTM_FWD0 is the padded image twin only the twin kernels write; without a twin of B none of them serves it
+    ("fwd0 C16 without twins", _fwd0(1, 64, 64, C16=7 * BASE), -3),
+    # the padded-A16 form: lda is the twin's stride and has to hold K rounded up to 8
+    ("fwd0 padded A16 lda 16 K 20", _fwd0(1, 20, 16, A16=7 * BASE, B16p=8 * BASE, i0=2), -3),
+    # tile (8, 4), the throughput kernel: split-K only, whole 64-column tiles only
+    ("tile 8x4 ksplit 1", _tp(128, 1), -1),
+    ("tile 8x4 N 96", _tp(96, 2), -3),
+    # a tile outside the instantiated ones is refused before the grid or the carried job's planes are sized by it
+    ("tile -1x1", _tiled((-1, 1)), -1),
+    ("tile -1x1 with a step job", _tiled((-1, 1), job=True), -1),
+    ("tile 2x1", _tiled((2, 1)), -1),
+]
+
+
+@pytest.mark.parametrize("what,g,code", REFUSED, ids=[r[0] for r in REFUSED])
+def test_the_name_and_the_launch_refuse_alike(what, g, code):
+    """air_gemm_kernel_name formats the plan air_gemm launches, so a descriptor the launch refuses gets the same code and no name"""
+    buf = C.create_string_buffer(128)
+    named = H.lib().air_gemm_kernel_name(C.byref(g), buf, 128)
+    assert named != 0, (what, buf.value)
+    # (air_gemm itself only once the host-only query has refused the descriptor: these pointers are made up)
+    assert H.lib().air_gemm(C.byref(g), None) == named == code, what
+
+
+def test_the_reported_names_are_the_pinned_ones():
+    """tests/golden/gemm_edge_kernel_names.json pins, for every kernel name, how many of the edge cases report it"""
+    with open(NAMES_JSON) as f:
+        pinned = json.load(f)
+    assert dict(collections.Counter(_name(c) for c in CASES)) == pinned
+
+
 if __name__ == "__main__":
+    if "--write-names" in sys.argv:                  # the pin of test_the_reported_names_are_the_pinned_ones: rewrite it on purpose only
+        with open(NAMES_JSON, "w") as f:
+            json.dump(dict(sorted(collections.Counter(_name(c) for c in CASES).items())), f, indent=1)
+            f.write("\n")
     print("| family | tile | layout | arm | cases |\n|---|---|---|---|---|")
     for r in coverage_rows():
         print("| %s | %s | %s | %s | %d |" % r)

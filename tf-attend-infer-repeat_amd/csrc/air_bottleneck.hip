@@ -19,16 +19,8 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 constexpr int THREADS = 256;
 constexpr int PAD = 8;
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ unsigned short bf16_of(float x) { return (unsigned short)(pack_bf16(x, 0.0f) & 0xffffu); }
 
 // 16-byte load of a row-major operand with the out-of-range case redirected to element 0 (branch-free;
 // the caller zeroes what was out of range when it consumes the value)
@@ -73,7 +65,7 @@ struct FwdArgs {
 
 // K1 = width of X (the last recognition layer), compile-time
 // TW: X, Wml and Wg are read from their bf16 twins (the producing GEMM's C16 / Adam's shadow): half the bytes through the
-// CU's vector-memory path (65 instead of 129 KB per workgroup), no conversion; the RNE twins are what pack_bf16 makes of
+// CU's vector-memory path (65 instead of 129 KB per workgroup), no conversion; the RNE twins are what air_pack_bf16 makes of
 // the fp32 arrays, so both forms give the same bits.
 template <int K1, bool TW>
 __global__ __launch_bounds__(THREADS) void bottleneck_fwd_kernel(FwdArgs a)
@@ -183,7 +175,7 @@ __global__ __launch_bounds__(THREADS) void bottleneck_fwd_kernel(FwdArgs a)
     for (int i = 0; i < NX; ++i) {
         const int t = tid + THREADS * i, row = t / (K1 / 4), c4 = t % (K1 / 4);
         const float4 x = zero_unless(m0 + row < M, vx[i]);
-        uint2 w; w.x = pack_bf16(x.x, x.y); w.y = pack_bf16(x.z, x.w);
+        uint2 w; w.x = air_pack_bf16(x.x, x.y); w.y = air_pack_bf16(x.z, x.w);
         *reinterpret_cast<uint2*>(&A1[row * L1 + c4 * 4]) = w;
     }
 #pragma unroll
@@ -195,8 +187,8 @@ __global__ __launch_bounds__(THREADS) void bottleneck_fwd_kernel(FwdArgs a)
             if (c >= Z2) continue;
             const int col = c < Z ? c : 64 + (c - Z);
             uint4 w;
-            w.x = pack_bf16(comp(vw[i][0], j), comp(vw[i][1], j)); w.y = pack_bf16(comp(vw[i][2], j), comp(vw[i][3], j));
-            w.z = pack_bf16(comp(vw[i][4], j), comp(vw[i][5], j)); w.w = pack_bf16(comp(vw[i][6], j), comp(vw[i][7], j));
+            w.x = air_pack_bf16(comp(vw[i][0], j), comp(vw[i][1], j)); w.y = air_pack_bf16(comp(vw[i][2], j), comp(vw[i][3], j));
+            w.z = air_pack_bf16(comp(vw[i][4], j), comp(vw[i][5], j)); w.w = air_pack_bf16(comp(vw[i][6], j), comp(vw[i][7], j));
             *reinterpret_cast<uint4*>(&B1[col * L1 + wg_[i] * 8]) = w;
         }
     }
@@ -207,8 +199,8 @@ __global__ __launch_bounds__(THREADS) void bottleneck_fwd_kernel(FwdArgs a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             uint4 w;
-            w.x = pack_bf16(comp(t8[0], j), comp(t8[1], j)); w.y = pack_bf16(comp(t8[2], j), comp(t8[3], j));
-            w.z = pack_bf16(comp(t8[4], j), comp(t8[5], j)); w.w = pack_bf16(comp(t8[6], j), comp(t8[7], j));
+            w.x = air_pack_bf16(comp(t8[0], j), comp(t8[1], j)); w.y = air_pack_bf16(comp(t8[2], j), comp(t8[3], j));
+            w.z = air_pack_bf16(comp(t8[4], j), comp(t8[5], j)); w.w = air_pack_bf16(comp(t8[6], j), comp(t8[7], j));
             *reinterpret_cast<uint4*>(&B2[(gq * 4 + j) * L2 + gg * 8]) = w;
         }
     }
@@ -233,9 +225,9 @@ __global__ __launch_bounds__(THREADS) void bottleneck_fwd_kernel(FwdArgs a)
             a.ml[(size_t)m * Z2 + u] = mean;
             a.ml[(size_t)m * Z2 + Z + u] = lv;
             a.z[(size_t)m * a.ldz + u] = zz;
-            if (a.z16) a.z16[(size_t)m * a.ldz + u] = bf16_of(zz);
+            if (a.z16) a.z16[(size_t)m * a.ldz + u] = air_bf16_of(zz);
         }
-        A2[row * L2 + u] = (uok && m < M) ? bf16_of(zz) : (unsigned short)0;
+        A2[row * L2 + u] = (uok && m < M) ? air_bf16_of(zz) : (unsigned short)0;
     }
     __syncthreads();
 
@@ -250,7 +242,7 @@ __global__ __launch_bounds__(THREADS) void bottleneck_fwd_kernel(FwdArgs a)
         if (m < M && n < H) {
             const float gv = air_softplus(ag[q] + b_g);
             a.g[(size_t)m * H + n] = gv;
-            if (a.g16) a.g16[(size_t)m * H + n] = bf16_of(gv);
+            if (a.g16) a.g16[(size_t)m * H + n] = air_bf16_of(gv);
         }
     }
 }
@@ -367,14 +359,14 @@ __global__ __launch_bounds__(THREADS) void bottleneck_bwd_kernel(BwdArgs a)
     for (int i = 0; i < NX; ++i) {
         const int t = tid + THREADS * i, row = t / (H / 4), c4 = t % (H / 4);
         const float4 x = zero_unless(m0 + row < M, vx[i]);
-        uint2 w; w.x = pack_bf16(x.x, x.y); w.y = pack_bf16(x.z, x.w);
+        uint2 w; w.x = air_pack_bf16(x.x, x.y); w.y = air_pack_bf16(x.z, x.w);
         *reinterpret_cast<uint2*>(&A1[row * L1 + c4 * 4]) = w;
     }
 #pragma unroll
     for (int i = 0; i < NG; ++i) {
         const int t = tid + THREADS * i, row = t / (H / 4), c4 = t % (H / 4);
         const float4 x = zero_unless(row < Z, vg[i]);
-        uint2 w; w.x = pack_bf16(x.x, x.y); w.y = pack_bf16(x.z, x.w);
+        uint2 w; w.x = air_pack_bf16(x.x, x.y); w.y = air_pack_bf16(x.z, x.w);
         *reinterpret_cast<uint2*>(&B1[row * L1 + c4 * 4]) = w;
     }
     }
@@ -387,7 +379,7 @@ __global__ __launch_bounds__(THREADS) void bottleneck_bwd_kernel(BwdArgs a)
         if (TW) *reinterpret_cast<uint2*>(&B2[row * L2 + c4 * 4]) = vmh[i];
         else {
             const float4 x = zero_unless(j0 + row < K1, vm[i]);       // 2Z % 4 == 0 (Z even): whole quads
-            uint2 w; w.x = pack_bf16(x.x, x.y); w.y = pack_bf16(x.z, x.w);
+            uint2 w; w.x = air_pack_bf16(x.x, x.y); w.y = air_pack_bf16(x.z, x.w);
             *reinterpret_cast<uint2*>(&B2[row * L2 + c4 * 4]) = w;
         }
     }
@@ -410,10 +402,10 @@ __global__ __launch_bounds__(THREADS) void bottleneck_bwd_kernel(BwdArgs a)
         if (uok && m < M) {
             if (blockIdx.y == 0) {
                 a.d_ml[(size_t)m * Z2 + u] = dmean; a.d_ml[(size_t)m * Z2 + Z + u] = dlv;
-                if (a.d_ml16) { a.d_ml16[(size_t)m * Z2 + u] = bf16_of(dmean); a.d_ml16[(size_t)m * Z2 + Z + u] = bf16_of(dlv); }
+                if (a.d_ml16) { a.d_ml16[(size_t)m * Z2 + u] = air_bf16_of(dmean); a.d_ml16[(size_t)m * Z2 + Z + u] = air_bf16_of(dlv); }
             }
-            A2[row * L2 + u] = bf16_of(dmean);
-            A2[row * L2 + Z + u] = bf16_of(dlv);
+            A2[row * L2 + u] = air_bf16_of(dmean);
+            A2[row * L2 + Z + u] = air_bf16_of(dlv);
         }
     }
     __syncthreads();
@@ -429,7 +421,7 @@ __global__ __launch_bounds__(THREADS) void bottleneck_bwd_kernel(BwdArgs a)
         if (m < M && jn < K1) {
             const float dxv = ax[q] * (1.0f - expf(-e_x[q]));
             a.d_x[(size_t)m * K1 + jn] = dxv;
-            if (a.d_x16) a.d_x16[(size_t)m * K1 + jn] = bf16_of(dxv);
+            if (a.d_x16) a.d_x16[(size_t)m * K1 + jn] = air_bf16_of(dxv);
         }
     }
 }

@@ -31,17 +31,6 @@ AIR_STAMPS_READER(air_debug_stamps_gemm)
 
 using namespace airg;
 
-namespace airg {
-// air_gemm_bf16.hip: the bf16-twin-operand kernels
-int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb);
-int twin_launch(const Args& a, int tm, int tn, bool tb, dim3 grid, hipStream_t s);
-void twin_kernel_name(const Args& a, int tm, int tn, bool tb, char* buf, int n);
-bool fwd0_padded(const Args& a);
-int xw_tp_ok(const Args& a, int precision, bool ta, bool tb, int ksplit);
-int xw_tp_launch(const Args& a, int job_planes_hint, hipStream_t s);
-int xw_tp_columns(const Args& a);
-}
-
 namespace {
 
 // ---------------------------------------------------------------------------
@@ -543,7 +532,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16v2_kernel(Args a)
             const int c = u / (BM * 16), row = (u / 16) % BM, hh = u & 15;
             const float4& x = va[i >> 1][i & 1];
             uint2 w;
-            w.x = pack_bf16(x.x, x.y); w.y = pack_bf16(x.z, x.w);
+            w.x = air_pack_bf16(x.x, x.y); w.y = air_pack_bf16(x.z, x.w);
             // half of the swizzled 16-byte slot of k-run hh >> 1
             if (u < R * BM * 16)
                 *reinterpret_cast<uint2*>(&ImgA[(c * BM + row) * KB + (((hh >> 1) ^ (row & 7)) << 3) + (hh & 1) * 4]) = w;
@@ -555,7 +544,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16v2_kernel(Args a)
                 const int c = u / (BN * 16), col = (u / 16) % BN, hh = u & 15;
                 const float4& x = vbk[i >> 1][i & 1];
                 uint2 w;
-                w.x = pack_bf16(x.x, x.y); w.y = pack_bf16(x.z, x.w);
+                w.x = air_pack_bf16(x.x, x.y); w.y = air_pack_bf16(x.z, x.w);
                 if (u < R * BN * 16)
                     *reinterpret_cast<uint2*>(&ImgB[(c * BN + col) * KB + (((hh >> 1) ^ (col & 7)) << 3) + (hh & 1) * 4]) = w;
             }
@@ -570,8 +559,8 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16v2_kernel(Args a)
                         const int col = q * 4 + e;
                         auto el = [&](int r) { const float4& x = vbn[i][r]; return e == 0 ? x.x : e == 1 ? x.y : e == 2 ? x.z : x.w; };
                         uint4 w;
-                        w.x = pack_bf16(el(0), el(1)); w.y = pack_bf16(el(2), el(3));
-                        w.z = pack_bf16(el(4), el(5)); w.w = pack_bf16(el(6), el(7));
+                        w.x = air_pack_bf16(el(0), el(1)); w.y = air_pack_bf16(el(2), el(3));
+                        w.z = air_pack_bf16(el(4), el(5)); w.w = air_pack_bf16(el(6), el(7));
                         *reinterpret_cast<uint4*>(&ImgB[(c * BN + col) * KB + ((g ^ (col & 7)) << 3)]) = w;
                     }
                 }
@@ -858,98 +847,41 @@ __global__ __launch_bounds__(THREADS) void gemm_f32v2_kernel(Args a)
 }
 
 
-bool use_bf16_v2(const Args& a, bool ta, bool tb);
+// ---------------------------------------------------------------------------
+// host: every fp32-operand kernel instantiation, once -- (template arguments) -> (function, dynamic LDS bytes)
+// ---------------------------------------------------------------------------
+// (a row: {Inst{family, tm, tn, ta, tb, epi, af32, r}, function, dynamic LDS bytes})
+#define FB(KERNEL, F, TM, TN, TA, TB) {{F, TM, TN, TA, TB, -1, false, 0}, reinterpret_cast<const void*>(&KERNEL<TM, TN, TA, TB>), 0}
+#define FB3(KERNEL, F, TM, TN) FB(KERNEL, F, TM, TN, false, false), FB(KERNEL, F, TM, TN, true, false), FB(KERNEL, F, TM, TN, false, true)
+#define F32V2_(TM, TN, TB, EPI) \
+    {{F32V2, TM, TN, false, TB, EPI, false, 0}, reinterpret_cast<const void*>(&gemm_f32v2_kernel<TM, TN, TB, EPI>), F32V2Cfg<TM, TN>::BYTES}
+#define V2(TM, TN, TB, EPI) \
+    {{BF16V2, TM, TN, false, TB, EPI, false, 0}, reinterpret_cast<const void*>(&gemm_bf16v2_kernel<TM, TN, TB, EPI>), 0}, F32V2_(TM, TN, TB, EPI)
+#define TILE(TM, TN) \
+    FB3(gemm_f32_kernel, F32, TM, TN), FB3(gemm_bf16_kernel, BF16, TM, TN), V2(TM, TN, false, AIR_EPI_GENERIC), V2(TM, TN, true, AIR_EPI_GENERIC)
+const Kern KERNELS[] = {
+    TILE(1, 1), TILE(1, 2), TILE(1, 4), TILE(2, 2), TILE(2, 4), TILE(4, 1), TILE(4, 2), TILE(4, 4),
+    // the lean kernels are instantiated per epilogue; a fused epilogue exists for its one tile shape (resolve_tile)
+    V2(1, 4, false, AIR_EPI_LSTM_FWD), V2(1, 2, false, AIR_EPI_REPARAM_FWD), V2(1, 1, false, AIR_EPI_LSTM_FWD0),
+    V2(1, 1, false, AIR_EPI_LSTM_BWD), V2(1, 1, false, AIR_EPI_LSTM_BWD_TAIL), V2(1, 1, false, AIR_EPI_REPARAM_BWD),
+    V2(1, 1, true, AIR_EPI_LSTM_BWD), V2(1, 1, true, AIR_EPI_LSTM_BWD_TAIL), V2(1, 1, true, AIR_EPI_REPARAM_BWD),
+    // exact-fp32 LSTM step on four-unit x four-gate tiles (as the bf16-twin path does): 4 x the workgroups, a quarter of
+    // the operand bytes each
+    F32V2_(1, 1, false, EPI_LSTM_FWD_Q)};
+#undef TILE
+#undef V2
+#undef F32V2_
+#undef FB3
+#undef FB
+template <int N> constexpr int count_of(const Kern (&)[N]) { return N; }
 
-template <int TM, int TN, bool TA, bool TB>
-int launch(const air_gemm_t* g, const Args& a0, hipStream_t s) {
-    Args a = a0;
-    constexpr int BM = 16 * TM, BN = 16 * TN;
-    const bool grouped = a.gstride != 16;
-    const int ncols = grouped ? a.gwidth : a.N;
-    const int tile_cols = a.epi == AIR_EPI_LSTM_FWD0 ? 4 : (grouped ? 16 : BN);      // units (grouped) or columns per tile
-    dim3 grid((ncols + tile_cols - 1) / tile_cols, (a.M + BM - 1) / BM, 1);
-    const int ks = g->ksplit > 1 ? g->ksplit : 1;
-    a.kslab = ((a.K + ks - 1) / ks + 3) & ~3;
-    if (a.job_on) {
-        // enough planes for ~1 quad of noise per thread (the prologue then ends well inside the GEMM)
-        const long quads = (a.job.n_normal + 3) / 4 + (a.job.n_uniform + 3) / 4 + (a.job.twin_n + 3) / 4;
-        const long plane = (long)grid.x * grid.y * THREADS;
-        long planes = (quads + plane - 1) / plane;
-        a.job_on = (int)(planes < 1 ? 1 : (planes > 16 ? 16 : planes));
-    }
-    grid.z = (a.K + a.kslab - 1) / a.kslab + a.job_on;
-    a.slab_stride = (long)a.M * a.ldc;
-    // bf16 twins of the operands supplied and this (tile, epilogue, layout) exists as a twin kernel
-    if (g->precision == 1 && !TA && twin_rounds(a, TM, TN, false, TB) > 0) return twin_launch(a, TM, TN, TB, grid, s);
-    // AIR_EPI_LSTM_FWD0's C16 is the padded image twin only the twin kernels write (air_hip.h): nobody else may be asked for it
-    if (a.epi == AIR_EPI_LSTM_FWD0 && a.C16) return AIR_EALIGN;
-    // ... and a PADDED A16 (i0 bit 1) redefines lda as the twin's stride: the kernels below would read the fp32 A with it
-    if (fwd0_padded(a)) return AIR_EALIGN;
-    // the lean kernels are instantiated per epilogue; a fused epilogue exists for its one tile shape
-    // (resolve_tile) -- any other combination would be a dispatch bug
-    constexpr bool T14 = TM == 1 && TN == 4, T12 = TM == 1 && TN == 2, T11 = TM == 1 && TN == 1;
-    const int epi = a.epi;
-    const bool epi_ok = epi == AIR_EPI_GENERIC || (epi == AIR_EPI_LSTM_FWD && T14 && !TB) || (epi == AIR_EPI_REPARAM_FWD && T12 && !TB) ||
-                        (epi == AIR_EPI_LSTM_FWD0 && T11 && !TB && !TA) ||
-                        ((epi == AIR_EPI_LSTM_BWD || epi == AIR_EPI_LSTM_BWD_TAIL || epi == AIR_EPI_REPARAM_BWD) && T11);
-    if (!epi_ok) return AIR_EINVAL;
-    // the four-unit column map of LSTM_FWD0 only exists in the lean kernels
-    if (epi == AIR_EPI_LSTM_FWD0 && !use_bf16_v2(a, TA, TB)) return AIR_EALIGN;
-#define AIR_V2_LAUNCH(KERNEL, LDS)                                                                                     \
-    do {                                                                                                                \
-        if (epi == AIR_EPI_GENERIC) hipLaunchKernelGGL((KERNEL<TM, TN, TB, AIR_EPI_GENERIC>), grid, dim3(THREADS), LDS, s, a);      \
-        else if constexpr (T14 && !TB) hipLaunchKernelGGL((KERNEL<1, 4, false, AIR_EPI_LSTM_FWD>), grid, dim3(THREADS), LDS, s, a);   \
-        else if constexpr (T12 && !TB) hipLaunchKernelGGL((KERNEL<1, 2, false, AIR_EPI_REPARAM_FWD>), grid, dim3(THREADS), LDS, s, a); \
-        else if constexpr (T11) {                                                                                      \
-            if constexpr (!TB) { if (epi == AIR_EPI_LSTM_FWD0) { hipLaunchKernelGGL((KERNEL<1, 1, false, AIR_EPI_LSTM_FWD0>), grid, dim3(THREADS), LDS, s, a); break; } } \
-            if (epi == AIR_EPI_LSTM_BWD) hipLaunchKernelGGL((KERNEL<1, 1, TB, AIR_EPI_LSTM_BWD>), grid, dim3(THREADS), LDS, s, a);   \
-            else if (epi == AIR_EPI_LSTM_BWD_TAIL) hipLaunchKernelGGL((KERNEL<1, 1, TB, AIR_EPI_LSTM_BWD_TAIL>), grid, dim3(THREADS), LDS, s, a); \
-            else hipLaunchKernelGGL((KERNEL<1, 1, TB, AIR_EPI_REPARAM_BWD>), grid, dim3(THREADS), LDS, s, a);             \
-        }                                                                                                               \
-    } while (0)
-    if constexpr (T14 && !TB && !TA) {
-        // exact-fp32 LSTM step on four-unit x four-gate tiles (as the bf16-twin path does): 4 x the workgroups, a quarter of
-        // the operand bytes each
-        if (g->precision == 0 && epi == AIR_EPI_LSTM_FWD && (a.gwidth & 3) == 0 && use_bf16_v2(a, TA, TB) && !a.job_on) {
-            using CfgQ = F32V2Cfg<1, 1>;
-            auto kq = gemm_f32v2_kernel<1, 1, false, EPI_LSTM_FWD_Q>;
-            const int rcq = air_grant_lds(reinterpret_cast<const void*>(kq), CfgQ::BYTES);
-            if (rcq) return rcq;
-            dim3 gq((a.gwidth + 3) / 4, grid.y, grid.z);
-            hipLaunchKernelGGL(kq, gq, dim3(THREADS), CfgQ::BYTES, s, a);
-            AIR_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    if (g->precision == 1) {
-        const bool v2 = use_bf16_v2(a, TA, TB);
-        if (v2) AIR_V2_LAUNCH(gemm_bf16v2_kernel, 0);
-        else hipLaunchKernelGGL((gemm_bf16_kernel<TM, TN, TA, TB>), grid, dim3(THREADS), 0, s, a);
-    }
-    else if (use_bf16_v2(a, TA, TB)) {   // same operand requirements
-        using Cfg = F32V2Cfg<TM, TN>;
-        if (Cfg::BYTES > 48 * 1024) {
-            // opt-in to the large dynamic LDS once per (kernel function, device): all epilogue variants of this tile
-            const void* fns[] = {
-                reinterpret_cast<const void*>(&gemm_f32v2_kernel<TM, TN, TB, AIR_EPI_GENERIC>),
-                T14 && !TB ? reinterpret_cast<const void*>(&gemm_f32v2_kernel<1, 4, false, AIR_EPI_LSTM_FWD>) : nullptr,
-                T12 && !TB ? reinterpret_cast<const void*>(&gemm_f32v2_kernel<1, 2, false, AIR_EPI_REPARAM_FWD>) : nullptr,
-                T11 ? reinterpret_cast<const void*>(&gemm_f32v2_kernel<1, 1, TB, AIR_EPI_LSTM_BWD>) : nullptr,
-                T11 ? reinterpret_cast<const void*>(&gemm_f32v2_kernel<1, 1, TB, AIR_EPI_LSTM_BWD_TAIL>) : nullptr,
-                T11 ? reinterpret_cast<const void*>(&gemm_f32v2_kernel<1, 1, TB, AIR_EPI_REPARAM_BWD>) : nullptr,
-                T11 && !TB ? reinterpret_cast<const void*>(&gemm_f32v2_kernel<1, 1, false, AIR_EPI_LSTM_FWD0>) : nullptr};
-            for (const void* fn : fns)
-                if (fn) {
-                    const int rc = air_grant_lds(fn, Cfg::BYTES);
-                    if (rc) return rc;
-                }
-        }
-        AIR_V2_LAUNCH(gemm_f32v2_kernel, Cfg::BYTES);
-    } else
-        hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, TA, TB>), grid, dim3(THREADS), 0, s, a);
-#undef AIR_V2_LAUNCH
-    AIR_CHECK_LAUNCH();
-    return 0;
+const Kern* find_kernel(const Inst& inst) {
+    int n = count_of(KERNELS);
+    const Kern* k = KERNELS;
+    if (inst.family == BF16TW || inst.family == XWX_GLDS || inst.family == XW_TP) k = twin_kernels(n);
+    for (int i = 0; i < n; ++i)
+        if (k[i].inst == inst) return k + i;
+    return nullptr;
 }
 
 void resolve_tile(const air_gemm_t* g, int& tm, int& tn) {
@@ -978,22 +910,149 @@ bool use_bf16_v2(const Args& a, bool ta, bool tb) {
            (tb || ((a.N & 1) == 0 && (a.gstride & 1) == 0 && (a.gwidth & 1) == 0));
 }
 
-template <bool TA, bool TB>
-int pick_tile(const air_gemm_t* g, const Args& a, hipStream_t s) {
-    int tm, tn;
-    resolve_tile(g, tm, tn);
-#define AIR_TILE(TM_, TN_) if (tm == TM_ && tn == TN_) return launch<TM_, TN_, TA, TB>(g, a, s)
-    AIR_TILE(1, 1); AIR_TILE(1, 2); AIR_TILE(1, 4); AIR_TILE(2, 2); AIR_TILE(2, 4); AIR_TILE(4, 1); AIR_TILE(4, 2); AIR_TILE(4, 4);
-#undef AIR_TILE
-    return AIR_EINVAL;
+// k-range per grid.z slab: K over ksplit, rounded up to whole k-steps of 4
+int kslab_of(int K, int ksplit) {
+    const int ks = ksplit > 1 ? ksplit : 1;
+    return ((K + ks - 1) / ks + 3) & ~3;
+}
+
+// grid.z planes given to the carried step job: enough for ~1 quad of noise per thread (the prologue then ends well
+// inside the GEMM), at most `cap`
+int job_planes(const Args& a, dim3 grid, int cap) {
+    if (!a.job_on) return 0;
+    const long quads = (a.job.n_normal + 3) / 4 + (a.job.n_uniform + 3) / 4 + (a.job.twin_n + 3) / 4;
+    const long plane = (long)grid.x * grid.y * THREADS;
+    const long planes = (quads + plane - 1) / plane;
+    return (int)(planes < 1 ? 1 : (planes > cap ? cap : planes));
+}
+
+int images_of(const Args& a) { return (a.kslab + 63) / 64; }
+
+// AIR_EPI_LSTM_FWD0 with A16 and air_gemm_t.i0 bit 1: A16 is the PADDED twin of the batch and lda ITS row stride, not A's --
+// no fp32-operand kernel may serve such a descriptor (plan_gemm refuses it where twin_rounds() is 0).  Bit 0 of i0
+// then keeps register staging.
+bool fwd0_padded(const Args& a) { return a.epi == AIR_EPI_LSTM_FWD0 && a.A16 != nullptr && (a.i0 & 2) != 0; }
+bool fwd0_glds(const Args& a) { return fwd0_padded(a) && (a.i0 & 1) == 0; }
+
+// Which (tile, epilogue, layout) combinations exist as twin kernels, and with how many images per round.
+// Returns R (> 0) or 0 when this descriptor has to take the fp32-operand kernels.
+int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb) {
+    // (a panel-blocked B twin serves the untransposed 16- / 32-column tiles and the four-unit LSTM tiles; everything
+    // else needs the row-major twin)
+    const bool pnl_tile = !tb && a.B16p != nullptr && ((tm == 1 && tn == 1) || (tm == 2 && tn == 2) || (tm == 1 && tn == 4));
+    if (ta || (!a.B16 && !pnl_tile)) return 0;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool af32 = a.A16 == nullptr;
+    // whole 16-byte pieces only: the ragged shapes keep the fp32-operand kernels
+    // (the twin-A x.Wx may read a PADDED twin -- air_gemm_t.i0 bit 1 says so; without it A16 is an ordinary twin with the
+    // leading dimension of A.  K itself may then be ragged: the 16-byte piece that straddles it ends inside the row's zero
+    // pad -- lda >= K rounded up to 8 -- and the panel twin of B is addressed by the true K)
+    const bool padded = fwd0_padded(a);
+    if (af32) { if (!al16(a.A) || (a.lda & 3) || (a.K & 3) || (a.kslab & 3) || (a.epi == AIR_EPI_LSTM_FWD0 && !al16(a.C16))) return 0; }
+    else if (padded) { if (!al16(a.A16) || (a.lda & 7) || a.lda < ((a.K + 7) & ~7) || !pnl_tile || tb) return 0; }
+    else if (!al16(a.A16) || (a.lda & 7) || (a.K & 7) || (a.kslab & 7)) return 0;
+    if (pnl_tile) { if (!al16(a.B16p)) return 0; }
+    else if (!al16(a.B16) || (a.ldb & 7)) return 0;
+    if (tb) { if ((a.K & 7) || (a.kslab & 7)) return 0; }
+    else if ((a.N & 7) || (a.gstride & 7) || (a.gwidth & 7)) return 0;
+    const int nimg = images_of(a);
+    const int e = a.epi;
+    if (tm == 1 && tn == 1) {
+        // the hoisted x.Wx carrying the first LSTM step: four-unit tiles over the WHOLE contraction, fp32 or twin A
+        // (K <= 2560: all 40 images in ONE round -- one memory round trip, 160 KB of LDS, one workgroup per CU)
+        if (e == AIR_EPI_LSTM_FWD0)
+            return (!tb && (a.gwidth & 3) == 0 && (int)((a.K + a.kslab - 1) / a.kslab) == 1)
+                       ? ((nimg <= 40 && nimg > 16) ? 40 : 16) : 0;
+        if (af32) return 0;
+        if (e == AIR_EPI_GENERIC || ((e == AIR_EPI_LSTM_BWD || e == AIR_EPI_LSTM_BWD_TAIL) && tb)) return nimg <= 4 ? 4 : (nimg <= 8 ? 8 : 16);
+        return 0;
+    }
+    // (untransposed B: gwidth % 8 == 0 above, so AIR_EPI_LSTM_FWD always runs on the four-unit tiles: plan_gemm)
+    if (tm == 1 && tn == 4) return (!af32 && !tb && e == AIR_EPI_LSTM_FWD) ? 4 : 0;
+    if (tm == 2 && tn == 2) return e == AIR_EPI_GENERIC ? (af32 ? (tb ? 0 : 8) : (nimg <= 4 ? 4 : 8)) : 0;
+    if (tm == 4 && tn == 2) return (e == AIR_EPI_GENERIC && !tb) ? 4 : 0;
+    if (tm == 4 && tn == 4) return (e == AIR_EPI_GENERIC && !tb) ? 4 : 0;      // 64 x 64: the deep x.Wx of large canvases
+    return 0;
+}
+
+// tile (8, 4) of the ABI = the throughput kernel (fp32 A x bf16 shadow, split-K slabs): eligibility
+int xw_tp_ok(const Args& a, int precision, bool ta, bool tb, int ksplit) {
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (precision != 1 || ta || tb || !a.B16 || a.epi != AIR_EPI_GENERIC || ksplit <= 1) return AIR_EINVAL;
+    if ((a.M % 64) || (a.N % 64) || (a.kslab % 64) || (a.K % 64)) return AIR_EALIGN;
+    if (!al16(a.A) || !al16(a.B16) || (a.lda & 3) || (a.ldb & 7)) return AIR_EALIGN;
+    return 0;
+}
+
+// 64 x 128 tiles when they still give every CU a workgroup
+int xw_tp_columns(const Args& a) {
+    const long slabs = (a.K + a.kslab - 1) / a.kslab;
+    const bool wide = (a.N % 128) == 0 && (long)(a.N / 128) * (a.M / 64) * slabs >= 256;
+    return wide ? 128 : 64;
 }
 
 }  // namespace
 
+int airg::plan_gemm(const air_gemm_t* g, const Args& filled, Plan& p) {
+    Args& a = p.args;
+    a = filled;
+    a.kslab = kslab_of(a.K, g->ksplit);
+    a.slab_stride = (long)a.M * a.ldc;
+    const bool ta = g->transA != 0, tb = g->transB != 0;
+    if (g->tile_m == 8 && g->tile_n == 4) {
+        const int ok = xw_tp_ok(a, g->precision, ta, tb, g->ksplit);
+        if (ok) return ok;
+        const int cols = xw_tp_columns(a);
+        p.inst = Inst{XW_TP, 8, 4, false, false, AIR_EPI_GENERIC, false, cols};
+        p.grid = dim3(a.N / cols, a.M / 64, 1);
+        a.job_on = job_planes(a, p.grid, 64);
+    } else {
+        int tm, tn;
+        resolve_tile(g, tm, tn);
+        // a tile outside the instantiated ones is refused before anything is sized by it (every tile has a fallback kernel)
+        if (!find_kernel(Inst{F32, tm, tn, false, false, -1, false, 0})) return AIR_EINVAL;
+        const bool grouped = a.gstride != 16;
+        const int ncols = grouped ? a.gwidth : a.N;
+        const int tile_cols = a.epi == AIR_EPI_LSTM_FWD0 ? 4 : (grouped ? 16 : 16 * tn);      // units (grouped) or columns per tile
+        p.grid = dim3((ncols + tile_cols - 1) / tile_cols, (a.M + 16 * tm - 1) / (16 * tm), 1);
+        a.job_on = job_planes(a, p.grid, 16);
+        // bf16 twins of the operands supplied and this (tile, epilogue, layout) exists as a twin kernel
+        const int r = g->precision == 1 ? twin_rounds(a, tm, tn, ta, tb) : 0;
+        const bool lean = use_bf16_v2(a, ta, tb);
+        bool quad = false;      // AIR_EPI_LSTM_FWD on 16-column tiles of four units x four gates (8-byte pieces of 4 units)
+        if (r > 0) {
+            // padded twin A: LDS-DMA staging unless air_gemm_t.i0 bit 0 keeps the register staging of the same operands (A/B arm)
+            p.inst = Inst{fwd0_glds(a) ? XWX_GLDS : BF16TW, tm, tn, false, tb, a.epi, a.A16 == nullptr, r};
+            quad = tm == 1 && tn == 4;
+        } else {
+            // AIR_EPI_LSTM_FWD0's C16 is the padded image twin only the twin kernels write (air_hip.h), a PADDED A16 redefines
+            // lda as the twin's stride, and the four-unit column map only exists in the lean kernels
+            if (a.epi == AIR_EPI_LSTM_FWD0 && (a.C16 || fwd0_padded(a) || !lean)) return AIR_EALIGN;
+            if (lean) p.inst = Inst{g->precision == 1 ? BF16V2 : F32V2, tm, tn, false, tb, a.epi, false, 0};
+            else p.inst = Inst{g->precision == 1 ? BF16 : F32, tm, tn, ta, tb, -1, false, 0};
+            quad = lean && g->precision == 0 && a.epi == AIR_EPI_LSTM_FWD && (a.gwidth & 3) == 0 && !a.job_on;
+        }
+        if (quad) {
+            p.inst.tn = 1;
+            p.inst.epi = EPI_LSTM_FWD_Q;
+            const unsigned wide = p.grid.x;
+            p.grid.x = (a.gwidth + 3) / 4;
+            // the carried job's planes were sized for the wide tiles' grid: same number of workgroups
+            if (a.job_on) a.job_on = (int)((a.job_on * wide + p.grid.x - 1) / p.grid.x);
+        }
+    }
+    p.grid.z = (a.K + a.kslab - 1) / a.kslab + a.job_on;
+    const Kern* k = find_kernel(p.inst);
+    if (!k) return AIR_EINVAL;                           // a (family, epilogue, layout) combination nobody instantiated
+    if ((size_t)k->lds > AIR_LDS_LIMIT) return AIR_ELIMIT;
+    p.fn = k->fn;
+    p.lds = k->lds;
+    return 0;
+}
+
 extern "C" int air_gemm_slabs(int K, int ksplit) {
     if (K <= 0) return 0;
-    const int ks = ksplit > 1 ? ksplit : 1;
-    const int kslab = ((K + ks - 1) / ks + 3) & ~3;
+    const int kslab = kslab_of(K, ksplit);
     return (K + kslab - 1) / kslab;
 }
 
@@ -1001,58 +1060,46 @@ static int fill_args(const air_gemm_t* g, Args& a);
 
 extern "C" int air_gemm(const air_gemm_t* g, void* stream) {
     Args a;
-    const int rc = fill_args(g, a);
+    Plan p;
+    int rc = fill_args(g, a);
+    if (!rc) rc = plan_gemm(g, a, p);
     if (rc) return rc;
-    hipStream_t s = air_stream(stream);
-    if (g->tile_m == 8 && g->tile_n == 4) {
-        // the throughput tiling (fp32 A x bf16 shadow, split-K slabs): air_gemm_bf16.hip::gemm_xw_tp_kernel
-        const int ks = g->ksplit > 1 ? g->ksplit : 1;
-        a.kslab = ((a.K + ks - 1) / ks + 3) & ~3;
-        const int ok = xw_tp_ok(a, g->precision, g->transA != 0, g->transB != 0, g->ksplit);
-        return ok ? ok : xw_tp_launch(a, 0, s);
-    }
-    if (g->transA) return pick_tile<true, false>(g, a, s);
-    if (g->transB) return pick_tile<false, true>(g, a, s);
-    return pick_tile<false, false>(g, a, s);
+    // opt-in to the large dynamic LDS once per (kernel function, device).  A lean fp32 tile grants every epilogue variant
+    // of that tile with its first launch: callers warm up eagerly, and no driver call may land inside stream capture
+    // (air_common.h, air_grant_lds) when a later launch of the same tile carries another epilogue
+    if (p.inst.family == F32V2 && p.lds > 48 * 1024)
+        for (const Kern& k : KERNELS) {
+            const Inst& i = k.inst;
+            const bool variant = i.family == F32V2 && i.tm == p.inst.tm && i.tn == p.inst.tn && i.tb == p.inst.tb &&
+                                 (i.epi == EPI_LSTM_FWD_Q) == (p.inst.epi == EPI_LSTM_FWD_Q);
+            if (variant && (rc = air_grant_lds(k.fn, k.lds)) != 0) return rc;
+        }
+    else if ((rc = air_grant_lds(p.fn, p.lds)) != 0) return rc;
+    void* kargs[] = {&p.args};
+    (void)hipLaunchKernel(p.fn, p.grid, dim3(THREADS), kargs, p.lds, air_stream(stream));
+    AIR_CHECK_LAUNCH();
+    return 0;
 }
 
-/* name of the kernel function this descriptor dispatches to, as rocprofv3 prints it
- * (profiling tools match per-op timings with the kernel-trace summary by it) */
+/* name of the kernel function this descriptor dispatches to, as rocprofv3 prints it (profiling tools match per-op
+ * timings with the kernel-trace summary by it) -- or the refusal air_gemm answers the descriptor with */
 extern "C" int air_gemm_kernel_name(const air_gemm_t* g, char* buf, int n) {
     Args a;
-    const int rc = fill_args(g, a);
+    Plan p;
+    int rc = fill_args(g, a);
     if (rc) return rc;
     if (!buf || n <= 0) return AIR_EINVAL;
-    int tm, tn;
-    resolve_tile(g, tm, tn);
-    const bool ta = g->transA != 0, tb = g->transB != 0;
-    {
-        const int ks = g->ksplit > 1 ? g->ksplit : 1;
-        a.kslab = ((a.K + ks - 1) / ks + 3) & ~3;
+    if ((rc = plan_gemm(g, a, p)) != 0) return rc;
+    static const char* const FAMILY[] = {"f32", "bf16", "f32v2", "bf16v2", "bf16tw", "xwx_glds", "xw_tp"};
+    const Inst& i = p.inst;
+    auto tf = [](bool b) { return b ? "true" : "false"; };
+    const char* fam = FAMILY[i.family];
+    switch (i.family) {           // the template parameter list of each family
+        case F32: case BF16: snprintf(buf, n, "gemm_%s_kernel<%d, %d, %s, %s>", fam, i.tm, i.tn, tf(i.ta), tf(i.tb)); break;
+        case F32V2: case BF16V2: snprintf(buf, n, "gemm_%s_kernel<%d, %d, %s, %d>", fam, i.tm, i.tn, tf(i.tb), i.epi); break;
+        case BF16TW: snprintf(buf, n, "gemm_%s_kernel<%d, %d, %s, %d, %s, %d>", fam, i.tm, i.tn, tf(i.tb), i.epi, tf(i.af32), i.r); break;
+        default: snprintf(buf, n, "gemm_%s_kernel<%d>", fam, i.r); break;
     }
-    if (g->tile_m == 8 && g->tile_n == 4) {
-        const int ok = xw_tp_ok(a, g->precision, ta, tb, g->ksplit);
-        if (ok) return ok;
-        snprintf(buf, n, "gemm_xw_tp_kernel<%d>", xw_tp_columns(a));
-        return 0;
-    }
-    if (g->precision == 1 && !ta && twin_rounds(a, tm, tn, false, tb) > 0) {
-        twin_kernel_name(a, tm, tn, tb, buf, n);
-        return 0;
-    }
-    // what only the twin kernels serve (launch<> refuses the same descriptors): the padded image twin, in or out
-    if (a.epi == AIR_EPI_LSTM_FWD0 && (a.C16 || fwd0_padded(a))) return AIR_EALIGN;
-    if (g->precision == 1 && use_bf16_v2(a, ta, tb))
-        snprintf(buf, n, "gemm_bf16v2_kernel<%d, %d, %s, %d>", tm, tn, tb ? "true" : "false", g->epi);
-    else if (g->precision == 0 && use_bf16_v2(a, ta, tb)) {
-        if (g->epi == AIR_EPI_LSTM_FWD && !ta && !tb && (a.gwidth & 3) == 0 && !g->step_job)
-            snprintf(buf, n, "gemm_f32v2_kernel<1, 1, false, %d>", EPI_LSTM_FWD_Q);
-        else
-            snprintf(buf, n, "gemm_f32v2_kernel<%d, %d, %s, %d>", tm, tn, tb ? "true" : "false", g->epi);
-    }
-    else
-        snprintf(buf, n, "gemm_%s_kernel<%d, %d, %s, %s>", g->precision == 1 ? "bf16" : "f32", tm, tn,
-                 ta ? "true" : "false", tb ? "true" : "false");
     return 0;
 }
 

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
                 const int u = tid + THREADS * i;
                 const int c = u / (BM * 16), row = (u / 16) % BM, hh = u & 15;
                 uint2 w;
-                w.x = pack_bf16(vaf[i].x, vaf[i].y); w.y = pack_bf16(vaf[i].z, vaf[i].w);
+                w.x = air_pack_bf16(vaf[i].x, vaf[i].y); w.y = air_pack_bf16(vaf[i].z, vaf[i].w);
                 if (u < R * BM * 16)
                     *reinterpret_cast<uint2*>(&ImgA[(c * BM + row) * KB + (((hh >> 1) ^ (row & 7)) << 3) + (hh & 1) * 4]) = w;
                 if (twin_out) {                       // (block-uniform) columns K .. ldt - 1 were loaded as zeros: the pad
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(THREADS) void gemm_xw_tp_kernel(Args a)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             uint2 w;
-            w.x = pack_bf16(va[d][i].x, va[d][i].y); w.y = pack_bf16(va[d][i].z, va[d][i].w);
+            w.x = air_pack_bf16(va[d][i].x, va[d][i].y); w.y = air_pack_bf16(va[d][i].z, va[d][i].w);
             *reinterpret_cast<uint2*>(&ImgA[buf][la + 16 * i * KB]) = w;
         }
 #pragma unroll
@@ -572,189 +572,38 @@ __global__ __launch_bounds__(THREADS) void gemm_xwx_glds_kernel(Args a)
     AIR_STAMP(61);
 }
 
-template <int R>
-int launch_glds(const Args& a, dim3 grid, hipStream_t s) {
-    using Cfg = TwCfg<1, 1, R>;
-    auto kern = gemm_xwx_glds_kernel<R>;
-    const int rc = air_grant_lds(reinterpret_cast<const void*>(kern), Cfg::BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), Cfg::BYTES, s, a);
-    AIR_CHECK_LAUNCH();
-    return 0;
-}
-
-template <int TM, int TN, bool TB, int EPI_, bool AF32, int R>
-int launch_one(const Args& a, dim3 grid, hipStream_t s) {
-    using Cfg = TwCfg<TM, TN, R>;
-    auto kern = gemm_bf16tw_kernel<TM, TN, TB, EPI_, AF32, R>;
-    const int rc = air_grant_lds(reinterpret_cast<const void*>(kern), Cfg::BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, grid, dim3(THREADS), Cfg::BYTES, s, a);
-    AIR_CHECK_LAUNCH();
-    return 0;
-}
-
-int images_of(const Args& a) { return (a.kslab + 63) / 64; }
+// every bf16-twin kernel instantiation, once: (template arguments) -> (function, dynamic LDS bytes)
+#define TW(TM_, TN_, TB_, EPI__, AF_, R_)                                                                               \
+    {{BF16TW, TM_, TN_, false, TB_, EPI__, AF_, R_}, reinterpret_cast<const void*>(&gemm_bf16tw_kernel<TM_, TN_, TB_, EPI__, AF_, R_>), \
+     TwCfg<TM_, TN_, R_>::BYTES}
+#define GLDS(R_) {{XWX_GLDS, 1, 1, false, false, AIR_EPI_LSTM_FWD0, false, R_}, reinterpret_cast<const void*>(&gemm_xwx_glds_kernel<R_>), TwCfg<1, 1, R_>::BYTES}
+#define TP(BN_) {{XW_TP, 8, 4, false, false, AIR_EPI_GENERIC, false, BN_}, reinterpret_cast<const void*>(&gemm_xw_tp_kernel<BN_>), 0}
+const Kern TWIN_KERNELS[] = {
+    // the hoisted x.Wx carrying the first LSTM step: fp32 or twin A, register or (padded twin A) LDS-DMA staging
+    TW(1, 1, false, AIR_EPI_LSTM_FWD0, true, 16), TW(1, 1, false, AIR_EPI_LSTM_FWD0, true, 40),
+    TW(1, 1, false, AIR_EPI_LSTM_FWD0, false, 16), TW(1, 1, false, AIR_EPI_LSTM_FWD0, false, 40), GLDS(16), GLDS(40),
+    TW(1, 1, false, AIR_EPI_GENERIC, false, 4), TW(1, 1, false, AIR_EPI_GENERIC, false, 8), TW(1, 1, false, AIR_EPI_GENERIC, false, 16),
+    TW(1, 1, true, AIR_EPI_GENERIC, false, 4), TW(1, 1, true, AIR_EPI_GENERIC, false, 8), TW(1, 1, true, AIR_EPI_GENERIC, false, 16),
+    TW(1, 1, true, AIR_EPI_LSTM_BWD, false, 4), TW(1, 1, true, AIR_EPI_LSTM_BWD, false, 8), TW(1, 1, true, AIR_EPI_LSTM_BWD, false, 16),
+    TW(1, 1, true, AIR_EPI_LSTM_BWD_TAIL, false, 4), TW(1, 1, true, AIR_EPI_LSTM_BWD_TAIL, false, 8), TW(1, 1, true, AIR_EPI_LSTM_BWD_TAIL, false, 16),
+    // AIR_EPI_LSTM_FWD: 16-column tiles of four units x four gates (8-byte pieces of 4 units)
+    TW(1, 1, false, EPI_LSTM_FWD_Q, false, 4),
+    TW(2, 2, false, AIR_EPI_GENERIC, true, 8), TW(2, 2, false, AIR_EPI_GENERIC, false, 4), TW(2, 2, false, AIR_EPI_GENERIC, false, 8),
+    TW(2, 2, true, AIR_EPI_GENERIC, false, 4), TW(2, 2, true, AIR_EPI_GENERIC, false, 8),
+    TW(4, 2, false, AIR_EPI_GENERIC, true, 4), TW(4, 2, false, AIR_EPI_GENERIC, false, 4),
+    TW(4, 4, false, AIR_EPI_GENERIC, true, 4), TW(4, 4, false, AIR_EPI_GENERIC, false, 4),
+    // tile (8, 4) of the ABI = the throughput kernel (128 x 64 or 64 x 128 per workgroup, quadrant per wave)
+    TP(64), TP(128)};
+#undef TW
+#undef GLDS
+#undef TP
 
 }  // namespace
 
-namespace airg {
-
-// AIR_EPI_LSTM_FWD0 with A16 and air_gemm_t.i0 bit 1: A16 is the PADDED twin of the batch and lda ITS row stride, not A's --
-// no fp32-operand kernel may serve such a descriptor (air_gemm.hip refuses it where twin_rounds() is 0).  Bit 0 of i0
-// then keeps register staging; the launch and its reported name both ask here.
-bool fwd0_padded(const Args& a) { return a.epi == AIR_EPI_LSTM_FWD0 && a.A16 != nullptr && (a.i0 & 2) != 0; }
-bool fwd0_glds(const Args& a) { return fwd0_padded(a) && (a.i0 & 1) == 0; }
-
-// Which (tile, epilogue, layout) combinations exist as twin kernels, and with how many images per round.
-// Returns R (> 0) or 0 when this descriptor has to take the fp32-operand kernels.
-int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb) {
-    // (a panel-blocked B twin serves the untransposed 16- / 32-column tiles and the four-unit LSTM tiles; everything
-    // else needs the row-major twin)
-    const bool pnl_tile = !tb && a.B16p != nullptr && ((tm == 1 && tn == 1) || (tm == 2 && tn == 2) || (tm == 1 && tn == 4));
-    if (ta || (!a.B16 && !pnl_tile)) return 0;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool af32 = a.A16 == nullptr;
-    // whole 16-byte pieces only: the ragged shapes keep the fp32-operand kernels
-    // (the twin-A x.Wx may read a PADDED twin -- air_gemm_t.i0 bit 1 says so; without it A16 is an ordinary twin with the
-    // leading dimension of A.  K itself may then be ragged: the 16-byte piece that straddles it ends inside the row's zero
-    // pad -- lda >= K rounded up to 8 -- and the panel twin of B is addressed by the true K)
-    const bool padded = fwd0_padded(a);
-    if (af32) { if (!al16(a.A) || (a.lda & 3) || (a.K & 3) || (a.kslab & 3) || (a.epi == AIR_EPI_LSTM_FWD0 && !al16(a.C16))) return 0; }
-    else if (padded) { if (!al16(a.A16) || (a.lda & 7) || a.lda < ((a.K + 7) & ~7) || !pnl_tile || tb) return 0; }
-    else if (!al16(a.A16) || (a.lda & 7) || (a.K & 7) || (a.kslab & 7)) return 0;
-    if (pnl_tile) { if (!al16(a.B16p)) return 0; }
-    else if (!al16(a.B16) || (a.ldb & 7)) return 0;
-    if (tb) { if ((a.K & 7) || (a.kslab & 7)) return 0; }
-    else if ((a.N & 7) || (a.gstride & 7) || (a.gwidth & 7)) return 0;
-    const int nimg = images_of(a);
-    const int e = a.epi;
-    if (tm == 1 && tn == 1) {
-        // the hoisted x.Wx carrying the first LSTM step: four-unit tiles over the WHOLE contraction, fp32 or twin A
-        // (K <= 2560: all 40 images in ONE round -- one memory round trip, 160 KB of LDS, one workgroup per CU)
-        if (e == AIR_EPI_LSTM_FWD0)
-            return (!tb && (a.gwidth & 3) == 0 && (int)((a.K + a.kslab - 1) / a.kslab) == 1)
-                       ? ((nimg <= 40 && nimg > 16) ? 40 : 16) : 0;
-        if (af32) return 0;
-        if (e == AIR_EPI_GENERIC || ((e == AIR_EPI_LSTM_BWD || e == AIR_EPI_LSTM_BWD_TAIL) && tb)) return nimg <= 4 ? 4 : (nimg <= 8 ? 8 : 16);
-        return 0;
-    }
-    if (tm == 1 && tn == 4) return (!af32 && !tb && e == AIR_EPI_LSTM_FWD) ? 4 : 0;       // (quad-unit tiles when gwidth % 4 == 0: twin_launch)
-    if (tm == 2 && tn == 2) return e == AIR_EPI_GENERIC ? (af32 ? (tb ? 0 : 8) : (nimg <= 4 ? 4 : 8)) : 0;
-    if (tm == 4 && tn == 2) return (e == AIR_EPI_GENERIC && !tb) ? 4 : 0;
-    if (tm == 4 && tn == 4) return (e == AIR_EPI_GENERIC && !tb) ? 4 : 0;      // 64 x 64: the deep x.Wx of large canvases
-    return 0;
+const Kern* airg::twin_kernels(int& n) {
+    n = (int)(sizeof(TWIN_KERNELS) / sizeof(TWIN_KERNELS[0]));
+    return TWIN_KERNELS;
 }
-
-int twin_launch(const Args& a, int tm, int tn, bool tb, dim3 grid, hipStream_t s) {
-    const int r = twin_rounds(a, tm, tn, false, tb);
-    const bool af32 = a.A16 == nullptr;
-    const int e = a.epi;
-#define TW(TM_, TN_, TB_, EPI__, AF_, R_) return launch_one<TM_, TN_, TB_, EPI__, AF_, R_>(a, grid, s)
-    if (tm == 1 && tn == 1 && e == AIR_EPI_LSTM_FWD0) {
-        // padded twin A: LDS-DMA staging unless air_gemm_t.i0 bit 0 keeps the register staging of the same operands (A/B arm)
-        const bool glds = fwd0_glds(a);
-        if (r == 40) {
-            if (af32) TW(1, 1, false, AIR_EPI_LSTM_FWD0, true, 40);
-            if (glds) return launch_glds<40>(a, grid, s);
-            TW(1, 1, false, AIR_EPI_LSTM_FWD0, false, 40);
-        }
-        if (af32) TW(1, 1, false, AIR_EPI_LSTM_FWD0, true, 16);
-        if (glds) return launch_glds<16>(a, grid, s);
-        TW(1, 1, false, AIR_EPI_LSTM_FWD0, false, 16);
-    }
-    if (tm == 1 && tn == 1) {
-        if (e == AIR_EPI_GENERIC) {
-            if (tb) { if (r == 4) TW(1, 1, true, AIR_EPI_GENERIC, false, 4); if (r == 8) TW(1, 1, true, AIR_EPI_GENERIC, false, 8); TW(1, 1, true, AIR_EPI_GENERIC, false, 16); }
-            if (r == 4) TW(1, 1, false, AIR_EPI_GENERIC, false, 4); if (r == 8) TW(1, 1, false, AIR_EPI_GENERIC, false, 8); TW(1, 1, false, AIR_EPI_GENERIC, false, 16);
-        }
-        if (e == AIR_EPI_LSTM_BWD) { if (r == 4) TW(1, 1, true, AIR_EPI_LSTM_BWD, false, 4); if (r == 8) TW(1, 1, true, AIR_EPI_LSTM_BWD, false, 8); TW(1, 1, true, AIR_EPI_LSTM_BWD, false, 16); }
-        if (e == AIR_EPI_LSTM_BWD_TAIL) { if (r == 4) TW(1, 1, true, AIR_EPI_LSTM_BWD_TAIL, false, 4); if (r == 8) TW(1, 1, true, AIR_EPI_LSTM_BWD_TAIL, false, 8); TW(1, 1, true, AIR_EPI_LSTM_BWD_TAIL, false, 16); }
-    }
-    if (tm == 1 && tn == 4) {
-        // AIR_EPI_LSTM_FWD: 16-column tiles of four units x four gates where the layout allows (8-byte pieces of 4 units)
-        if ((a.gwidth & 3) == 0) {
-            dim3 gq((a.gwidth + 3) / 4, grid.y, grid.z);
-            Args b = a;
-            if (a.job_on) {          // the carried job's planes were sized for the wide tiles' grid: same number of workgroups
-                b.job_on = (int)((a.job_on * grid.x + gq.x - 1) / gq.x);
-                if (b.job_on < 1) b.job_on = 1;
-                gq.z = grid.z - a.job_on + b.job_on;
-            }
-            return launch_one<1, 1, false, EPI_LSTM_FWD_Q, false, 4>(b, gq, s);
-        }
-        // (the wide tiles read the row-major twin: a gate-interleaved panel twin is laid out for the four-unit tiles only)
-        if (!a.B16) return AIR_EINVAL;
-        Args w = a;
-        w.B16p = nullptr;
-        return launch_one<1, 4, false, AIR_EPI_LSTM_FWD, false, 4>(w, grid, s);
-    }
-    if (tm == 2 && tn == 2) {
-        if (af32) TW(2, 2, false, AIR_EPI_GENERIC, true, 8);
-        if (tb) { if (r == 4) TW(2, 2, true, AIR_EPI_GENERIC, false, 4); TW(2, 2, true, AIR_EPI_GENERIC, false, 8); }
-        if (r == 4) TW(2, 2, false, AIR_EPI_GENERIC, false, 4); TW(2, 2, false, AIR_EPI_GENERIC, false, 8);
-    }
-    if (tm == 4 && tn == 2) { if (af32) TW(4, 2, false, AIR_EPI_GENERIC, true, 4); TW(4, 2, false, AIR_EPI_GENERIC, false, 4); }
-    if (tm == 4 && tn == 4) { if (af32) TW(4, 4, false, AIR_EPI_GENERIC, true, 4); TW(4, 4, false, AIR_EPI_GENERIC, false, 4); }
-#undef TW
-    return AIR_EINVAL;
-}
-
-// tile (8, 4) of the ABI = the throughput kernel (128 x 64 per workgroup, quadrant per wave): eligibility and launch
-int xw_tp_ok(const Args& a, int precision, bool ta, bool tb, int ksplit) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    if (precision != 1 || ta || tb || !a.B16 || a.epi != AIR_EPI_GENERIC || ksplit <= 1) return AIR_EINVAL;
-    if ((a.M % 64) || (a.N % 64) || (a.kslab % 64) || (a.K % 64)) return AIR_EALIGN;
-    if (!al16(a.A) || !al16(a.B16) || (a.lda & 3) || (a.ldb & 7)) return AIR_EALIGN;
-    return 0;
-}
-
-// 64 x 128 tiles when they still give every CU a workgroup
-int xw_tp_columns(const Args& a) {
-    const long slabs = (a.K + a.kslab - 1) / a.kslab;
-    const bool wide = (a.N % 128) == 0 && (long)(a.N / 128) * (a.M / 64) * slabs >= 256;
-    return wide ? 128 : 64;
-}
-
-int xw_tp_launch(const Args& a0, int job_planes_hint, hipStream_t s) {
-    Args a = a0;
-    const bool wide = xw_tp_columns(a0) == 128;
-    dim3 grid(a.N / (wide ? 128 : 64), a.M / 64, 1);
-    if (a.job_on) {
-        const long quads = (a.job.n_normal + 3) / 4 + (a.job.n_uniform + 3) / 4 + (a.job.twin_n + 3) / 4;
-        const long plane = (long)grid.x * grid.y * THREADS;
-        long planes = (quads + plane - 1) / plane;
-        a.job_on = (int)(planes < 1 ? 1 : (planes > 64 ? 64 : planes));
-    }
-    (void)job_planes_hint;
-    grid.z = (a.K + a.kslab - 1) / a.kslab + a.job_on;
-    a.slab_stride = (long)a.M * a.ldc;
-    a.i1 = 0;
-    if (wide) hipLaunchKernelGGL(gemm_xw_tp_kernel<128>, grid, dim3(THREADS), 0, s, a);
-    else hipLaunchKernelGGL(gemm_xw_tp_kernel<64>, grid, dim3(THREADS), 0, s, a);
-    AIR_CHECK_LAUNCH();
-    return 0;
-}
-
-void twin_kernel_name(const Args& a, int tm, int tn, bool tb, char* buf, int n) {
-    if (tm == 1 && tn == 4 && (a.gwidth & 3) == 0) {
-        snprintf(buf, n, "gemm_bf16tw_kernel<1, 1, false, %d, false, 4>", EPI_LSTM_FWD_Q);
-        return;
-    }
-    if (tm == 1 && tn == 1 && fwd0_glds(a)) {
-        snprintf(buf, n, "gemm_xwx_glds_kernel<%d>", twin_rounds(a, tm, tn, false, tb));
-        return;
-    }
-    if (tm == 1 && tn == 1 && a.epi == AIR_EPI_LSTM_FWD0) {
-        snprintf(buf, n, "gemm_bf16tw_kernel<1, 1, false, %d, %s, %d>", AIR_EPI_LSTM_FWD0, a.A16 == nullptr ? "true" : "false",
-                 twin_rounds(a, tm, tn, false, tb));
-        return;
-    }
-    snprintf(buf, n, "gemm_bf16tw_kernel<%d, %d, %s, %d, %s, %d>", tm, tn, tb ? "true" : "false", a.epi,
-             a.A16 == nullptr ? "true" : "false", twin_rounds(a, tm, tn, false, tb));
-}
-
-}  // namespace airg
 
 namespace {
 
@@ -764,9 +613,9 @@ __global__ __launch_bounds__(256) void bf16_twin_kernel(const float* __restrict_
     const long n4 = n / 4;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
         const float4 v = reinterpret_cast<const float4*>(src)[i];
-        reinterpret_cast<uint2*>(dst)[i] = make_uint2(pack_bf16(v.x, v.y), pack_bf16(v.z, v.w));
+        reinterpret_cast<uint2*>(dst)[i] = make_uint2(air_pack_bf16(v.x, v.y), air_pack_bf16(v.z, v.w));
     }
-    if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) dst[n4 * 4 + threadIdx.x] = bf16_of(src[n4 * 4 + threadIdx.x]);
+    if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4 * 4)) dst[n4 * 4 + threadIdx.x] = air_bf16_of(src[n4 * 4 + threadIdx.x]);
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 // Shared pieces of the GEMM translation units (air_gemm.hip: fp32-operand kernels; air_gemm_bf16.hip:
 // bf16-twin-operand kernels): kernel arguments, the prefetched fused epilogues, the cross-wave reduction
-// and the XCD-aware tile map.  Everything here is inline device code in namespace airg.
+// and the XCD-aware tile map -- inline device code in namespace airg -- and, at the end, the host's dispatch plan.
 #pragma once
 #include "air_common.h"
 #include "air_philox.h"
@@ -23,16 +23,6 @@ __device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
 }
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-// two fp32 -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-// one value, the same rounding: what a consumer's staging conversion would have produced from the fp32 array
-__device__ __forceinline__ unsigned short bf16_of(float v) { return (unsigned short)(pack_bf16(v, 0.0f) & 0xffffu); }
 
 struct Args {
     const float* A; const float* B; float* C;
@@ -206,7 +196,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
             float* c = a.C + (size_t)m * a.ldc + n;
             if (a.accumulate) v += *c;
             *c = v;
-            if (a.C16) a.C16[(size_t)m * a.ldc + n] = bf16_of(v);
+            if (a.C16) a.C16[(size_t)m * a.ldc + n] = air_bf16_of(v);
         }
         return;
     }
@@ -233,7 +223,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                 a.q1[(size_t)m * R + u] = cn;
                 const float hn = tanhf(cn) * so;
                 a.q2[(size_t)m * R + u] = hn;
-                if (a.q2_16) a.q2_16[(size_t)m * R + u] = bf16_of(hn);
+                if (a.q2_16) a.q2_16[(size_t)m * R + u] = air_bf16_of(hn);
             }
         }
         return;
@@ -264,7 +254,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                 a.q1[(size_t)m * R + u] = cn;
                 const float hn = tanhf(cn) * so;
                 a.q2[(size_t)m * R + u] = hn;
-                if (a.q2_16) a.q2_16[(size_t)m * R + u] = bf16_of(hn);
+                if (a.q2_16) a.q2_16[(size_t)m * R + u] = air_bf16_of(hn);
             }
         }
         return;
@@ -300,7 +290,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                 a.q1[(size_t)m * R + u] = cn;
                 const float hn = tanhf(cn) * so;
                 a.q2[(size_t)m * R + u] = hn;
-                if (a.q2_16) a.q2_16[(size_t)m * R + u] = bf16_of(hn);
+                if (a.q2_16) a.q2_16[(size_t)m * R + u] = air_bf16_of(hn);
             }
         } else if (E == AIR_EPI_REPARAM_FWD) {
             // vae.py:16-24: mean | log_var (+bias), sample = mean + eps*sqrt(exp(lv))
@@ -313,7 +303,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                 a.C[(size_t)m * a.ldc + Z + u] = lv;
                 const float zv = mean + pre.f[2] * sqrtf(expf(lv));
                 a.q0[(size_t)m * Z + u] = zv;
-                if (a.q0_16) a.q0_16[(size_t)m * Z + u] = bf16_of(zv);
+                if (a.q0_16) a.q0_16[(size_t)m * Z + u] = air_bf16_of(zv);
             }
         } else if (E == AIR_EPI_LSTM_BWD || E == AIR_EPI_LSTM_BWD_TAIL) {
             // v[0] (+ addend) = d loss / d h'.  p0 = acts, p1 = c_prev, p2 = c, p3 = dc_in (nullable)
@@ -338,7 +328,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                 dg[u] = dgi; dg[R + u] = dgj; dg[2 * R + u] = dgf; dg[3 * R + u] = dgo;
                 if (a.q0_16) {
                     unsigned short* dgb = a.q0_16 + (size_t)mrow * 4 * R;
-                    dgb[u] = bf16_of(dgi); dgb[R + u] = bf16_of(dgj); dgb[2 * R + u] = bf16_of(dgf); dgb[3 * R + u] = bf16_of(dgo);
+                    dgb[u] = air_bf16_of(dgi); dgb[R + u] = air_bf16_of(dgj); dgb[2 * R + u] = air_bf16_of(dgf); dgb[3 * R + u] = air_bf16_of(dgo);
                 }
                 a.q1[idx] = dc * sf;
                 if (a.q2) {
@@ -348,7 +338,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                     ds[u] = s0; ds[R + u] = s1; ds[2 * R + u] = s2; ds[3 * R + u] = s3;
                     if (a.q2_16) {       // the running sum's twin: passed by the caller with the LAST accumulation only
                         unsigned short* dsb = a.q2_16 + (size_t)mrow * 4 * R;
-                        dsb[u] = bf16_of(s0); dsb[R + u] = bf16_of(s1); dsb[2 * R + u] = bf16_of(s2); dsb[3 * R + u] = bf16_of(s3);
+                        dsb[u] = air_bf16_of(s0); dsb[R + u] = air_bf16_of(s1); dsb[2 * R + u] = air_bf16_of(s2); dsb[3 * R + u] = air_bf16_of(s3);
                     }
                 }
             }
@@ -364,7 +354,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
             const float dlv = d * pre.f[2] * 0.5f * sd + klg * 0.5f * (var / pv - 1.0f);
             a.C[(size_t)m * a.ldc + u] = dmean;
             a.C[(size_t)m * a.ldc + Z + u] = dlv;
-            if (a.C16) { a.C16[(size_t)m * a.ldc + u] = bf16_of(dmean); a.C16[(size_t)m * a.ldc + Z + u] = bf16_of(dlv); }
+            if (a.C16) { a.C16[(size_t)m * a.ldc + u] = air_bf16_of(dmean); a.C16[(size_t)m * a.ldc + Z + u] = air_bf16_of(dlv); }
         }
     }
 }
@@ -416,5 +406,31 @@ __device__ __forceinline__ void xcd_tile(int& tile_m, int& tile_n) {
 }
 
 __host__ __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- host: the dispatch plan.  plan_gemm (air_gemm.hip) is the ONE place that decides which kernel a descriptor gets;
+// air_gemm launches the plan and air_gemm_kernel_name formats it, so the two cannot disagree.
+enum Family { F32, BF16, F32V2, BF16V2, BF16TW, XWX_GLDS, XW_TP };
+// the template arguments of one instantiation; what a family does not take stays at false / 0 (epi -1: chosen at run time)
+struct Inst {
+    int family, tm, tn;
+    bool ta, tb;
+    int epi;          // template epilogue id: EPI_LSTM_FWD_Q where AIR_EPI_LSTM_FWD runs on the four-unit tiles
+    bool af32;
+    int r;            // images per round (BF16TW, XWX_GLDS) or columns per workgroup (XW_TP)
+};
+inline bool operator==(const Inst& x, const Inst& y) {
+    return x.family == y.family && x.tm == y.tm && x.tn == y.tn && x.ta == y.ta && x.tb == y.tb && x.epi == y.epi &&
+           x.af32 == y.af32 && x.r == y.r;
+}
+// one row per kernel instantiation: each translation unit lists its own kernels ONCE
+struct Kern { Inst inst; const void* fn; int lds; };     // lds: dynamic LDS bytes
+struct Plan {
+    Inst inst;
+    const void* fn; int lds;
+    dim3 grid;
+    Args args;        // as the kernel receives them (k-slab, slab stride, prologue planes already set)
+};
+int plan_gemm(const air_gemm_t* g, const Args& filled, Plan& p);     // 0, or the refusal air_gemm returns
+const Kern* twin_kernels(int& n);                                    // air_gemm_bf16.hip: BF16TW, XWX_GLDS, XW_TP
 
 }  // namespace airg

@@ -168,15 +168,8 @@ __device__ __forceinline__ const Prob& find_tile(const Table& tab, int block, in
 // registers before rounding.
 // ---------------------------------------------------------------------------
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 constexpr int KB = 64;          // rows per LDS image
 constexpr int NIMG_W = 3;       // images resident per round in the weight-gradient kernel: K <= 192 needs one round
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    const f32x2_t v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
 
 // bf16 tile: as tile_f32, operands rounded to bf16; Img = [operand][image][column][k] shorts of LDS,
 // the fp32 tile is left at its start (64 rows of LS floats, barrier-synchronised).
@@ -261,8 +254,8 @@ __device__ __forceinline__ float tile_bf16(const Prob& pr, int m0, int n0, unsig
                     const int col = 4 * q + j;
                     auto e = [&](int r) { const float4& t = v[c][r]; return j == 0 ? t.x : j == 1 ? t.y : j == 2 ? t.z : t.w; };
                     uint4 w;
-                    w.x = pack_bf16(e(0), e(1)); w.y = pack_bf16(e(2), e(3));
-                    w.z = pack_bf16(e(4), e(5)); w.w = pack_bf16(e(6), e(7));
+                    w.x = air_pack_bf16(e(0), e(1)); w.y = air_pack_bf16(e(2), e(3));
+                    w.z = air_pack_bf16(e(4), e(5)); w.w = air_pack_bf16(e(6), e(7));
                     *reinterpret_cast<uint4*>(&img[(size_t)c * BT * KB + col * KB + ((g ^ (col & 7)) << 3)]) = w;
                 }
             }
