@@ -674,6 +674,61 @@ typedef struct {
 } air_step_lds_t;
 int air_step_lds(int N, int C, int w, int Hs, int Hh, int Hz, int wout_ld, air_step_lds_t* out);
 
+/* ---- stand-alone Concrete and VAE pieces (additive to ABI 6) ----------------------------------------------------------
+ * The ops of the reference's air/concrete.py and the pointwise gradients of air/vae.py as launches of their own, for
+ * callers that compose them with torch.autograd (air/concrete.py, air/vae.py of this package) -- the train step keeps
+ * computing them inside air_attend_fwd / air_attend_bwd and the GEMM epilogues.  Plain element-wise kernels over n fp32
+ * elements (any n >= 1): a grid-stride loop, 16-byte loads and stores when every array of the call is 16-byte aligned
+ * (4-byte ones otherwise) and a scalar tail, no LDS, no atomics; fp32 in the reference's op order, one rounding per op.
+ *
+ * air_scalar_t: an argument the reference takes as a scalar OR a tensor (temperatures, prior log-odds).
+ *   ptr == NULL:             `value`, by value;
+ *   ptr != NULL, stride 0:   ONE device float, read by the kernel when it runs (a slot of `dyn` that a schedule
+ *                            rewrites every step: no host read, a captured graph sees the new value);
+ *   ptr != NULL, stride 1:   [n], one value per element.
+ * AIR_EINVAL (all entry points below, answered on the host before any HIP call): a null descriptor or required pointer,
+ * n < 1, a stride other than 0 or 1, Z < 1. */
+typedef struct { const float* ptr; float value; int32_t stride; } air_scalar_t;
+
+/* concrete.py:4-17 with the uniform sample u [n] given: noise = log(u + eps) - log(1 - u + eps); y = log_odds + noise;
+ * sig_y = sigmoid(y / temperature), and with hard != 0 its tf.round (half to even).  y / sig_y: either may be NULL. */
+int air_concrete_sample_fwd(const float* log_odds, const float* u, const air_scalar_t* temperature, float eps, int hard,
+                            float* y /*nullable*/, float* sig_y /*nullable*/, int64_t n, void* stream);
+/* its gradient: d_log_odds = d_y + (d_sig_y * s * (1 - s)) / temperature with s = sigmoid(y / temperature), the SOFT value
+ * also when the forward was hard (the stop_gradient of concrete.py:15: straight-through).  d_y / d_sig_y: either may be
+ * NULL (a zero gradient), not both. */
+int air_concrete_sample_bwd(const float* y, const air_scalar_t* temperature, const float* d_y /*nullable*/,
+                            const float* d_sig_y /*nullable*/, float* d_log_odds, int64_t n, void* stream);
+/* concrete.py:20-27: y = (log_odds + noise) / temperature -- the expression of air_attend_fwd (AIR_ATT_ZPRE), same bits */
+int air_concrete_presigmoid_fwd(const float* log_odds, const float* u, const air_scalar_t* temperature, float eps,
+                                float* y, int64_t n, void* stream);
+/* d_log_odds = d_y / temperature */
+int air_concrete_presigmoid_bwd(const float* d_y, const air_scalar_t* temperature, float* d_log_odds, int64_t n, void* stream);
+/* concrete.py:30-43: kl = log q(y) - log p(y), log r(y) = log(T_r + eps) - y T_r + a_r - 2 log(1 + exp(-y T_r + a_r) + eps)
+ * for the prior (prior_log_odds, prior_temperature) and the posterior (posterior_log_odds [n], posterior_temperature) --
+ * the expression of air_attend_fwd (AIR_ATT_KL_Z; shared device code), same bits. */
+int air_concrete_kl_fwd(const float* y, const air_scalar_t* prior_log_odds, const air_scalar_t* prior_temperature,
+                        const float* posterior_log_odds, const air_scalar_t* posterior_temperature, float eps,
+                        float* kl, int64_t n, void* stream);
+/* its exact derivatives: with e = exp(-y T + a), D = 1 + e + eps:  d log r / d a = 1 - 2 e / D,  d log r / d y = -T (1 - 2 e / D);
+ * d_y = d_kl (d log q / d y - d log p / d y), d_posterior_log_odds = d_kl d log q / d a, d_prior_log_odds = -d_kl d log p / d a.
+ * Each output may be NULL (not all three); d_prior_log_odds [n] only with a per-element prior_log_odds (stride 1). */
+int air_concrete_kl_bwd(const float* d_kl, const float* y, const air_scalar_t* prior_log_odds,
+                        const air_scalar_t* prior_temperature, const float* posterior_log_odds,
+                        const air_scalar_t* posterior_temperature, float eps, float* d_y /*nullable*/,
+                        float* d_posterior_log_odds /*nullable*/, float* d_prior_log_odds /*nullable*/, int64_t n, void* stream);
+
+/* gradient of the sigmoid that ends the decoder (vae.py:39-41): d_pre = (d_rec * rec) * (1 - rec) from the saved output */
+int air_sigmoid_bwd(const float* d_rec, const float* rec, float* d_pre, int64_t n, void* stream);
+/* gradient of the re-parameterisation (vae.py:22-24) ALONE -- air_reparam_bwd / AIR_EPI_REPARAM_BWD add the VAE-KL term of
+ * the model from att and dyn; this one takes what arrives at the mean and the log-variance from outside instead:
+ *   d_ml[m, j]     = d_z[m, j] + d_mean_in[m, j]
+ *   d_ml[m, Z + j] = ((d_z[m, j] * eps[m, j]) * 0.5) * sqrt(exp(ml[m, Z + j])) + d_lv_in[m, j]
+ * ml / d_ml [M, 2Z] (mean | log_var), d_z / eps / d_mean_in / d_lv_in [M, Z]; the two incoming gradients are nullable
+ * (nothing is added). */
+int air_reparam_bwd_plain(const float* d_z, const float* ml, const float* eps, const float* d_mean_in /*nullable*/,
+                          const float* d_lv_in /*nullable*/, float* d_ml, int M, int Z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,11 @@ class StepLds(C.Structure):
                                          "write_bwd_graph", "limit")]
 
 
+class Scalar(C.Structure):
+    """air_scalar_t: a float by value (ptr NULL), one device float read by the kernel (stride 0), or one per element (stride 1)"""
+    _fields_ = [("ptr", _p), ("value", _f), ("stride", _i)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -194,6 +199,15 @@ _SIGNATURES = {
     "air_render": (C.c_int, [C.POINTER(Render), _p]),
     "air_philox_fill": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.c_uint64, C.c_uint64, _p]),
     "air_step_lds": (C.c_int, [C.c_int] * 7 + [C.POINTER(StepLds)]),
+    "air_concrete_sample_fwd": (C.c_int, [_p, _p, C.POINTER(Scalar), _f, C.c_int, _p, _p, C.c_int64, _p]),
+    "air_concrete_sample_bwd": (C.c_int, [_p, C.POINTER(Scalar), _p, _p, _p, C.c_int64, _p]),
+    "air_concrete_presigmoid_fwd": (C.c_int, [_p, _p, C.POINTER(Scalar), _f, _p, C.c_int64, _p]),
+    "air_concrete_presigmoid_bwd": (C.c_int, [_p, C.POINTER(Scalar), _p, C.c_int64, _p]),
+    "air_concrete_kl_fwd": (C.c_int, [_p, C.POINTER(Scalar), C.POINTER(Scalar), _p, C.POINTER(Scalar), _f, _p, C.c_int64, _p]),
+    "air_concrete_kl_bwd": (C.c_int, [_p, _p, C.POINTER(Scalar), C.POINTER(Scalar), _p, C.POINTER(Scalar), _f, _p, _p, _p,
+                                      C.c_int64, _p]),
+    "air_sigmoid_bwd": (C.c_int, [_p, _p, _p, C.c_int64, _p]),
+    "air_reparam_bwd_plain": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -58,6 +58,18 @@ def _align8(n):
     return (n + 7) & ~7
 
 
+def xavier_uniform_(variables, seed=0):
+    """Fills every 2-D tensor of the name -> tensor mapping with Glorot-uniform values, limit sqrt(6 / (fan_in + fan_out)), from
+    ONE numpy stream seeded by `seed`, in the mapping's order (layers.xavier_initializer, the TF 1.3 default of
+    fully_connected and BasicLSTMCell); 1-D tensors (biases: zeros) are left alone."""
+    rng = np.random.RandomState(seed)
+    with torch.no_grad():
+        for v in variables.values():
+            if v.dim() == 2:
+                limit = math.sqrt(6.0 / (v.shape[0] + v.shape[1]))
+                v.copy_(torch.from_numpy(rng.uniform(-limit, limit, size=tuple(v.shape)).astype(np.float32)))
+
+
 class VariableStore:
     """All trainable variables of one scope in ONE flat fp32 buffer (+ grads,
     Adam m/v) so that the optimizer and the data-parallel all-reduce are a
@@ -193,12 +205,8 @@ class VariableStore:
         """Xavier/Glorot-uniform weights, zero biases -- TF1.3 defaults of
         BasicLSTMCell / layers.fully_connected (limits sqrt(6/(in+out)) as in
         air-model.meta's initializer constants); zero Adam slots, step 0."""
-        rng = np.random.RandomState(seed)
         self.params.zero_()
-        for name, v in self.variables.items():
-            if v.dim() == 2:
-                limit = math.sqrt(6.0 / (v.shape[0] + v.shape[1]))
-                v.copy_(torch.from_numpy(rng.uniform(-limit, limit, size=tuple(v.shape)).astype(np.float32)))
+        xavier_uniform_(self.variables, seed)
         self.m.zero_(); self.v.zero_(); self.grads.zero_(); self.istate.zero_()
         self.shadow_stale = True
 

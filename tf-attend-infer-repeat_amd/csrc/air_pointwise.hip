@@ -3,6 +3,7 @@
 // All are HBM/latency bound; each reads and writes every byte once with
 // coalesced accesses and reduces in a fixed order (deterministic).
 #include "air_common.h"
+#include "air_elementwise.h"
 
 namespace {
 
@@ -137,6 +138,36 @@ __global__ __launch_bounds__(THREADS) void reparam_bwd_kernel(
     dml[(size_t)b * 2 * Z + j] = d + klg * (r[j] - pm) / pv;
     dml[(size_t)b * 2 * Z + Z + j] = d * eps[idx] * 0.5f * sd + klg * 0.5f * (var / pv - 1.0f);
 }
+
+// gradient of the sample alone (vae.py:22-24): what reaches the mean and the log-variance from outside is added, no KL
+__global__ __launch_bounds__(THREADS) void reparam_bwd_plain_kernel(
+    const float* __restrict__ dzs, const float* __restrict__ ml, const float* __restrict__ eps,
+    const float* __restrict__ dmean, const float* __restrict__ dlv, float* __restrict__ dml, long total, int Z)
+{
+    for (long idx = (long)blockIdx.x * THREADS + threadIdx.x; idx < total; idx += (long)gridDim.x * THREADS) {
+        const long b = idx / Z;
+        const int j = (int)(idx - b * Z);
+        const float sd = sqrtf(expf(ml[b * 2 * Z + Z + j]));
+        const float d = dzs[idx];
+        float gm = d, gl = ((d * eps[idx]) * 0.5f) * sd;
+        if (dmean) gm = gm + dmean[idx];
+        if (dlv) gl = gl + dlv[idx];
+        dml[b * 2 * Z + j] = gm;
+        dml[b * 2 * Z + Z + j] = gl;
+    }
+}
+
+// SigmoidGrad of the decoder's last op (vae.py:39-41), from the saved output
+struct SigmoidBwd {
+    const float* g; const float* r; float* out;
+    template <int W> __device__ __forceinline__ void run(long i) const {
+        float gv[W], rv[W], o[W];
+        ew_ld<W>(g, i, gv); ew_ld<W>(r, i, rv);
+#pragma unroll
+        for (int k = 0; k < W; ++k) o[k] = (gv[k] * rv[k]) * (1.0f - rv[k]);
+        ew_st<W>(out, i, o);
+    }
+};
 
 // air_model.py:580-593 + d loss / d running_recon; one workgroup per image
 __global__ __launch_bounds__(THREADS) void bce_kernel(
@@ -308,6 +339,23 @@ extern "C" int air_reparam_bwd(const float* d_zs, const float* ml, const float* 
                        air_stream(stream), d_zs, ml, eps_z, att, dyn, d_ml, B, Z);
     AIR_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int air_reparam_bwd_plain(const float* d_z, const float* ml, const float* eps, const float* d_mean_in,
+                                     const float* d_lv_in, float* d_ml, int M, int Z, void* stream) {
+    if (!d_z || !ml || !eps || !d_ml || M < 1 || Z < 1) return AIR_EINVAL;
+    const long total = (long)M * Z;
+    long blocks = (total + THREADS - 1) / THREADS;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(reparam_bwd_plain_kernel, dim3((int)blocks), dim3(THREADS), 0, air_stream(stream),
+                       d_z, ml, eps, d_mean_in, d_lv_in, d_ml, total, Z);
+    AIR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int air_sigmoid_bwd(const float* d_rec, const float* rec, float* d_pre, int64_t n, void* stream) {
+    if (!d_rec || !rec || !d_pre || n < 1) return AIR_EINVAL;
+    return ew_launch(SigmoidBwd{d_rec, rec, d_pre}, n, ew_al16(d_rec) && ew_al16(rec) && ew_al16(d_pre), stream);
 }
 
 extern "C" int air_bce_fwd_bwd(const float* images, const float* run_recon, const float* dyn,

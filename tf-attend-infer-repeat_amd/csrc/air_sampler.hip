@@ -230,10 +230,7 @@ __global__ __launch_bounds__(THREADS) void attend_fwd_kernel(air_attend_fwd_t a)
         if (!a.train) z_l = rintf(z_l);                   // tf.round (half-to-even) :389-390
         // concrete.py:30-43 (prior and posterior temperatures are both T :403-407); meaningful on lane 3
         const float plo = dyn[AIR_DYN_PRIOR_LOG_ODDS];
-        const float yT = ypre_l * T;
-        const float log_prior = ((logf(T + AIR_EPS) - yT) + plo) - 2.0f * logf((1.0f + expf(-yT + plo)) + AIR_EPS);
-        const float log_post = ((logf(T + AIR_EPS) - yT) + lo) - 2.0f * logf((1.0f + expf(-yT + lo)) + AIR_EPS);
-        const float kl_z_l = log_post - log_prior;
+        const float kl_z_l = concrete_log_density(ypre_l, T, lo) - concrete_log_density(ypre_l, T, plo);
         // gather (uniform broadcasts)
         const float s = __shfl(act, 0, 64), x = __shfl(act, 1, 64), y = __shfl(act, 2, 64);
         const float kl_s = 0.5f * __shfl(term, 0, 64);

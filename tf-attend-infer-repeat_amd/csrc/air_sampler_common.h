@@ -86,9 +86,17 @@ __device__ __forceinline__ void graph_dxy(float g, float Ia, float Ib, float Ic,
 constexpr int MAX_STEPS = AIR_MAX_STEPS;     // the per-image records of the attend / compose / render kernels
 
 // concrete.py:20-27 + air_model.py:385-390: pre-sigmoid sample and z_pres
-__device__ __forceinline__ float concrete_presigmoid(float lo, float u, float T) {
-    const float noise = logf(u + AIR_EPS) - logf((1.0f - u) + AIR_EPS);
-    return (lo + noise) / T;
+__device__ __forceinline__ float concrete_noise(float u, float eps = AIR_EPS) {
+    return logf(u + eps) - logf((1.0f - u) + eps);
+}
+__device__ __forceinline__ float concrete_presigmoid(float lo, float u, float T, float eps = AIR_EPS) {
+    return (lo + concrete_noise(u, eps)) / T;
+}
+// concrete.py:35-37 / :39-41: log density of the pre-sigmoid sample y under a binary Concrete with log-odds `lo` and
+// temperature T -- one expression for the prior and the posterior of attend_fwd_kernel and for air_concrete_kl_fwd
+__device__ __forceinline__ float concrete_log_density(float y, float T, float lo, float eps = AIR_EPS) {
+    const float yT = y * T;
+    return ((logf(T + eps) - yT) + lo) - 2.0f * logf((1.0f + expf(-yT + lo)) + eps);
 }
 
 // ---- compose, the part air_write_fwd and air_render share: one workgroup per image, CF_THREADS threads ----------------
