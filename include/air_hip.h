@@ -729,6 +729,55 @@ int air_sigmoid_bwd(const float* d_rec, const float* rec, float* d_pre, int64_t 
 int air_reparam_bwd_plain(const float* d_z, const float* ml, const float* eps, const float* d_mean_in /*nullable*/,
                           const float* d_lv_in /*nullable*/, float* d_ml, int M, int Z, void* stream);
 
+/* ---- stand-alone CNN front-end (additive to ABI 6) --------------------------------------------------------------------
+ * air_model.py:510-533, the block in front of the LSTM when cnn=True, generalised from the 50 x 50 canvas to S x S:
+ *   conv1 (5x5, stride 1, SAME, 1 -> F, + bias, ReLU) -> pool1 (2x2, stride 2, VALID: S1 = S / 2, an odd last row and column
+ *   are dropped) -> conv2 (F -> F, ReLU) -> pool2 (S2 = S1 / 2) -> conv3 (F -> F, ReLU) -> [B, S2 * S2 * F], (y, x, channel).
+ * fp32 throughout, NHWC tensors, kernels [5, 5, Cin, F] and biases [F] as tf.layers.conv2d stores them.  The train step
+ * does not call these entry points (AIRModel(cnn=True) is not wired yet); they serve air/cnn.py of this package.
+ *
+ * Max-pool routing: the pooled value is the maximum of the four ReLU outputs of its window, its code 2 dy + dx names the
+ * FIRST maximum in row-major window order (what TF's MaxPoolGrad and torch's CPU max_pool2d route the gradient to), one
+ * byte per pooled element.  ReLU's gradient (pre > 0) is read off the saved pooled value: pool(relu(x)) = relu(pool(x)).
+ *
+ * Launches: the forward is ONE launch (a workgroup per image; the un-pooled conv outputs never reach memory), the backward
+ * one launch per image plus one that sums the per-image partials of the variable gradients in ascending image order.  No
+ * atomics: the same inputs give the same bits.  Every inner product is one chain of fmaf in a fixed order, written out at
+ * the top of csrc/air_cnn.hip.
+ *
+ * Limits: 1 <= F <= 8, 4 <= S <= 128, and the LDS of BOTH kernels must fit a workgroup's 160 KiB (S <= 77, 83, 89, 97, 107,
+ * 118 at F = 8 .. 3, S <= 128 at F <= 2); the three entry points give the same answer for the same (B, S, F).
+ * AIR_EINVAL (before any HIP call): a null descriptor or required pointer, some but not all of the four saved tensors,
+ * B < 1, S < 4, F < 1.  AIR_ELIMIT (before any HIP call): F or S beyond the limits above. */
+typedef struct {
+    const float* images;                 /* [B, S * S] (= [B, S, S, 1])                                                */
+    const float* k1; const float* b1;    /* [5, 5, 1, F], [F]                                                          */
+    const float* k2; const float* b2;    /* [5, 5, F, F], [F]                                                          */
+    const float* k3; const float* b3;    /* [5, 5, F, F], [F]                                                          */
+    float* out;                          /* [B, S2 * S2 * F]                                                           */
+    float* pool1; float* pool2;          /* nullable: [B, S1, S1, F], [B, S2, S2, F], what the backward needs ...       */
+    uint8_t* arg1; uint8_t* arg2;        /* ... with their argmax codes; all four or none (the inference forward: `out`
+                                            has the same bits)                                                         */
+    int32_t B, S, F;
+} air_cnn_fwd_t;
+int air_cnn_fwd(const air_cnn_fwd_t* args, void* stream);
+
+typedef struct {
+    const float* d_out; const float* out;           /* [B, S2 * S2 * F]: the incoming gradient, the forward's output   */
+    const float* images;                            /* the forward's input                                             */
+    const float* pool1; const float* pool2;         /* the forward's saved tensors                                     */
+    const uint8_t* arg1; const uint8_t* arg2;
+    const float* k1; const float* k2; const float* k3;
+    float* workspace;                               /* [>= air_cnn_workspace_floats(B, S, F)] floats of scratch        */
+    float* d_k1; float* d_b1; float* d_k2; float* d_b2; float* d_k3; float* d_b3;    /* overwritten, not accumulated    */
+    float* d_images;                                /* nullable: [B, S * S], computed only when given                  */
+    int32_t B, S, F;
+} air_cnn_bwd_t;
+int air_cnn_bwd(const air_cnn_bwd_t* args, void* stream);
+/* floats of `workspace` (the per-image partials of the six variable gradients), or AIR_EINVAL / AIR_ELIMIT for a
+ * (B, S, F) the entry points refuse -- no GPU is touched */
+int64_t air_cnn_workspace_floats(int B, int S, int F);
+
 #ifdef __cplusplus
 }
 #endif

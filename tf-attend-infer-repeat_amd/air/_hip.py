@@ -152,6 +152,19 @@ class Scalar(C.Structure):
     _fields_ = [("ptr", _p), ("value", _f), ("stride", _i)]
 
 
+class CnnFwd(C.Structure):
+    """air_cnn_fwd_t: the four saved tensors (pool1, pool2, arg1, arg2) come together or not at all"""
+    _fields_ = [("images", _p), ("k1", _p), ("b1", _p), ("k2", _p), ("b2", _p), ("k3", _p), ("b3", _p), ("out", _p),
+                ("pool1", _p), ("pool2", _p), ("arg1", _p), ("arg2", _p), ("B", _i), ("S", _i), ("F", _i)]
+
+
+class CnnBwd(C.Structure):
+    _fields_ = [("d_out", _p), ("out", _p), ("images", _p), ("pool1", _p), ("pool2", _p), ("arg1", _p), ("arg2", _p),
+                ("k1", _p), ("k2", _p), ("k3", _p), ("workspace", _p),
+                ("d_k1", _p), ("d_b1", _p), ("d_k2", _p), ("d_b2", _p), ("d_k3", _p), ("d_b3", _p), ("d_images", _p),
+                ("B", _i), ("S", _i), ("F", _i)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -208,6 +221,9 @@ _SIGNATURES = {
                                       C.c_int64, _p]),
     "air_sigmoid_bwd": (C.c_int, [_p, _p, _p, C.c_int64, _p]),
     "air_reparam_bwd_plain": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, _p]),
+    "air_cnn_fwd": (C.c_int, [C.POINTER(CnnFwd), _p]),
+    "air_cnn_bwd": (C.c_int, [C.POINTER(CnnBwd), _p]),
+    "air_cnn_workspace_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
