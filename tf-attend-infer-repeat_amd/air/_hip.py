@@ -65,6 +65,7 @@ class Panel(C.Structure):
 
 
 MAX_PANELS = 16
+MAX_WGRAD_PROBLEMS = 16       # air_wgrad_grouped takes that many problems in one launch
 
 
 class Colsum(C.Structure):
@@ -266,3 +267,28 @@ def check(rc: int, what: str = ""):
         msg = lib().air_strerror(rc)
         raise AirHipError("%s failed with code %d: %s" % (what or "libair_hip call", rc,
                                                           msg.decode() if msg else "?"))
+
+
+# ---- host helpers of every module that calls the library ---------------------------------------------------------------
+def ptr(t):
+    """device pointer of a tensor; NULL for None"""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def stream(device):
+    """the current stream of `device`, as the hipStream_t every entry point takes last"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def launch(name, device, *args):
+    """one eager call of the entry point `name` on the current stream of `device`"""
+    check(getattr(lib(), name)(*args, stream(device)), name)
+
+
+def require_device(t, what, op, capture_too=False):
+    """AirHipError unless `t` is a device tensor; capture_too: also while the current stream is capturing (the op modules
+    that refuse to run under torch.cuda.graph: DESIGN.md section 18.5)"""
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise AirHipError("%s: %s must be a device tensor (no CPU fallback)" % (op, what))
+    if capture_too and torch.cuda.is_current_stream_capturing():
+        raise AirHipError("%s: not supported under stream capture (torch.cuda.graph); run it eagerly" % op)

@@ -29,6 +29,8 @@ import numpy as np
 import torch
 
 from . import _hip as H
+from ._hip import ptr as _ptr
+from ._layers import VaeLayers
 
 # "fp32": exact-fp32 MFMA (parity path); "bf16": bf16 operands, fp32 accumulate
 GEMM_PRECISION = os.environ.get("AIR_GEMM_PRECISION", "fp32")
@@ -48,10 +50,6 @@ TRAINING_BACKWARD = "reference"
 def reset_default_graph():
     """Drops all variable scopes (the tf.reset_default_graph() of this runtime)."""
     _SCOPES.clear()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def _align8(n):
@@ -84,7 +82,7 @@ class VariableStore:
         Hs, Hh, Hz = hp["scale_hidden_units"], hp["shift_hidden_units"], hp["z_pres_hidden_units"]
         HT, Hmax = 2 * Hs + 2 * Hh + Hz, max(Hs, Hh, Hz)
         self.dims = dict(D=D, d=d, R=R, Z=Z, Hs=Hs, Hh=Hh, Hz=Hz, HT=HT, Hmax=Hmax)
-        rec, gen = list(hp["vae_recognition_units"]), list(hp["vae_generative_units"])
+        self.vae_layers = VaeLayers(d, hp["vae_recognition_units"], Z, hp["vae_generative_units"])
 
         fused = OrderedDict()           # fused device tensors: name -> shape
         fused["lstm_kernel"] = (D + R, 4 * R)
@@ -93,20 +91,7 @@ class VariableStore:
         fused["bhid"] = (HT,)
         fused["wout"] = (7, Hmax)
         fused["bout"] = (8,)
-        prev = d
-        for i, u in enumerate(rec):
-            fused["rec%d_w" % i] = (prev, u)
-            fused["rec%d_b" % i] = (u,)
-            prev = u
-        fused["ml_w"] = (prev, 2 * Z)
-        fused["ml_b"] = (2 * Z,)
-        prev = Z
-        for i, u in enumerate(gen):
-            fused["gen%d_w" % i] = (prev, u)
-            fused["gen%d_b" % i] = (u,)
-            prev = u
-        fused["out_w"] = (prev, d)
-        fused["out_b"] = (d,)
+        fused.update(self.vae_layers.shapes())
 
         self.offsets = OrderedDict()
         off = 0
@@ -185,15 +170,7 @@ class VariableStore:
                 o[head + "/output/weights"] = V["wout"][r0:r1, :wid].t()
                 o[head + "/output/biases"] = V["bout"][r0:r1]
                 seg += wid
-            for i in range(len(rec)):
-                o["vae/recognition_%d/weights" % (i + 1)] = V["rec%d_w" % i]
-                o["vae/recognition_%d/biases" % (i + 1)] = V["rec%d_b" % i]
-            o["vae/rec_mean/weights"], o["vae/rec_mean/biases"] = V["ml_w"][:, :Z], V["ml_b"][:Z]
-            o["vae/rec_log_variance/weights"], o["vae/rec_log_variance/biases"] = V["ml_w"][:, Z:], V["ml_b"][Z:]
-            for i in range(len(gen)):
-                o["vae/generative_%d/weights" % (i + 1)] = V["gen%d_w" % i]
-                o["vae/generative_%d/biases" % (i + 1)] = V["gen%d_b" % i]
-            o["vae/gen_mean/weights"], o["vae/gen_mean/biases"] = V["out_w"], V["out_b"]
+            o.update(self.vae_layers.tf_views(V))
             return o
         self.variables = named(self.P)
         self.gradients = named(self.G)
@@ -216,7 +193,7 @@ class VariableStore:
 
     def refresh_shadow(self, stream=None):
         if stream is None:
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = H.stream(self.device)
         H.check(H.lib().air_bf16_twin(_ptr(self.params), _ptr(self.params16), self.n, stream), "air_bf16_twin")
         if len(self.panels):
             H.check(H.lib().air_panel_shadow(_ptr(self.params), _ptr(self.params16p), self.panels, len(self.panels), stream),
@@ -356,6 +333,11 @@ def check_step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld, li
                 "live in LDS) -- reduce canvas_size or max_steps" % (canvas_size, max_steps, windows_size, launch, nbytes, limit))
 
 
+# the weight-gradient problems AIRModel._build_wgrad appends beside the VAE's: Wh, whid, wout (head pack), Wx
+_NON_VAE_WGRAD_PROBLEMS = 4
+_NOISE_KEYS = ("eps_scale", "eps_shift", "eps_z", "eps_x", "u")
+
+
 def _carve_noise(normals, uniforms, N, B, Z, d):
     """(eps_scale [N,B,1], eps_shift [N,B,2], eps_z [N,B,Z], eps_x [N,B,d], u [N,B]): views of one normals / uniforms pair
     (one contiguous buffer each: one Philox launch fills them)"""
@@ -363,6 +345,18 @@ def _carve_noise(normals, uniforms, N, B, Z, d):
     assert normals.numel() == sum(sizes) and uniforms.numel() == N * B
     es, exy, ez, ex = torch.split(normals, sizes)
     return es.view(N, B, 1), exy.view(N, B, 2), ez.view(N, B, Z), ex.view(N, B, d), uniforms.view(N, B)
+
+
+def _row16(t, i):
+    """block i of a bf16 twin buffer (None when the twins are off)"""
+    return None if t is None else t[i]
+
+
+def _copy_noise(noise, dst):
+    """copies the five noise tensors of the dict `noise` (tensors or arrays) into the buffers dst(key)"""
+    for k in _NOISE_KEYS:
+        buf = dst(k)
+        buf.copy_(torch.as_tensor(np.asarray(noise[k]), dtype=torch.float32).reshape(buf.shape))
 
 
 class AIRModel:
@@ -392,8 +386,10 @@ class AIRModel:
         # known (check_step_lds)
         limits = (("max_steps", max_steps, 16, "the per-image records of the compose / attend kernels hold 16 steps"),
                   ("windows_size", windows_size, 32, "the sampler backward gives every glimpse pixel a thread of a 1024-thread workgroup"),
-                  ("len(vae_recognition_units) + len(vae_generative_units)", len(vae_recognition_units) + len(vae_generative_units), 10,
-                   "the grouped weight-gradient launch takes 16 problems"))
+                  # (the VAE's products beside its two fixed ones, ml and out: VaeLayers.products)
+                  ("len(vae_recognition_units) + len(vae_generative_units)", len(vae_recognition_units) + len(vae_generative_units),
+                   H.MAX_WGRAD_PROBLEMS - _NON_VAE_WGRAD_PROBLEMS - 2,
+                   "the grouped weight-gradient launch takes %d problems" % H.MAX_WGRAD_PROBLEMS))
         for name, val, cap, why in limits:
             if val > cap:
                 raise NotImplementedError("%s = %d exceeds the HIP path's limit of %d (%s)" % (name, val, cap, why))
@@ -530,12 +526,19 @@ class AIRModel:
         self._build_programs()
 
     # ------------------------------------------------------------------ buffers
+    def _f32(self, *shape):
+        return torch.zeros(*shape, dtype=torch.float32, device=self.input_images.device)
+
+    def _i16(self, *shape):
+        """a bf16 twin buffer (None when the twins are off)"""
+        return torch.zeros(*shape, dtype=torch.int16, device=self.input_images.device) if self._twins else None
+
     def _alloc(self):
         st, dv = self.store, self.input_images.device
         dm = st.dims
         B, N = self.batch_size, self.max_steps
         D, d, R, Z, HT = dm["D"], dm["d"], dm["R"], dm["Z"], dm["HT"]
-        f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dv)  # noqa: E731
+        f, h16 = self._f32, self._i16
 
         # dynamic scalars + annealing table (reference :76-82, 94-121)
         dyn = np.zeros(H.DYN_COUNT, np.float32)
@@ -624,8 +627,6 @@ class AIRModel:
         self._loss_item = f(B)
         self.scalars = self.store.grads[self.store.n:self.store.n + 4] if self.train else f(4)
 
-        tw = self._twins
-        h16 = lambda *s: (torch.zeros(*s, dtype=torch.int16, device=dv) if tw else None)  # noqa: E731
         self.h16 = h16(N + 1, B, R)                     # [0] stays zero like h[0]
         self.hid16 = h16(N, B, HT)
         self.window16 = h16(N, B, d)
@@ -672,12 +673,13 @@ class AIRModel:
               A16=None, B16=None, C16=None, q0_16=None, q2_16=None, B16p=None):
         p = list(p) + [None] * (4 - len(p))
         q = list(q) + [None] * (3 - len(q))
-        g = H.Gemm(_ptr(A), _ptr(Bm), _ptr(Cm), M, N, K, lda, ldb, ldc, ta, tb, _ptr(bias), _ptr(addend), ldadd,
-                   _ptr(aux), ldaux, aux_scale, act, actgrad, accumulate, self._prec,
-                   epi, tile[0], tile[1], ksplit, addend_slabs, i0,
-                   _ptr(p[0]), _ptr(p[1]), _ptr(p[2]), _ptr(p[3]), _ptr(q[0]), _ptr(q[1]), _ptr(q[2]),
-                   C.pointer(step_job) if step_job is not None else None,
-                   _ptr(A16), _ptr(B16), _ptr(C16), _ptr(q0_16), _ptr(q2_16), _ptr(B16p))
+        g = H.Gemm(A=_ptr(A), B=_ptr(Bm), C=_ptr(Cm), M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, transA=ta, transB=tb,
+                   bias=_ptr(bias), addend=_ptr(addend), ldadd=ldadd, aux=_ptr(aux), ldaux=ldaux, aux_scale=aux_scale,
+                   act=act, actgrad=actgrad, accumulate=accumulate, precision=self._prec,
+                   epi=epi, tile_m=tile[0], tile_n=tile[1], ksplit=ksplit, addend_slabs=addend_slabs, i0=i0,
+                   p0=_ptr(p[0]), p1=_ptr(p[1]), p2=_ptr(p[2]), p3=_ptr(p[3]), q0=_ptr(q[0]), q1=_ptr(q[1]), q2=_ptr(q[2]),
+                   step_job=C.pointer(step_job) if step_job is not None else None,
+                   A16=_ptr(A16), B16=_ptr(B16), C16=_ptr(C16), q0_16=_ptr(q0_16), q2_16=_ptr(q2_16), B16p=_ptr(B16p))
         fn = self.lib.air_gemm
         kbuf = C.create_string_buffer(96)
         H.check(self.lib.air_gemm_kernel_name(C.byref(g), kbuf, 96), "air_gemm_kernel_name")
@@ -708,45 +710,62 @@ class AIRModel:
         return _Op(tag or name, lambda s, fn=fn, args=args, name=name: H.check(fn(*args, s), name),
                    nbytes=nbytes, flops=flops, kernel=kernel)
 
-    def _generative_ops(self, x, x16, k, act, act16, out, eps_x, aux_scale, first=0):
-        """The generative layers from index `first` on and gen_mean (vae.py:26-41), reading x [N*B, k] (twin x16): softplus
-        layers into act[i] / act16[i], then sigmoid(. + aux_scale * eps_x) into out.  The forward and the generation
-        lists are built from this one set of descriptors."""
-        st, P, tw = self.store, self.store.P, self._twins
-        T = (lambda name: st.P16[name]) if tw else (lambda name: None)  # noqa: E731
-        TP = (lambda name: st.panel(name)) if tw else (lambda name: None)  # noqa: E731
-        NB, d = self.max_steps * self.batch_size, st.dims["d"]
+    # bf16 twins of the weights (None when the twins are off): the activations carry their own twin buffers
+    def _T(self, name):
+        """the row-major bf16 shadow of a fused variable"""
+        return self.store.P16[name] if self._twins else None
+
+    def _TP(self, name):
+        """its panel-blocked twin (forward products only; None for a matrix the store built no panel of: row-major shadow)"""
+        return self.store.panel(name) if self._twins else None
+
+    def _lstm_weights(self):
+        """(Wx, Wh, Wx16, Wh16): the input and the recurrent rows of the LSTM kernel and of its row-major bf16 shadow"""
+        D, K = self.store.dims["D"], self.store.P["lstm_kernel"]
+        K16 = self._T("lstm_kernel")
+        return (K[:D], K[D:]) + ((K16[:D], K16[D:]) if K16 is not None else (None, None))
+
+    def _generative_ops(self, x, x16, act, act16, out, eps_x, aux_scale, first=0):
+        """The generative layers from index `first` on and gen_mean (vae.py:26-41), reading x (twin x16), the input of layer
+        `first`: softplus layers into act[i] / act16[i], then sigmoid(. + aux_scale * eps_x) into out.  The forward and the
+        generation lists are built from this one set of descriptors."""
+        P, T, TP, L = self.store.P, self._T, self._TP, self.store.vae_layers
+        NB = self.max_steps * self.batch_size
         ops = []
-        for i in range(first, len(self.vae_generative_units)):
-            u = self.vae_generative_units[i]
-            ops.append(self._gemm(x, P["gen%d_w" % i], act[i], NB, u, k, k, u, u,
-                                  bias=P["gen%d_b" % i], act=H.ACT_SOFTPLUS, tag="vae_gen",
-                                  A16=x16, B16=T("gen%d_w" % i), C16=act16[i], B16p=TP("gen%d_w" % i)))
-            x, x16, k = act[i], act16[i], u
-        ops.append(self._gemm(x, P["out_w"], out, NB, d, k, k, d, d, bias=P["out_b"],
-                              act=H.ACT_SIGMOID_NOISE, aux=eps_x, ldaux=d, aux_scale=aux_scale, tag="vae_out",
-                              A16=x16, B16=T("out_w"), B16p=TP("out_w")))
+        for i in range(first, len(L.gen)):
+            l = L.gen[i]
+            ops.append(self._gemm(x, P[l.w], act[i], NB, l.N, l.K, l.K, l.N, l.N,
+                                  bias=P[l.b], act=H.ACT_SOFTPLUS, tag="vae_gen",
+                                  A16=x16, B16=T(l.w), C16=act16[i], B16p=TP(l.w)))
+            x, x16 = act[i], act16[i]
+        l = L.out
+        ops.append(self._gemm(x, P[l.w], out, NB, l.N, l.K, l.K, l.N, l.N, bias=P[l.b],
+                              act=H.ACT_SIGMOID_NOISE, aux=eps_x, ldaux=l.N, aux_scale=aux_scale, tag="vae_out",
+                              A16=x16, B16=T(l.w), B16p=TP(l.w)))
         return ops
 
     def _build_programs(self):
-        st, P, G = self.store, self.store.P, self.store.G
+        self._keep = []                 # ctypes structs referenced by the closures
+        self._build_forward()
+        if not self.train:
+            self._bwd, self._opt, self._wgrad_plain = [], [], None
+            return
+        self._build_wgrad()
+        self._build_backward()
+        self._opt = None
+        self._opt_world = None
+
+    def _build_forward(self):
+        st, P, L = self.store, self.store.P, self.store.vae_layers
         dm = st.dims
         B, N = self.batch_size, self.max_steps
         D, d, R, Z, HT = dm["D"], dm["d"], dm["R"], dm["Z"], dm["HT"]
         Hs, Hh, Hz, Hmax = dm["Hs"], dm["Hh"], dm["Hz"], dm["Hmax"]
         Cc, w = self.canvas_size, self.windows_size
-        rec_u, gen_u = list(self.vae_recognition_units), list(self.vae_generative_units)
-        Wx, Wh = P["lstm_kernel"][:D], P["lstm_kernel"][D:]
-        # bf16 twins (None when off): T(name) = shadow of a fused variable; activations carry their own twin buffers
-        tw = self._twins
-        P16 = st.P16
-        T = (lambda k: P16[k]) if tw else (lambda k: None)  # noqa: E731
-        # panel-blocked twins (forward products only; None for a matrix the store built no panel of: row-major shadow)
-        TP = (lambda k: st.panel(k)) if tw else (lambda k: None)  # noqa: E731
-        Wx16, Wh16 = (P16["lstm_kernel"][:D], P16["lstm_kernel"][D:]) if tw else (None, None)
-        o16 = lambda t, i=None: (None if t is None else (t if i is None else t[i]))  # noqa: E731
+        tw, T, TP = self._twins, self._T, self._TP
+        Wx, Wh, Wx16, Wh16 = self._lstm_weights()
         imgs = self.input_images
-        keep = self._keep = []          # ctypes structs referenced by the closures
+        keep = self._keep
 
         NB = N * B
         fwd = []
@@ -768,13 +787,13 @@ class AIRModel:
             import warnings
             warnings.warn("AIRModel(scope=%r): bf16 twins are on but x.Wx reads the fp32 Wx (the scope's store maintains only the "
                           "panel twin of Wx; this model does not fuse the first step: xw_tile or step0_fusion=False given?)"
-                          % self.scope, RuntimeWarning, stacklevel=3)
+                          % self.scope, RuntimeWarning, stacklevel=4)
         if self._fuse_step0:
             # the first step rides in the x.Wx launch: h_0 = c_0 = 0 (zero_state, :540), so its gates are x.Wx + b
             # (twins: the panel twin of Wx is the ONLY bf16 form of Wx that is maintained when the store made it exclusive)
             wx_pan = TP("Wx")
             step0 = dict(bias=P["lstm_bias"], epi=H.EPI_LSTM_FWD0, q=(self.acts[0], self.c[1], self.h[1]),
-                         extra_bytes=4 * B * R * 6, q2_16=o16(self.h16, 1), B16p=wx_pan,
+                         extra_bytes=4 * B * R * 6, q2_16=_row16(self.h16, 1), B16p=wx_pan,
                          B16=(Wx16 if (wx_pan is None and not st.wx_exclusive) else None))
             # (panel twin + train: the launch also leaves the padded bf16 twin of the batch behind -- air_gemm_t.C16 of this
             # epilogue -- and a second op reads it in place of the fp32 batch: capture_graph decides where that is allowed)
@@ -803,7 +822,7 @@ class AIRModel:
                                               extra_bytes=noise_bytes, B16=Wx16))
             # step 0 starts from zero_state (:540): h_0 . Wh = 0, the gates are x.Wx + b -- a pointwise launch
             fwd.append(self._call("air_lstm_first_step", _ptr(self.xw), self._xw_slabs, _ptr(P["lstm_bias"]),
-                                  _ptr(self.acts[0]), _ptr(self.c[1]), _ptr(self.h[1]), _ptr(o16(self.h16, 1)), B, R,
+                                  _ptr(self.acts[0]), _ptr(self.c[1]), _ptr(self.h[1]), _ptr(_row16(self.h16, 1)), B, R,
                                   nbytes=4 * B * R * (4 * self._xw_slabs + 6) + 16 * R, tag="lstm_fwd0"))
         # the recurrence: the remaining LSTM steps, chained (the only sequential part of the loop -- the LSTM
         # sees the same image every step and nothing downstream feeds back into it, :286/:535)
@@ -811,7 +830,7 @@ class AIRModel:
             lstm_kw = dict(bias=P["lstm_bias"], addend=self.xw, ldadd=4 * R, addend_slabs=self._xw_slabs,
                            epi=H.EPI_LSTM_FWD, p=(self.c[t],), q=(self.acts[t], self.c[t + 1], self.h[t + 1]),
                            extra_bytes=4 * B * R * 7, tag="lstm_fwd",
-                           A16=o16(self.h16, t), B16=Wh16, q2_16=o16(self.h16, t + 1), B16p=TP("Wh"))
+                           A16=_row16(self.h16, t), B16=Wh16, q2_16=_row16(self.h16, t + 1), B16p=TP("Wh"))
             gemm(self.h[t], Wh, self.gates_pre, B, 4 * R, R, R, 4 * R, 4 * R, **lstm_kw)
             if t == 1 and self._fuse_step0 and tw:
                 # With the first step fused into it, x.Wx is ONE round of 160 KB of LDS per workgroup: prologue workgroups in
@@ -822,45 +841,46 @@ class AIRModel:
                                                              step_job=job, **lstm_kw))
         # everything else runs ONCE over all N*B (step, image) rows
         gemm(self.h[1], P["whid"], self.hid, NB, HT, R, R, HT, HT, bias=P["bhid"],
-             act=H.ACT_RELU, tag="heads_hid", A16=o16(self.h16, 1), B16=T("whid"), C16=self.hid16, B16p=TP("whid"))
+             act=H.ACT_RELU, tag="heads_hid", A16=_row16(self.h16, 1), B16=T("whid"), C16=self.hid16, B16p=TP("whid"))
         a = H.AttendFwd(_ptr(self.hid), _ptr(P["wout"]), _ptr(P["bout"]), _ptr(imgs),
                         _ptr(self.eps_scale), _ptr(self.eps_shift), _ptr(self.u), _ptr(self.dyn),
                         _ptr(self.out7), _ptr(self.att), _ptr(self.window),
                         B, N, Cc, w, Hs, Hh, Hz, Hmax, 1 if self.train else 0, _ptr(self.window16))
         keep.append(a)
         fwd.append(self._call("air_attend_fwd", C.byref(a), nbytes=NB * ((D + d + HT) * 4 + 12), tag="attend_fwd"))
-        x, x16, k = self.window, self.window16, d
-        for i, u in enumerate(rec_u):
-            gemm(x, P["rec%d_w" % i], self.rec_act[i], NB, u, k, k, u, u,
-                 bias=P["rec%d_b" % i], act=H.ACT_SOFTPLUS, tag="vae_rec",
-                 A16=x16, B16=T("rec%d_w" % i), C16=self.rec_act16[i], B16p=TP("rec%d_w" % i))
-            x, x16, k = self.rec_act[i], self.rec_act16[i], u
+        x, x16 = self.window, self.window16
+        for i, l in enumerate(L.rec):
+            gemm(x, P[l.w], self.rec_act[i], NB, l.N, l.K, l.K, l.N, l.N,
+                 bias=P[l.b], act=H.ACT_SOFTPLUS, tag="vae_rec",
+                 A16=x16, B16=T(l.w), C16=self.rec_act16[i], B16p=TP(l.w))
+            x, x16 = self.rec_act[i], self.rec_act16[i]
         # the bottleneck (last recognition product -> reparameterised sample -> first generative layer) is
         # ONE launch where the fused kernel's limits hold (bf16 operands; vae.py:16-30); else two GEMMs
         # bf16 path: on.  fp32 path (the parity precision): OFF -- its exact-fp32 form is 3e-6 from the two launches (another
         # fp32 order of a K = 256 sum) and saves 7 us, but over 32 seeds x 60 k iterations 4 runs never separate one count
         # class with it against 0 of 32 with two launches (profiles/r04_seed_sweep_fp32_bottleneck_*, r05_sweep_fp32_bottleneck_*).
         # (the library keeps the exact-fp32 form of the two kernels, air_bottleneck_*_t.exact_fp32 = 1: the model does not use it)
-        fuse = self._prec == 1
-        fuse_f = fuse and len(gen_u) >= 1 and k == 256 and Z <= 64 and Z % 2 == 0 and gen_u[0] % 4 == 0
+        ml = L.ml
+        fuse_f = self._prec == 1 and len(L.gen) >= 1 and ml.K == 256 and Z <= 64 and Z % 2 == 0 and L.gen[0].N % 4 == 0
         self._zs_fused = fuse_f
         if fuse_f:
+            g0 = L.gen[0]
             self.zs = self._zs_pad[:, :, :Z]                 # (the sample lives in the padded rows)
-            bf = H.BottleneckFwd(_ptr(x), _ptr(P["ml_w"]), _ptr(P["ml_b"]), _ptr(self.eps_z), _ptr(P["gen0_w"]),
-                                 _ptr(P["gen0_b"]), _ptr(self.ml), _ptr(self._zs_pad), _ptr(self.gen_act[0]), NB, k, Z, gen_u[0], k,
-                                 _ptr(self._zs16_pad), _ptr(self.gen_act16[0]), _ptr(x16), _ptr(T("ml_w")), _ptr(T("gen0_w")),
+            bf = H.BottleneckFwd(_ptr(x), _ptr(P[ml.w]), _ptr(P[ml.b]), _ptr(self.eps_z), _ptr(P[g0.w]),
+                                 _ptr(P[g0.b]), _ptr(self.ml), _ptr(self._zs_pad), _ptr(self.gen_act[0]), NB, ml.K, Z, g0.N, ml.K,
+                                 _ptr(self._zs16_pad), _ptr(self.gen_act16[0]), _ptr(x16), _ptr(T(ml.w)), _ptr(T(g0.w)),
                                  0, self._zs_ld)
             keep.append(bf)
             fwd.append(self._call("air_vae_bottleneck_fwd", C.byref(bf),
-                                  nbytes=4 * (NB * (k + 4 * Z + gen_u[0]) + k * 2 * Z + Z * gen_u[0]),
-                                  flops=2 * NB * (k * 2 * Z + Z * gen_u[0]), tag="vae_bottleneck"))
-            fwd += self._generative_ops(self.gen_act[0], self.gen_act16[0], gen_u[0], self.gen_act, self.gen_act16, self.vrec,
+                                  nbytes=4 * (NB * (ml.K + 4 * Z + g0.N) + ml.K * 2 * Z + Z * g0.N),
+                                  flops=2 * NB * (ml.K * 2 * Z + Z * g0.N), tag="vae_bottleneck"))
+            fwd += self._generative_ops(self.gen_act[0], self.gen_act16[0], self.gen_act, self.gen_act16, self.vrec,
                                         self.eps_x, float(self.vae_likelihood_std), first=1)
         else:
-            fwd.append(self._gemm(x, P["ml_w"], self.ml, NB, 2 * Z, k, k, 2 * Z, 2 * Z, bias=P["ml_b"],
+            fwd.append(self._gemm(x, P[ml.w], self.ml, NB, ml.N, ml.K, ml.K, ml.N, ml.N, bias=P[ml.b],
                                   epi=H.EPI_REPARAM_FWD, p=(self.eps_z,), q=(self.zs,),
                                   extra_bytes=8 * NB * Z, tag="ml_reparam", q0_16=self.zs16))
-            fwd += self._generative_ops(self.zs, self.zs16, Z, self.gen_act, self.gen_act16, self.vrec,
+            fwd += self._generative_ops(self.zs, self.zs16, self.gen_act, self.gen_act16, self.vrec,
                                         self.eps_x, float(self.vae_likelihood_std))
         # more (image, step) items than CUs: the graph-order write backward takes them longest first (one extra workgroup of
         # the compose launch sorts them; air_write_fwd_t.wb_order)
@@ -881,46 +901,77 @@ class AIRModel:
         self._begin_sched_only = self._call(
             "air_step_begin", _ptr(self.sched), self._nsched, _ptr(self.dyn), _ptr(st.istate),
             None, 0, None, 0, C.c_uint64(self._seed), *twin_job)
-        if not self.train:
-            self._bwd, self._opt, self._wgrad_plain = [], [], None
-            return
 
-        # ---- the weight-gradient problems: dW = A^T . dY for every variable; weights are shared across the time steps, so
-        # every dW contracts over all N*B rows, the LSTM input weights over sum_t dgates.  Order = tile numbering = order
-        # of the global-norm partials.
+    def _build_wgrad(self):
+        """The weight-gradient problems: dW = A^T . dY for every variable; weights are shared across the time steps, so
+        every dW contracts over all N*B rows, the LSTM input weights over sum_t dgates.  Order = tile numbering = order
+        of the global-norm partials."""
         # (Round 4 let the VAE tiles RIDE as trailing workgroups of dh_heads and the BPTT steps -- their operands exist once
         # the data gradient has reached the glimpse.  Bit-identical, and slower: 0.1912 vs 0.1762 ms per step, 0.86 vs 0.70
         # at 128 x 128 -- a launch lasts as long as its slowest workgroup, a K = 192 tile needs 5.5 us, the carriers 3-4 us.
         # Removed; DESIGN.md section 8.)
+        st, G, L = self.store, self.store.G, self.store.vae_layers
+        dm = st.dims
+        B, NB = self.batch_size, self.max_steps * self.batch_size
+        D, R, HT = dm["D"], dm["R"], dm["HT"]
         Gx, Gh = G["lstm_kernel"][:D], G["lstm_kernel"][D:]
         probs = []
 
         def wg(A, dY, dW, db, M, Nn, K, A16=None, dY16=None, lda=None):
-            probs.append(H.Wgrad(_ptr(A), _ptr(dY), _ptr(dW), _ptr(db), M, Nn, K, lda or M, Nn, Nn, 0, 0, 0, 0, _ptr(A16), _ptr(dY16)))
-        wg(self.h[0], self.dgates, Gh, None, R, 4 * R, NB, o16(self.h16, 0), self.dgates16)
-        wg(self.h[1], self.d_hid, G["whid"], G["bhid"], R, HT, NB, o16(self.h16, 1), self.d_hid16)
-        x, x16, k = self.window, self.window16, d
-        for i, u in enumerate(rec_u):
-            wg(x, self.d_rec[i], G["rec%d_w" % i], G["rec%d_b" % i], k, u, NB, x16, self.d_rec16[i])
-            x, x16, k = self.rec_act[i], self.rec_act16[i], u
-        wg(x, self.d_ml, G["ml_w"], G["ml_b"], k, 2 * Z, NB, x16, self.d_ml16)
-        x, x16, k = self.zs, self.zs16, Z
-        zl = None
-        if self._zs_fused:
-            x, x16, zl = self._zs_pad, self._zs16_pad, self._zs_ld
-        for i, u in enumerate(gen_u):
-            wg(x, self.d_gen[i], G["gen%d_w" % i], G["gen%d_b" % i], k, u, NB, x16, self.d_gen16[i], lda=(zl if i == 0 else None))
-            x, x16, k = self.gen_act[i], self.gen_act16[i], u
-        wg(x, self.d_genpre, G["out_w"], G["out_b"], k, d, NB, x16, self.d_genpre16)
-        probs.append(H.Wgrad(_ptr(self.d_out7), _ptr(self.hid), _ptr(G["wout"]), _ptr(G["bout"]),
-                             H.OUT_STRIDE, HT, NB, H.OUT_STRIDE, HT, Hmax, 1, Hs, Hh, Hz))
+            probs.append(H.Wgrad(A=_ptr(A), dY=_ptr(dY), dW=_ptr(dW), db=_ptr(db), M=M, N=Nn, K=K, lda=lda or M, ldb=Nn, ldc=Nn,
+                                 A16=_ptr(A16), dY16=_ptr(dY16)))
+        wg(self.h[0], self.dgates, Gh, None, R, 4 * R, NB, _row16(self.h16, 0), self.dgates16)
+        wg(self.h[1], self.d_hid, G["whid"], G["bhid"], R, HT, NB, _row16(self.h16, 1), self.d_hid16)
+        # the VAE's products in layer order: the input of each (the fused bottleneck leaves z in padded rows) and the
+        # gradient of its pre-activation
+        z, z16, zl = (self._zs_pad, self._zs16_pad, self._zs_ld) if self._zs_fused else (self.zs, self.zs16, None)
+        xs = [(self.window, self.window16)] + list(zip(self.rec_act, self.rec_act16)) + \
+             [(z, z16)] + list(zip(self.gen_act, self.gen_act16))
+        dys = list(zip(self.d_rec, self.d_rec16)) + [(self.d_ml, self.d_ml16)] + \
+              list(zip(self.d_gen, self.d_gen16)) + [(self.d_genpre, self.d_genpre16)]
+        for l, (x, x16), (dy, dy16) in zip(L.products(), xs, dys):
+            wg(x, dy, G[l.w], G[l.b], l.K, l.N, NB, x16, dy16, lda=(zl if l is L.decoder[0] else None))
+        probs.append(H.Wgrad(A=_ptr(self.d_out7), dY=_ptr(self.hid), dW=_ptr(G["wout"]), db=_ptr(G["bout"]),
+                             M=H.OUT_STRIDE, N=HT, K=NB, lda=H.OUT_STRIDE, ldb=HT, ldc=dm["Hmax"],
+                             head_pack=1, Hs=dm["Hs"], Hh=dm["Hh"], Hz=dm["Hz"]))
         # the input-weight gradient contracts over B rows only (sum_t dgates): its many light
         # workgroups go LAST so that they fill the tail of the launch behind the K = N*B ones
-        wg(imgs, self.dgsum, Gx, G["lstm_bias"], D, 4 * R, B, self.images16, self.dgsum16)
-        assert len(probs) <= 16                              # (constructor: at most 10 VAE layers)
+        wg(self.input_images, self.dgsum, Gx, G["lstm_bias"], D, 4 * R, B, self.images16, self.dgsum16)
+        assert len(probs) == _NON_VAE_WGRAD_PROBLEMS + len(L.products()) <= H.MAX_WGRAD_PROBLEMS      # (constructor: the limit)
         arr = (H.Wgrad * len(probs))(*probs)
-        keep.append(arr)
+        self._keep.append(arr)
         self._wgrad_arr = arr
+
+        # weight + bias grads of all variables: ONE grouped launch (weights are shared across the
+        # time steps, so every dW contracts over all N*B rows; the LSTM input weights over sum_t dgates)
+        wbytes = sum(4 * q.M * q.N + (2 if (q.A16 and q.dY16) else 4) * q.K * (q.M + q.N) for q in probs)
+        wflops = sum(2 * q.M * q.N * q.K for q in probs)
+        self._wgrad_plain = self._call("air_wgrad_grouped", arr, len(probs), self._prec, None, None,
+                                       nbytes=wbytes, flops=wflops, tag="wgrad_grouped")
+        # single-GPU train step: the same launch also leaves the global-norm partial sums and counts
+        # the step, so no separate pass over the 16 MB gradient is needed before Adam
+        self._wgrad_blocks = self.lib.air_wgrad_num_blocks(arr, len(probs))
+        if self._wgrad_blocks <= 0:
+            H.check(self._wgrad_blocks, "air_wgrad_num_blocks")
+        if st.partials.numel() < self._wgrad_blocks:
+            raise NotImplementedError("weight-gradient launch of %d workgroups exceeds the partial-sum buffer" % self._wgrad_blocks)
+        # (Adam rebuilding dWx = X^T.(sum_t dgates) from its factors instead of reading the stored 10 MB -- bit-identical, the
+        # tiles rebuilt inside Adam cost ~7 us against ~1 us saved in this launch -- was an option until round 5: removed)
+        self._wgrad_fused = self._call("air_wgrad_grouped", arr, len(probs), self._prec, _ptr(st.partials),
+                                       _ptr(st.istate), nbytes=wbytes, flops=wflops, tag="wgrad_grouped")
+        self._sqnorm = self._call("air_grad_sqnorm", _ptr(st.grads), st.n, _ptr(st.partials), _ptr(st.istate),
+                                  nbytes=4 * st.n, tag="grad_sqnorm")
+
+    def _build_backward(self):
+        st, P, L = self.store, self.store.P, self.store.vae_layers
+        dm = st.dims
+        B, N = self.batch_size, self.max_steps
+        D, d, R, Z, HT = dm["D"], dm["d"], dm["R"], dm["Z"], dm["HT"]
+        Hs, Hh, Hz, Hmax = dm["Hs"], dm["Hh"], dm["Hz"], dm["Hmax"]
+        Cc, w = self.canvas_size, self.windows_size
+        T = self._T
+        _, Wh, _, Wh16 = self._lstm_weights()
+        imgs, keep, NB = self.input_images, self._keep, N * B
 
         bwd = []
         lit = self._literal
@@ -938,41 +989,42 @@ class AIRModel:
         bwd.append(self._call("air_write_bwd", C.byref(wb), nbytes=NB * ((D + d) * 4 + 16 + 12), tag="write_bwd"))
         self._write_bwd_fin = self._call("air_write_bwd", C.byref(wbf), nbytes=NB * ((D + d) * 4 + 16 + 12), tag="write_bwd")
         bwd[-1].kernel = self._write_bwd_fin.kernel = kbuf.value.decode()
-        # decoder data-grads over all N*B rows: dX = dY . W^T, times softplus'(saved activation)
-        dy, dy16, n_out, wname = self.d_genpre, self.d_genpre16, d, "out_w"
-        for i in reversed(range(len(gen_u))):
-            u = gen_u[i]
-            bwd.append(self._gemm(dy, P[wname], self.d_gen[i], NB, u, n_out, n_out, n_out, u, tb=1,
-                                  aux=self.gen_act[i], ldaux=u, actgrad=H.GRAD_SOFTPLUS, tag="dgrad_gen",
-                                  A16=dy16, B16=T(wname), C16=self.d_gen16[i]))
-            dy, dy16, n_out, wname = self.d_gen[i], self.d_gen16[i], u, "gen%d_w" % i
-        fuse_b = fuse and len(gen_u) >= 1 and len(rec_u) >= 1 and gen_u[0] == 256 and Z <= 64 and Z % 2 == 0
-        last_rec = len(rec_u)
+
+        def dgrad(l, dy, dy16, out, out16, saved=None, tag="dgrad_win"):
+            """dX = dY . W^T of product l; times softplus'(saved activation X) where one is given"""
+            bwd.append(self._gemm(dy, P[l.w], out, NB, l.K, l.N, l.N, l.N, l.K, tb=1, aux=saved,
+                                  ldaux=l.K if saved is not None else 0,
+                                  actgrad=H.GRAD_SOFTPLUS if saved is not None else H.GRAD_NONE, tag=tag,
+                                  A16=dy16, B16=T(l.w), C16=out16))
+            return out, out16
+        # decoder data-grads over all N*B rows: decoder[i + 1] is the product that read the activation of gen[i]
+        dy, dy16 = self.d_genpre, self.d_genpre16
+        for i in reversed(range(len(L.gen))):
+            dy, dy16 = dgrad(L.decoder[i + 1], dy, dy16, self.d_gen[i], self.d_gen16[i], self.gen_act[i], "dgrad_gen")
+        fuse_b = self._prec == 1 and len(L.gen) >= 1 and len(L.rec) >= 1 and L.gen[0].N == 256 and Z <= 64 and Z % 2 == 0
+        last_rec = len(L.rec)
         if fuse_b:
             # d_gen[0] -> d_z -> (d_mean | d_lv) -> d_rec[last] in ONE launch (vae.py:22-24 and the KL, backwards)
-            bb = H.BottleneckBwd(_ptr(dy), _ptr(P["gen0_w"]), _ptr(self.ml), _ptr(self.eps_z), _ptr(self.att), _ptr(self.dyn),
-                                 _ptr(P["ml_w"]), _ptr(self.rec_act[-1]), _ptr(self.d_ml), _ptr(self.d_rec[-1]),
-                                 NB, rec_u[-1], Z, gen_u[0], _ptr(self.d_ml16), _ptr(self.d_rec16[-1]),
-                                 _ptr(dy16), _ptr(T("gen0_w")), _ptr(T("ml_w")), 0)
+            g0, ml = L.gen[0], L.ml
+            bb = H.BottleneckBwd(_ptr(dy), _ptr(P[g0.w]), _ptr(self.ml), _ptr(self.eps_z), _ptr(self.att), _ptr(self.dyn),
+                                 _ptr(P[ml.w]), _ptr(self.rec_act[-1]), _ptr(self.d_ml), _ptr(self.d_rec[-1]),
+                                 NB, ml.K, Z, g0.N, _ptr(self.d_ml16), _ptr(self.d_rec16[-1]),
+                                 _ptr(dy16), _ptr(T(g0.w)), _ptr(T(ml.w)), 0)
             keep.append(bb)
             bwd.append(self._call("air_vae_bottleneck_bwd", C.byref(bb),
-                                  nbytes=4 * (NB * (gen_u[0] + 5 * Z + 2 * rec_u[-1]) + Z * gen_u[0] + rec_u[-1] * 2 * Z),
-                                  flops=2 * NB * (gen_u[0] * Z + 2 * Z * rec_u[-1]), tag="vae_bottleneck_bwd"))
-            dy, dy16, n_out, wname, last_rec = (self.d_rec[-1], self.d_rec16[-1], rec_u[-1], "rec%d_w" % (len(rec_u) - 1),
-                                                len(rec_u) - 1)
+                                  nbytes=4 * (NB * (g0.N + 5 * Z + 2 * ml.K) + Z * g0.N + ml.K * 2 * Z),
+                                  flops=2 * NB * (g0.N * Z + 2 * Z * ml.K), tag="vae_bottleneck_bwd"))
+            dy, dy16, last_rec = self.d_rec[-1], self.d_rec16[-1], len(L.rec) - 1
         else:
-            bwd.append(self._gemm(dy, P[wname], self.d_ml, NB, Z, n_out, n_out, n_out, 2 * Z, tb=1,
+            l = L.decoder[0]
+            bwd.append(self._gemm(dy, P[l.w], self.d_ml, NB, l.K, l.N, l.N, l.N, 2 * Z, tb=1,
                                   epi=H.EPI_REPARAM_BWD, p=(self.ml, self.eps_z, self.att, self.dyn),
                                   extra_bytes=16 * NB * Z, tag="dz_reparam", C16=self.d_ml16))
-            dy, dy16, n_out, wname = self.d_ml, self.d_ml16, 2 * Z, "ml_w"
+            dy, dy16 = self.d_ml, self.d_ml16
+        # ... and the encoder's: encoder[i + 1] is the product that read the activation of rec[i]
         for i in reversed(range(last_rec)):
-            u = rec_u[i]
-            bwd.append(self._gemm(dy, P[wname], self.d_rec[i], NB, u, n_out, n_out, n_out, u, tb=1,
-                                  aux=self.rec_act[i], ldaux=u, actgrad=H.GRAD_SOFTPLUS, tag="dgrad_rec",
-                                  A16=dy16, B16=T(wname), C16=self.d_rec16[i]))
-            dy, dy16, n_out, wname = self.d_rec[i], self.d_rec16[i], u, "rec%d_w" % i
-        bwd.append(self._gemm(dy, P[wname], self.d_window, NB, d, n_out, n_out, n_out, d, tb=1, tag="dgrad_win",
-                              A16=dy16, B16=T(wname)))
+            dy, dy16 = dgrad(L.encoder[i + 1], dy, dy16, self.d_rec[i], self.d_rec16[i], self.rec_act[i], "dgrad_rec")
+        dgrad(L.encoder[0], dy, dy16, self.d_window, None)
         ab = H.AttendBwd(_ptr(self.hid), _ptr(P["wout"]), _ptr(imgs), _ptr(self.eps_scale),
                          _ptr(self.eps_shift), _ptr(self.dyn), _ptr(self.out7), _ptr(self.att),
                          _ptr(self.d_window), _ptr(self.d_sxyw), _ptr(self.d_hid), _ptr(self.d_out7),
@@ -987,7 +1039,7 @@ class AIRModel:
                               p=(self.acts[tl], self.c[tl], self.c[tl + 1]),
                               q=(self.dgates[tl], self.dc[tl % 2], self.dgsum),
                               extra_bytes=4 * B * R * 15, tag="dh_heads", A16=self.d_hid16, B16=T("whid"),
-                              q0_16=o16(self.dgates16, tl), q2_16=(self.dgsum16 if N == 1 else None)))
+                              q0_16=_row16(self.dgates16, tl), q2_16=(self.dgsum16 if N == 1 else None)))
         # back-propagation through time: the only sequential part of the backward
         for t in reversed(range(N - 1)):
             # d h'[t] = heads[t] + dgates[t+1] . Wh^T, LSTM pointwise backward fused in the epilogue
@@ -996,43 +1048,18 @@ class AIRModel:
                                   p=(self.acts[t], self.c[t], self.c[t + 1], self.dc[(t + 1) % 2]),
                                   q=(self.dgates[t], self.dc[t % 2], self.dgsum), i0=1,
                                   extra_bytes=4 * B * R * 15, tag="bptt_lstm_bwd",
-                                  A16=o16(self.dgates16, t + 1), B16=Wh16, q0_16=o16(self.dgates16, t),
+                                  A16=_row16(self.dgates16, t + 1), B16=Wh16, q0_16=_row16(self.dgates16, t),
                                   q2_16=(self.dgsum16 if t == 0 else None)))
         self._bwd = bwd
 
-        # weight + bias grads of all variables: ONE grouped launch (weights are shared across the
-        # time steps, so every dW contracts over all N*B rows; the LSTM input weights over sum_t dgates)
-        arr, probs = self._wgrad_arr, list(self._wgrad_arr)
-        wbytes = sum(4 * q.M * q.N + (2 if (q.A16 and q.dY16) else 4) * q.K * (q.M + q.N) for q in probs)
-        wflops = sum(2 * q.M * q.N * q.K for q in probs)
-        self._wgrad_plain = self._call("air_wgrad_grouped", arr, len(probs), self._prec, None, None,
-                                       nbytes=wbytes, flops=wflops, tag="wgrad_grouped")
-        # single-GPU train step: the same launch also leaves the global-norm partial sums and counts
-        # the step, so no separate pass over the 16 MB gradient is needed before Adam
-        self._wgrad_blocks = self.lib.air_wgrad_num_blocks(arr, len(probs))
-        if self._wgrad_blocks <= 0:
-            H.check(self._wgrad_blocks, "air_wgrad_num_blocks")
-        if st.partials.numel() < self._wgrad_blocks:
-            raise NotImplementedError("weight-gradient launch of %d workgroups exceeds the partial-sum buffer" % self._wgrad_blocks)
-        # (Adam rebuilding dWx = X^T.(sum_t dgates) from its factors instead of reading the stored 10 MB -- bit-identical, the
-        # tiles rebuilt inside Adam cost ~7 us against ~1 us saved in this launch -- was an option until round 5: removed)
-        self._wgrad_fused = self._call("air_wgrad_grouped", arr, len(probs), self._prec, _ptr(st.partials),
-                                       _ptr(st.istate), nbytes=wbytes, flops=wflops, tag="wgrad_grouped")
-
-        self._sqnorm = self._call("air_grad_sqnorm", _ptr(st.grads), st.n, _ptr(st.partials), _ptr(st.istate),
-                                  nbytes=4 * st.n, tag="grad_sqnorm")
-        self._opt = None
-        self._opt_world = None
-
     # ------------------------------------------------------------------ running
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.input_images.device).cuda_stream)
+        return H.stream(self.input_images.device)
 
     def set_noise(self, noise):
         """Inject the noise tensors of one pass (parity tests): dict with eps_scale
         [N,B,1], eps_shift [N,B,2], eps_z [N,B,Z], eps_x [N,B,d], u [N,B]."""
-        for k in ("eps_scale", "eps_shift", "eps_z", "eps_x", "u"):
-            getattr(self, k).copy_(torch.as_tensor(np.asarray(noise[k]), dtype=torch.float32).reshape(getattr(self, k).shape))
+        _copy_noise(noise, lambda k: getattr(self, k))
         self._injected_noise = True
         self._dirty = True
 
@@ -1210,7 +1237,8 @@ class AIRModel:
         x_all = torch.zeros(world * B, D, dtype=torch.float32, device=dv)
         dg_all = torch.zeros(world * B, 4 * R, dtype=torch.float32, device=dv)
         Gx = G["lstm_kernel"][:D]
-        fac = (H.Wgrad * 1)(H.Wgrad(_ptr(x_all), _ptr(dg_all), _ptr(Gx), None, D, 4 * R, world * B, D, 4 * R, 4 * R, 0, 0, 0, 0))
+        fac = (H.Wgrad * 1)(H.Wgrad(A=_ptr(x_all), dY=_ptr(dg_all), dW=_ptr(Gx), M=D, N=4 * R, K=world * B, lda=D, ldb=4 * R,
+                                    ldc=4 * R))
         cs = (H.Colsum * 1)(H.Colsum(_ptr(self.dgsum), _ptr(G["lstm_bias"]), B, 4 * R, 4 * R, 0))
         self._keep += [local, fac, cs]
         ops = dict(world=world, x_all=x_all, dg_all=dg_all, tail=st.grads[D * 4 * R:],
@@ -1435,8 +1463,7 @@ class AIRModel:
             dm, dv = self.store.dims, self.input_images.device
             B, N = self.batch_size, self.max_steps
             D, d, Z = dm["D"], dm["d"], dm["Z"]
-            f = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dv)  # noqa: E731
-            h16 = lambda *s: (torch.zeros(*s, dtype=torch.int16, device=dv) if self._twins else None)  # noqa: E731
+            f, h16 = self._f32, self._i16
             g = self._gen = dict(ops=None)
             g["normals"], g["uniforms"] = f(N * B * (1 + 2 + Z + d)), f(N * B)
             g["eps_scale"], g["eps_shift"], g["eps_z"], g["eps_x"], g["u"] = _carve_noise(g["normals"], g["uniforms"], N, B, Z, d)
@@ -1466,7 +1493,7 @@ class AIRModel:
             self._keep.append(r)
             ops[mode] = self._call("air_scene_records", C.byref(r), nbytes=NB * (4 * (4 + 2 * Z) + 64), tag="scene_records_" + mode)
         for name, sigma in (("out_noise", float(self.vae_likelihood_std)), ("out_mean", 0.0)):
-            dec = self._generative_ops(g["z"], g["z16"], Z, g["act"], g["act16"], g["vrec"], g["eps_x"], sigma)
+            dec = self._generative_ops(g["z"], g["z16"], g["act"], g["act16"], g["vrec"], g["eps_x"], sigma)
             ops["decoder"], ops[name] = dec[:-1], dec[-1]          # (the layers' descriptors do not depend on sigma)
         rd = H.Render(_ptr(g["vrec"]), _ptr(g["att"]), _ptr(g["canvas"]), _ptr(g["digits"]), B, N,
                       self.canvas_size, self.windows_size)
@@ -1507,8 +1534,7 @@ class AIRModel:
         """Injects eps_scale [N,B,1], eps_shift [N,B,2], eps_z [N,B,Z], eps_x [N,B,d], u [N,B] (the dict of set_noise) for
         ONE generate() / decode() call; the device RNG is back after it."""
         g = self._gen_state()
-        for k in ("eps_scale", "eps_shift", "eps_z", "eps_x", "u"):
-            g[k].copy_(torch.as_tensor(np.asarray(noise[k]), dtype=torch.float32).reshape(g[k].shape))
+        _copy_noise(noise, g.__getitem__)
         self._gen_injected = True
 
     def generate(self, likelihood_noise=False):

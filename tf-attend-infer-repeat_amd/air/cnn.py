@@ -26,16 +26,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _hip as H
+from ._layers import load_variables
 
 _SALT = 0x434E4E31            # keeps this module's initial values apart from others keyed by the same user seed
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def _check_sizes(canvas_size, filters):
@@ -67,10 +60,10 @@ class _CnnFn(torch.autograd.Function):
             pool2 = torch.empty(B, S2, S2, F, dtype=torch.float32, device=dev)
             arg1 = torch.empty(B, S1, S1, F, dtype=torch.uint8, device=dev)
             arg2 = torch.empty(B, S2, S2, F, dtype=torch.uint8, device=dev)
-        a = H.CnnFwd(_p(x), _p(P[0]), _p(P[1]), _p(P[2]), _p(P[3]), _p(P[4]), _p(P[5]), _p(out),
-                     _p(pool1), _p(pool2), _p(arg1), _p(arg2), B, S, F)
+        a = H.CnnFwd(H.ptr(x), H.ptr(P[0]), H.ptr(P[1]), H.ptr(P[2]), H.ptr(P[3]), H.ptr(P[4]), H.ptr(P[5]), H.ptr(out),
+                     H.ptr(pool1), H.ptr(pool2), H.ptr(arg1), H.ptr(arg2), B, S, F)
         with torch.cuda.device(dev):                 # the launch belongs to the input's device, whichever is current
-            H.check(H.lib().air_cnn_fwd(C.byref(a), _stream(dev)), "air_cnn_fwd")
+            H.launch("air_cnn_fwd", dev, C.byref(a))
         ctx.set_materialize_grads(False)
         # the input, the variables and the output through save_for_backward: an in-place change of any of them between
         # forward and backward is an error of autograd's, not a silently wrong gradient.  x and P are the same storage
@@ -92,14 +85,13 @@ class _CnnFn(torch.autograd.Function):
         dev = out.device
         B, S, F = int(x.shape[0]), mod.canvas_size, mod.filters
         d_out = d_out.contiguous().float()
-        lib = H.lib()
-        ws = torch.empty(int(lib.air_cnn_workspace_floats(B, S, F)), dtype=torch.float32, device=dev)
+        ws = torch.empty(int(H.lib().air_cnn_workspace_floats(B, S, F)), dtype=torch.float32, device=dev)
         grads = [torch.empty_like(q) for q in P]
         d_images = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        a = H.CnnBwd(_p(d_out), _p(out), _p(x), _p(pool1), _p(pool2), _p(arg1), _p(arg2), _p(P[0]), _p(P[2]), _p(P[4]),
-                     _p(ws), *[_p(g) for g in grads], _p(d_images), B, S, F)
+        a = H.CnnBwd(H.ptr(d_out), H.ptr(out), H.ptr(x), H.ptr(pool1), H.ptr(pool2), H.ptr(arg1), H.ptr(arg2),
+                     H.ptr(P[0]), H.ptr(P[2]), H.ptr(P[4]), H.ptr(ws), *[H.ptr(g) for g in grads], H.ptr(d_images), B, S, F)
         with torch.cuda.device(dev):
-            H.check(lib.air_cnn_bwd(C.byref(a), _stream(dev)), "air_cnn_bwd")
+            H.launch("air_cnn_bwd", dev, C.byref(a))
         if d_images is not None:
             d_images = d_images.view(ctx.in_shape).to(ctx.in_dtype)
         return (None, d_images) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
@@ -140,26 +132,10 @@ class CNN(torch.nn.Module):
     def load_variables(self, mapping, scope=""):
         """Copies every variable from mapping[scope + name] (tensors or arrays).  All of them must be there with the right
         number of elements: nothing is written otherwise."""
-        prefix = scope if (not scope or scope.endswith("/")) else scope + "/"
-        mine = self.variables()
-        src = {}
-        for name, v in mine.items():
-            if prefix + name not in mapping:
-                raise KeyError("missing variable %s" % (prefix + name))
-            t = mapping[prefix + name]
-            t = t.detach() if torch.is_tensor(t) else torch.as_tensor(np.array(t))
-            if t.numel() != v.numel():
-                raise ValueError("variable %s has %r elements, expected %r" % (prefix + name, tuple(t.shape), tuple(v.shape)))
-            src[name] = t
-        with torch.no_grad():
-            for name, v in mine.items():
-                v.copy_(src[name].to(device=v.device, dtype=v.dtype).reshape(v.shape))
+        load_variables(self.variables(), mapping, scope)
 
     def forward(self, input_images):
-        if not (torch.is_tensor(input_images) and input_images.is_cuda):
-            raise H.AirHipError("cnn: input_images must be a device tensor (no CPU fallback)")
-        if torch.cuda.is_current_stream_capturing():
-            raise H.AirHipError("cnn: not supported under stream capture (torch.cuda.graph); run it eagerly")
+        H.require_device(input_images, "input_images", "cnn", capture_too=True)
         S = self.canvas_size
         shp = tuple(int(d) for d in input_images.shape)
         if not (len(shp) >= 2 and shp[0] >= 1 and shp[1:] in ((S * S,), (S, S, 1))):
@@ -172,8 +148,7 @@ class CNN(torch.nn.Module):
 def cnn(input_images, canvas_size=50, cnn_filters=8, *, module=None):
     """air_model.py:510-533.  With `module` (a CNN) that module's variables are used -- the variable scope of the reference;
     without one a module with freshly initialised variables is built on the device of `input_images`."""
-    if not (torch.is_tensor(input_images) and input_images.is_cuda):
-        raise H.AirHipError("cnn: input_images must be a device tensor (no CPU fallback)")
+    H.require_device(input_images, "input_images", "cnn")
     if module is None:
         module = CNN(canvas_size, cnn_filters, device=input_images.device)
     return module(input_images)

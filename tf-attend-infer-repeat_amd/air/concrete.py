@@ -37,19 +37,8 @@ def manual_seed(seed):
     _state["seed"], _state["calls"] = int(seed), 0
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
 def _device_f32(t, what, op):
-    if not (torch.is_tensor(t) and t.is_cuda):
-        raise H.AirHipError("%s: %s must be a device tensor (no CPU fallback)" % (op, what))
-    if torch.cuda.is_current_stream_capturing():
-        raise H.AirHipError("%s: not supported under stream capture (torch.cuda.graph); run it eagerly" % op)
+    H.require_device(t, what, op, capture_too=True)
     return t.detach().contiguous().float()
 
 
@@ -84,8 +73,8 @@ def _uniforms(like, u, op):
             raise ValueError("%s: u has %d elements, log_odds %d" % (op, uu.numel(), like.numel()))
         return uu
     uu = torch.empty_like(like)
-    H.check(H.lib().air_philox_fill(None, 0, _p(uu), uu.numel(), C.c_uint64(_state["seed"] ^ _SALT),
-                                    C.c_uint64(_state["calls"]), _stream(like.device)), "air_philox_fill")
+    H.launch("air_philox_fill", like.device, None, 0, H.ptr(uu), uu.numel(), C.c_uint64(_state["seed"] ^ _SALT),
+             C.c_uint64(_state["calls"]))
     _state["calls"] += 1
     return uu
 
@@ -93,15 +82,14 @@ def _uniforms(like, u, op):
 # ---- the samples ----------------------------------------------------------------------------------------------------
 def _sample_fwd(lo, u, T, eps, hard):
     y, s = torch.empty_like(lo), torch.empty_like(lo)
-    H.check(H.lib().air_concrete_sample_fwd(_p(lo), _p(u), C.byref(T[0]), eps, 1 if hard else 0, _p(y), _p(s), lo.numel(),
-                                            _stream(lo.device)), "air_concrete_sample_fwd")
+    H.launch("air_concrete_sample_fwd", lo.device, H.ptr(lo), H.ptr(u), C.byref(T[0]), eps, 1 if hard else 0, H.ptr(y), H.ptr(s),
+             lo.numel())
     return y, s
 
 
 def _presigmoid_fwd(lo, u, T, eps):
     y = torch.empty_like(lo)
-    H.check(H.lib().air_concrete_presigmoid_fwd(_p(lo), _p(u), C.byref(T[0]), eps, _p(y), lo.numel(), _stream(lo.device)),
-            "air_concrete_presigmoid_fwd")
+    H.launch("air_concrete_presigmoid_fwd", lo.device, H.ptr(lo), H.ptr(u), C.byref(T[0]), eps, H.ptr(y), lo.numel())
     return y
 
 
@@ -123,8 +111,7 @@ class _SampleFn(torch.autograd.Function):
         gy = d_y.contiguous().float() if d_y is not None else None
         gs = d_s.contiguous().float() if d_s is not None else None
         d_lo = torch.empty_like(y)
-        H.check(H.lib().air_concrete_sample_bwd(_p(y), C.byref(T[0]), _p(gy), _p(gs), _p(d_lo), y.numel(), _stream(y.device)),
-                "air_concrete_sample_bwd")
+        H.launch("air_concrete_sample_bwd", y.device, H.ptr(y), C.byref(T[0]), H.ptr(gy), H.ptr(gs), H.ptr(d_lo), y.numel())
         return d_lo, None, None, None, None, None
 
 
@@ -138,8 +125,7 @@ class _PresigmoidFn(torch.autograd.Function):
     def backward(ctx, d_y):
         g = d_y.contiguous().float()
         d_lo = torch.empty_like(g)
-        H.check(H.lib().air_concrete_presigmoid_bwd(_p(g), C.byref(ctx.T[0]), _p(d_lo), g.numel(), _stream(g.device)),
-                "air_concrete_presigmoid_bwd")
+        H.launch("air_concrete_presigmoid_bwd", g.device, H.ptr(g), C.byref(ctx.T[0]), H.ptr(d_lo), g.numel())
         return d_lo, None, None, None, None
 
 
@@ -171,8 +157,8 @@ def concrete_binary_pre_sigmoid_sample(log_odds, temperature, eps=10e-10, *, u=N
 # ---- the one-sample KL ----------------------------------------------------------------------------------------------
 def _kl_fwd(y, plo, pT, qlo, qT, eps):
     kl = torch.empty_like(y)
-    H.check(H.lib().air_concrete_kl_fwd(_p(y), C.byref(plo[0]), C.byref(pT[0]), _p(qlo), C.byref(qT[0]), eps, _p(kl), y.numel(),
-                                        _stream(y.device)), "air_concrete_kl_fwd")
+    H.launch("air_concrete_kl_fwd", y.device, H.ptr(y), C.byref(plo[0]), C.byref(pT[0]), H.ptr(qlo), C.byref(qT[0]), eps, H.ptr(kl),
+             y.numel())
     return kl
 
 
@@ -191,8 +177,8 @@ class _KlFn(torch.autograd.Function):
         d_y = torch.empty_like(y) if need_y else None
         d_p = torch.empty_like(y) if need_p else None
         d_q = torch.empty_like(y) if need_q else None
-        H.check(H.lib().air_concrete_kl_bwd(_p(g), _p(y), C.byref(plo[0]), C.byref(pT[0]), _p(qlo), C.byref(qT[0]), eps,
-                                            _p(d_y), _p(d_q), _p(d_p), y.numel(), _stream(y.device)), "air_concrete_kl_bwd")
+        H.launch("air_concrete_kl_bwd", y.device, H.ptr(g), H.ptr(y), C.byref(plo[0]), C.byref(pT[0]), H.ptr(qlo), C.byref(qT[0]), eps,
+                 H.ptr(d_y), H.ptr(d_q), H.ptr(d_p), y.numel())
         sy, sp, sq = ctx.shapes
         return (d_y.view(sy) if need_y else None, d_p.view(sp) if need_p else None, d_q.view(sq) if need_q else None,
                 None, None, None, None, None, None)

@@ -8,19 +8,9 @@ Runs the hand-written HIP kernels; no CPU fallback.  One channel goes through ai
 air_transformer_nc_bwd, which sample image b for row b*T+t without copying it T times.
 When U or theta require a gradient the ops are differentiable the way the reference's are under tf.gradients (same op
 order, see include/air_hip.h); torch.autograd only carries the call."""
-import ctypes as C
-
 import torch
 
 from . import _hip as H
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def _nc_forward(U, theta, out_size, T):
@@ -30,8 +20,7 @@ def _nc_forward(U, theta, out_size, T):
     Uc = U.contiguous().float()
     th = theta.reshape(B * T, 6).contiguous().float()
     out = torch.empty(B * T, Ho, Wo, Ch, dtype=torch.float32, device=U.device)
-    H.check(H.lib().air_transformer_nc_fwd(_p(Uc), _p(th), _p(out), B, T, Hi, Wi, Ch, Ho, Wo, _stream(U.device)),
-            "air_transformer_nc_fwd")
+    H.launch("air_transformer_nc_fwd", U.device, H.ptr(Uc), H.ptr(th), H.ptr(out), B, T, Hi, Wi, Ch, Ho, Wo)
     return out
 
 
@@ -43,8 +32,7 @@ def _nc_grad(U, theta, out_size, d_out, T, need_dU, need_dtheta):
     g = d_out.reshape(B * T, Ho, Wo, Ch).contiguous().float()
     dU = torch.empty_like(Uc) if need_dU else None
     dth = torch.empty_like(th) if need_dtheta else None
-    H.check(H.lib().air_transformer_nc_bwd(_p(Uc), _p(th), _p(g), _p(dU), _p(dth), B, T, Hi, Wi, Ch, Ho, Wo,
-                                           _stream(U.device)), "air_transformer_nc_bwd")
+    H.launch("air_transformer_nc_bwd", U.device, H.ptr(Uc), H.ptr(th), H.ptr(g), H.ptr(dU), H.ptr(dth), B, T, Hi, Wi, Ch, Ho, Wo)
     return dU, dth
 
 
@@ -60,8 +48,7 @@ def transformer_grad(U, theta, out_size, d_out, need_dU=True, need_dtheta=True):
     g = d_out.reshape(B, Ho, Wo).contiguous().float()
     dU = torch.empty_like(Uc) if need_dU else None
     dth = torch.empty_like(th) if need_dtheta else None
-    H.check(H.lib().air_transformer_bwd(_p(Uc), _p(th), _p(g), _p(dU), _p(dth), B, Hi, Wi, Ho, Wo, _stream(U.device)),
-            "air_transformer_bwd")
+    H.launch("air_transformer_bwd", U.device, H.ptr(Uc), H.ptr(th), H.ptr(g), H.ptr(dU), H.ptr(dth), B, Hi, Wi, Ho, Wo)
     return dU, dth
 
 
@@ -106,8 +93,7 @@ class _BatchTransformerFn(torch.autograd.Function):
 def transformer(U, theta, out_size, name="SpatialTransformer", **kwargs):
     if torch.is_grad_enabled() and (U.requires_grad or theta.requires_grad):
         return _TransformerFn.apply(U, theta, tuple(out_size))
-    if not U.is_cuda:
-        raise H.AirHipError("transformer: U must be a device tensor (no CPU fallback)")
+    H.require_device(U, "U", "transformer")
     squeeze = U.dim() == 4
     if squeeze and U.shape[3] != 1:
         return _nc_forward(U, theta, out_size, 1)
@@ -116,9 +102,7 @@ def transformer(U, theta, out_size, name="SpatialTransformer", **kwargs):
     Uc = U.reshape(B, Hi, Wi).contiguous().float()
     th = theta.reshape(B, 6).contiguous().float()
     out = torch.empty(B, Ho, Wo, dtype=torch.float32, device=U.device)
-    s = C.c_void_p(torch.cuda.current_stream(U.device).cuda_stream)
-    H.check(H.lib().air_transformer_fwd(C.c_void_p(Uc.data_ptr()), C.c_void_p(th.data_ptr()),
-                                        C.c_void_p(out.data_ptr()), B, Hi, Wi, Ho, Wo, s), "air_transformer_fwd")
+    H.launch("air_transformer_fwd", U.device, H.ptr(Uc), H.ptr(th), H.ptr(out), B, Hi, Wi, Ho, Wo)
     return out.unsqueeze(3) if squeeze else out
 
 
@@ -127,7 +111,6 @@ def batch_transformer(U, thetas, out_size, name="BatchSpatialTransformer"):
     being input b under thetas[b,t] ([B*T,Ho,Wo] for a 3-D U)."""
     if torch.is_grad_enabled() and (U.requires_grad or thetas.requires_grad):
         return _BatchTransformerFn.apply(U, thetas, tuple(out_size))
-    if not U.is_cuda:
-        raise H.AirHipError("batch_transformer: U must be a device tensor (no CPU fallback)")
+    H.require_device(U, "U", "batch_transformer")
     out = _nc_forward(U.unsqueeze(3) if U.dim() == 3 else U, thetas, out_size, int(thetas.shape[1]))
     return out.squeeze(3) if U.dim() == 3 else out

@@ -279,7 +279,7 @@ class ShuffleBatchQueue:
         H.check(H.lib().air_shuffle_batch_init(C.byref(self._sq), self._s()), "air_shuffle_batch_init")
 
     def _s(self):
-        return self._C.c_void_p(self._torch.cuda.current_stream(self.images.device).cuda_stream)
+        return self._H.stream(self.images.device)
 
     def _gather(self, picks):
         H = self._H
