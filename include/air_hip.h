@@ -778,6 +778,61 @@ int air_cnn_bwd(const air_cnn_bwd_t* args, void* stream);
  * (B, S, F) the entry points refuse -- no GPU is touched */
 int64_t air_cnn_workspace_floats(int B, int S, int F);
 
+/* ---- histogram summaries (additive to ABI 6) --------------------------------------------------------------------------
+ * tf.summary.histogram of the reference's variables and gradients (air_model.py:642-687, written by training.py:144-218):
+ * TensorFlow 1.3's HistogramSummary (core/lib/histogram/histogram.cc) of up to AIR_HISTOGRAM_MAX strided views in ONE call.
+ *
+ * Buckets.  Positive limits: v = 1e-12; while (v < 1e20) { push v; v *= 1.1; } in double, then DBL_MAX.  All limits,
+ * ascending: the negated positive limits in reverse, 0.0, the positive limits -- air_histogram_num_buckets() of them
+ * (air_histogram_limits writes them; a host call, no GPU is touched).  A value x is cast to double and counted in bucket
+ * upper_bound(limits, x), the index of the first limit strictly greater than x: +-0.0 and positive denormals land in the
+ * bucket whose limit is 1e-12, |x| >= 9.92e19 in a DBL_MAX bucket.  The index is exact for every fp32 value.
+ *
+ * Values.  scale_kind 0: the element as stored; 1: x * prescale; 2: x * (prescale * s), s = clip * min(1 / gnorm, 1 / clip)
+ * with clip = dyn[AIR_DYN_CLIP_NORM] (s = 1 when clip <= 0) and gnorm = *gnorm read on the device -- the factor
+ * air_adam_clip_step applies to the gradient, ONE fp32 multiply per element.  A non-finite value (after the multiply) is
+ * counted in `nonfinite` and left out of every other field (TF fails the op instead; the host side raises).
+ *
+ * A descriptor is a 2-D view as it lies in memory: element (r, c) is base[r * ld + c], r < rows, c < cols <= ld.  The
+ * floats between cols and ld are never read into a result.  base: 4-byte aligned (AIR_EALIGN); 16-byte loads are used when
+ * base is 16-byte aligned and cols and ld are multiples of 4, scalar loads otherwise.  rows * cols < 2^32 (AIR_ELIMIT).
+ *
+ * Output: record h at (char*)out + h * air_histogram_record_bytes():
+ *   double min, max, num, sum, sum_squares, nonfinite;       (num == 0: min = +inf, max = -inf)
+ *   uint32_t count[air_histogram_num_buckets()];             dense, in limit order
+ *   uint32_t pad;                                            (0: keeps the next record 8-byte aligned)
+ * out and workspace: 8-byte aligned device buffers (AIR_EALIGN) of at least air_histograms_output_bytes /
+ * air_histograms_workspace_bytes bytes (out_bytes / workspace_bytes say what the caller allocated: AIR_EINVAL when short).
+ * The call initialises everything it reports: both buffers may hold garbage.  sum and sum_squares are fp64 sums in a fixed
+ * order and the counts integer sums: the same input gives the same bits.  Stream work (three kernels), no synchronisation,
+ * no device value is read by the host.
+ *
+ * AIR_EINVAL / AIR_ELIMIT, from all three descriptor-taking calls alike and before any HIP call: null descs, count < 1
+ * (EINVAL) or > AIR_HISTOGRAM_MAX (ELIMIT), a null base, rows or cols < 1, ld < cols, a scale_kind outside 0..2.
+ * air_histograms also: a null descriptor, out or workspace, and null dyn / gnorm when a descriptor has scale_kind 2. */
+#define AIR_HISTOGRAM_MAX 128
+typedef struct {
+    const float* base;                   /* DEVICE pointer */
+    int32_t rows, cols, ld, scale_kind;
+} air_histogram_desc_t;
+typedef struct {
+    const air_histogram_desc_t* descs;   /* HOST array [count], read during the call only */
+    int32_t count;
+    float prescale;                      /* scale_kind 1 and 2 */
+    const float* dyn;                    /* AIR_DYN_* device array (scale_kind 2) */
+    const float* gnorm;                  /* one device float: the global norm air_adam_clip_step wrote (scale_kind 2) */
+    void* out;
+    void* workspace;
+    int64_t out_bytes, workspace_bytes;
+} air_histograms_t;
+int air_histogram_num_buckets(void);
+int air_histogram_limits(double* out /* HOST, [air_histogram_num_buckets()] */);
+int air_histogram_chunk(void);           /* elements per work item: a view of n elements is ceil(n / chunk) work items */
+int64_t air_histogram_record_bytes(void);
+int64_t air_histograms_output_bytes(const air_histogram_desc_t* descs, int count);
+int64_t air_histograms_workspace_bytes(const air_histogram_desc_t* descs, int count);
+int air_histograms(const air_histograms_t* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,21 @@ class CnnBwd(C.Structure):
                 ("B", _i), ("S", _i), ("F", _i)]
 
 
+MAX_HISTOGRAMS = 128          # AIR_HISTOGRAM_MAX
+
+
+class HistogramDesc(C.Structure):
+    """air_histogram_desc_t: a 2-D view as it lies in memory, element (r, c) = base[r * ld + c]; scale_kind 0 stored value,
+    1 x * prescale, 2 x * (prescale * clip factor)"""
+    _fields_ = [("base", _p), ("rows", _i), ("cols", _i), ("ld", _i), ("scale_kind", _i)]
+
+
+class Histograms(C.Structure):
+    """air_histograms_t: `descs` is a HOST array; out / workspace are device buffers of out_bytes / workspace_bytes"""
+    _fields_ = [("descs", C.POINTER(HistogramDesc)), ("count", _i), ("prescale", _f), ("dyn", _p), ("gnorm", _p),
+                ("out", _p), ("workspace", _p), ("out_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -225,6 +240,13 @@ _SIGNATURES = {
     "air_cnn_fwd": (C.c_int, [C.POINTER(CnnFwd), _p]),
     "air_cnn_bwd": (C.c_int, [C.POINTER(CnnBwd), _p]),
     "air_cnn_workspace_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "air_histogram_num_buckets": (C.c_int, []),
+    "air_histogram_limits": (C.c_int, [C.POINTER(C.c_double)]),
+    "air_histogram_chunk": (C.c_int, []),
+    "air_histogram_record_bytes": (C.c_int64, []),
+    "air_histograms_output_bytes": (C.c_int64, [C.POINTER(HistogramDesc), C.c_int]),
+    "air_histograms_workspace_bytes": (C.c_int64, [C.POINTER(HistogramDesc), C.c_int]),
+    "air_histograms": (C.c_int, [C.POINTER(Histograms), _p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

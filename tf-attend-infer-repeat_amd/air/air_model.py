@@ -424,7 +424,9 @@ class AIRModel:
         self.scope = scope
         self.annealing_schedules = annealing_schedules
         self.rnn_input = self.input_images            # reference :535
-        self.num_summaries, self.img_summaries, self.var_summaries, self.grad_summaries = [], [], [], []
+        # (the reference's var_summaries / grad_summaries lists of summary ops are the methods of that name here)
+        self.num_summaries, self.img_summaries = [], []
+        self._hist_plans = {}
         prec = gemm_precision or GEMM_PRECISION
         if prec not in ("fp32", "bf16"):
             raise ValueError("gemm_precision must be 'fp32' or 'bf16'")
@@ -1630,6 +1632,73 @@ class AIRModel:
                         _ptr(self._loss_item), _ptr(self.scalars), _ptr(out), self.batch_size, self.max_steps, self.max_digits)
         H.check(self.lib.air_summaries(C.byref(a), self._stream()), "air_summaries")
         return out
+
+    # ---- histogram summaries (air_model.py:642-687): air_histograms over strided views of the flat buffers -----------
+    def _summary_tags(self):
+        from .summaries import summary_tags
+        return summary_tags(self.max_steps, self.max_digits, self.vae_recognition_units, self.vae_generative_units, self.scope)
+
+    def var_summary_names(self):
+        """Tags of var_summaries(), the reference's 36 at its shapes: "<scope>_1/summaries/<scope>/rnn/<variable>_0" in
+        tf.trainable_variables() order (the name scope of the variable-sharing test model, which training.py fetches
+        them from)."""
+        return self._summary_tags().variables
+
+    def grad_summary_names(self):
+        """Tags of the histograms of grad_summaries(): "<scope>/training/<scope>/rnn/<variable>_0_grad_original" for every
+        variable, then "..._grad_applied" (air_model.py:657-687).  air.summaries.gradient_summaries() adds the _norm / _avg
+        scalars the reference writes beside each."""
+        return self._summary_tags().gradients[::3]
+
+    def _histogram_plan(self, which):
+        """descriptors + workspace of one of the two launches, built once (the views never move)"""
+        if which not in self._hist_plans:
+            from .summaries import variable_order, view_2d
+            order = variable_order(len(self.vae_recognition_units), len(self.vae_generative_units))
+            views = self.store.variables if which == "var" else self.store.gradients
+            kinds = (0,) if which == "var" else (1, 2)
+            descs = []
+            for kind in kinds:
+                for name in order:
+                    v = views[name]
+                    rows, cols, ld = view_2d(v)
+                    descs.append(H.HistogramDesc(v.data_ptr(), rows, cols, ld, kind))
+            arr = (H.HistogramDesc * len(descs))(*descs)
+            nout = self.lib.air_histograms_output_bytes(arr, len(descs))
+            nws = self.lib.air_histograms_workspace_bytes(arr, len(descs))
+            if nout < 0 or nws < 0:
+                H.check(int(min(nout, nws)), "air_histograms_workspace_bytes")
+            ws = torch.empty(int(nws), dtype=torch.uint8, device=self.input_images.device)
+            self._hist_plans[which] = (arr, int(nout), ws)
+        return self._hist_plans[which]
+
+    def _histograms(self, which, out):
+        arr, nout, ws = self._histogram_plan(which)
+        if out is None:
+            out = torch.empty(nout, dtype=torch.uint8, device=self.input_images.device)
+        if out.numel() != nout or out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous uint8 device vector of %d bytes" % nout)
+        a = H.Histograms(arr, len(arr), 1.0 / self._world(), _ptr(self.dyn), _ptr(self.store.gnorm), _ptr(out), _ptr(ws),
+                         nout, ws.numel())
+        H.check(self.lib.air_histograms(C.byref(a), self._stream()), "air_histograms")
+        return out
+
+    def var_summaries(self, out=None):
+        """TensorFlow's histograms of the variables (tf.summary.histogram(v.name, v.value()), air_model.py:642-649), tags
+        var_summary_names(), as ONE call of air_histograms (include/air_hip.h) on the current stream over the strided views
+        of the flat variable buffer -- nothing is copied out variable by variable.  `out`: a uint8 device vector
+        (allocated when None) that air.summaries.decode_histograms() reads once fetched.  No host synchronisation."""
+        return self._histograms("var", out)
+
+    def grad_summaries(self, out=None):
+        """The histograms of the gradients, original and applied (air_model.py:657-687), tags grad_summary_names(), as ONE
+        call of air_histograms over the flat gradient buffer: original = g / world, applied = that times the
+        clip_by_global_norm factor air_adam_clip_step used, from the global norm it left on the device.  Describes the
+        gradient left by the LAST train step: after a captured replay of several steps that is the last step of the replay.
+        Train models only.  No host synchronisation."""
+        if not self.train:
+            raise H.AirHipError("grad_summaries: the model was built with train=False and has no gradients")
+        return self._histograms("grad", out)
 
     @property
     def rec_st_back(self):

@@ -6,7 +6,8 @@ layout (:41-61), the same constructor call (:100-122), train + test models shari
 shift_zero_digits_images ordering (:143-156, 169-200), checkpoints every 10 000 iterations
 (:203-207) and the same stdout line (:226).  TensorBoard summaries become JSONL scalars
 (summary/scalars.jsonl): loss, accuracy and the per-digit-count breakdown of
-AIRModel._summarize_by_digit_count (air_model.py:160-182, 614-617).
+AIRModel._summarize_by_digit_count (air_model.py:160-182, 614-617).  With --tensorboard the reference's four summary
+groups are also written to summary/events.out.tfevents.* (TensorBoardWriter; tf_events.py) at its cadences (:165-218).
 
 The whole dataset lives in HBM.  A batch comes out of tf.train.shuffle_batch's queue, kept on the
 device (multi_mnist.ShuffleBatchQueue; multi_mnist.py:240-249: capacity 10 000 + 10 * batch, min_after_dequeue
@@ -78,8 +79,8 @@ class SummaryWriter:
     launch into a device vector; the vector is copied into a pinned host ring without blocking and a row is written
     when the NEXT evaluation has been enqueued, so the host never waits for the step it has just launched."""
 
-    def __init__(self, model, path, t0, slots=2):
-        self.model, self.t0 = model, t0
+    def __init__(self, model, path, t0, slots=2, on_row=None):
+        self.model, self.t0, self.on_row = model, t0, on_row
         self.names = model.summary_names()
         self.dev = torch.empty(len(self.names), dtype=torch.float32, device=model.input_images.device)
         self.host = torch.empty(slots, len(self.names), dtype=torch.float32).pin_memory()
@@ -103,10 +104,96 @@ class SummaryWriter:
         row.update({k: (round(v, 5) if v == v else None) for k, v in zip(self.names, self.host[slot].tolist())})
         self.file.write(json.dumps(row) + "\n")
         self.file.flush()
+        if self.on_row is not None:
+            self.on_row(step, self.host[slot].tolist())
 
     def flush(self):
         while self.pending:
             self._drain_one()
+
+
+class TensorBoardWriter:
+    """--tensorboard: the reference's four summary groups (training.py:144-149) as a TensorBoard event file in summary/,
+    under its tags (air.summaries.summary_tags) and at its cadences and steps (:165-218):
+      numeric    every 50 iterations, the numbers SummaryWriter has fetched anyway (its on_row hook; loss and accuracy, which
+                 the reference does not summarise, are left out);
+      variables  every 250: test_model.var_summaries(), one air_histograms call;
+      image      every 500: the first num_summary_images reconstructions with their attention boxes (air/visualize.py);
+      gradients  every 100: train_model.grad_summaries() after the train step, under the global step AFTER that step
+                 (the `step` the reference fetches beside the train op, :212-218); with several steps per hipGraph replay
+                 it is taken after the replay that contains the step and describes -- and is written under -- the LAST
+                 step of that replay.
+    Nothing blocks: every group is one or a few launches into a device buffer, a non-blocking copy into a pinned host
+    buffer and an event; the bytes are decoded and written when a later fetch is enqueued (or at flush())."""
+
+    def __init__(self, logdir, train_model, test_model, depth=2):
+        import tf_events
+        from air.summaries import summary_tags
+        self.train_model, self.test_model, self.depth = train_model, test_model, depth
+        m = test_model
+        self.tags = summary_tags(m.max_steps, m.max_digits, m.vae_recognition_units, m.vae_generative_units, m.scope)
+        self.events = tf_events.EventFileWriter(logdir)
+        self.pending, self.slots, self.dev = [], {}, {}
+
+    def _fetch(self, kind, dev, done):
+        """`dev` -> a pinned host buffer of `kind` without blocking; done(host tensor) runs once the copy has landed"""
+        if kind not in self.slots:
+            self.slots[kind] = ([torch.empty(dev.shape, dtype=dev.dtype).pin_memory() for _ in range(self.depth)], [0])
+        hosts, k = self.slots[kind]
+        slot = k[0] % len(hosts)
+        k[0] += 1
+        while any(p[0] == (kind, slot) for p in self.pending):       # (the slot's previous fetch has to be written first)
+            self._drain_one()
+        hosts[slot].copy_(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pending.append(((kind, slot), ev, done, hosts[slot]))
+        while len(self.pending) > self.depth:
+            self._drain_one()
+
+    def _drain_one(self):
+        _, ev, done, host = self.pending.pop(0)
+        ev.synchronize()
+        done(host)
+
+    def numeric(self, step, values):
+        """SummaryWriter's row of `step` (AIRModel.summary_names() order: loss, accuracy, then the reference's scalars)"""
+        self.events.add_scalars(step, zip(self.tags.numeric, values[2:]))
+
+    def variables(self, step):
+        from air.summaries import decode_histograms
+        buf = self.dev["var"] = self.test_model.var_summaries(self.dev.get("var"))
+        self._fetch("var", buf, lambda h: self.events.add_histograms(step, decode_histograms(h, self.tags.variables)))
+
+    def image(self, step):
+        from air import _hip as H
+        from air.air_model import _st_matrices
+        from air.visualize import visualize_reconstructions
+        m = self.test_model
+        n = min(m.num_summary_images, m.batch_size)
+        # every max_steps record (no read of T' on the host): a step the loop did not reach draws no box, no image has
+        # more digits than steps were run (air_model.py:224-231 pads those steps with zeros)
+        st_back = _st_matrices(m.att[:, :n, H.ATT_ST_BACK:H.ATT_ST_BACK + 3].transpose(0, 1))
+        img = visualize_reconstructions(m.input_images[:n], m.reconstruction[:n], st_back, m.rec_num_digits[:n],
+                                        m.canvas_size, m.windows_size, m.max_steps, zoom=2).contiguous()
+        tag = self.tags.image[0]
+        self._fetch("img", img, lambda h: self.events.add_images(step, tag, h.numpy(), max_outputs=m.num_summary_images,
+                                                                 png_level=1))
+
+    def gradients(self, step):
+        from air.summaries import decode_histograms, gradient_summaries
+        buf = self.dev["grad"] = self.train_model.grad_summaries(self.dev.get("grad"))
+        names = self.tags.gradients[::3]
+        self._fetch("grad", buf, lambda h: self.events.add_summary(step, gradient_summaries(decode_histograms(h, names))))
+
+    def flush(self):
+        while self.pending:
+            self._drain_one()
+        self.events.flush()
+
+    def close(self):
+        self.flush()
+        self.events.close()
 
 
 def main():
@@ -125,6 +212,13 @@ def main():
     parser.add_argument("--graph-steps", type=int, default=50,
                         help="train steps per hipGraph replay when --print-every 0 (a divisor of 50)")
     parser.add_argument("--seed", type=int, default=0)
+    parser.add_argument("--tensorboard", action="store_true",
+                        help="also write the reference's TensorBoard summaries to summary/events.out.tfevents.*: 88 scalars every "
+                             "50 iterations, 36 variable histograms every 250, 60 reconstruction images every 500 (all at the "
+                             "iteration's step, from the test model) and 216 gradient summaries every 100, taken after the train "
+                             "step and written under the global step after it.  With --graph-steps > 1 (--print-every 0) the "
+                             "gradient summary is taken after the replay that contains its step: it describes, and is written "
+                             "under, the last step of that replay")
     parser.add_argument("--backward", default="reference", choices=["reference", "reference_carried", "exact"],
                         help="sampler backward: the reference graph's op order, the same streams with the long ones in 16 "
                              "carried chunks per tap, or the exact adjoint")
@@ -224,11 +318,16 @@ def main():
     step = 0
     order = train_model.backward
     t0 = time.perf_counter()
-    writer = SummaryWriter(test_model, summaries_folder + "scalars.jsonl", t0)
+    board = TensorBoardWriter(summaries_folder, train_model, test_model) if args.tensorboard else None
+    writer = SummaryWriter(test_model, summaries_folder + "scalars.jsonl", t0, on_row=board.numeric if board else None)
     while step < total:
         if step % NUM_SUMMARIES_EACH_ITERATIONS == 0:
             test_model.forward()
             writer.push(step)
+            if board and step % VAR_SUMMARIES_EACH_ITERATIONS == 0:
+                if step % IMG_SUMMARIES_EACH_ITERATIONS == 0:
+                    board.image(step)
+                board.variables(step)
         if step % SAVE_PARAMS_EACH_ITERATIONS == 0:
             torch.save(train_model.state_dict(), models_folder + "air-model-%d.pt" % step)
             if args.tf_checkpoints:                                   # training.py:203-207 saver.save(..., global_step)
@@ -239,12 +338,16 @@ def main():
         if gsteps == 1:
             batches.next_batch()
         train_model.training()
+        if board and step % GRAD_SUMMARIES_EACH_ITERATIONS == 0:
+            board.gradients(step + gsteps)
         step += gsteps
         if args.print_every and step % args.print_every == 0:
             print("iteration {}\tloss {:.3f}\taccuracy {:.2f}".format(
                 int(train_model.global_step), float(train_model.loss), float(train_model.accuracy)))
     torch.cuda.synchronize()
     writer.flush()
+    if board:
+        board.close()
     test_model.forward()
     print()
     print("training has ended")
