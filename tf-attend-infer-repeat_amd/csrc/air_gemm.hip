@@ -57,25 +57,12 @@ __global__ __launch_bounds__(THREADS) void gemm_f32_kernel(Args a)
     __shared__ __attribute__((aligned(16))) float Bs[2][BKC * LB];
     __shared__ float Red[3 * TM * TN * 4 * 64];
 
-    if ((int)blockIdx.z < a.job_on) {                    // block-uniform: the prologue's planes of workgroups (dispatched first)
-        const long plane = (long)gridDim.x * gridDim.y;
-        air_step_job_run(a.job, blockIdx.z * plane + (long)blockIdx.y * gridDim.x + blockIdx.x, plane * a.job_on);
-        return;
-    }
-    const int nslab = (int)gridDim.z - a.job_on;
-    const int zslab = (int)blockIdx.z - a.job_on;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tile_m, tile_n;
-    xcd_tile(tile_m, tile_n);
-    const int m0 = tile_m * BM, n0 = tile_n * BN / TN * (a.gstride == 16 ? TN : 1);
-    const int kbeg = zslab * a.kslab;
-    const int kend = min(a.K, kbeg + a.kslab);
+    if (prologue_plane(a)) return;
+    const Frame f = frame_of<TM, TN, false>(a);
+    const int nslab = f.nslab, zslab = f.zslab, tid = f.tid, lane = f.lane, wave = f.wave, m0 = f.m0, n0 = f.n0, kbeg = f.kbeg, kend = f.kend;
 
     f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     const bool vecA = ((a.lda & 3) == 0) && aligned16(a.A);
     const bool vecB = ((a.ldb & 3) == 0) && aligned16(a.B) && ((a.gstride & 3) == 0);
@@ -155,12 +142,11 @@ __global__ __launch_bounds__(THREADS) void gemm_f32_kernel(Args a)
             constexpr int NQ = BN / 4;
             const int it = tid + THREADS * i;
             const int k = it / NQ, q4 = it % NQ;
-            const int j = q4 >> 2, c = (q4 & 3) * 4;
-            const int cg = n0 + c + (a.gstride == 16 ? j * 16 : 0);   // bound-check coordinate
-            const int gn = n0 + j * a.gstride + c, gk = k0 + k;
+            const GroupCol c = group_col(a, n0, q4 * 4);
+            const int gk = k0 + k;
             if (gk < kend) {
-                const float* src = a.B + (size_t)gk * a.ldb + gn;
-                const int lim = min(a.gwidth - cg, a.N - gn);        // valid columns from here
+                const float* src = a.B + (size_t)gk * a.ldb + c.gn;
+                const int lim = min(a.gwidth - c.cg, a.N - c.gn);    // valid columns from here
                 if (vecB && lim >= 4) v = *reinterpret_cast<const float4*>(src);
                 else {
                     if (lim > 0) v.x = src[0];
@@ -234,20 +220,7 @@ __global__ __launch_bounds__(THREADS) void gemm_f32_kernel(Args a)
         }
     }
     reduce_waves<TM, TN>(acc, Red, lane, wave);
-    if (nslab > 1) {
-        // split-K slab: plain store, the consumer sums the slabs
-        float* Cz = a.C + (size_t)zslab * a.slab_stride;
-        for (int t = wave; t < TM * TN; t += 4) {
-            const int i = t / TN, j = t % TN;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = m0 + i * 16 + (lane >> 4) * 4 + q;
-                const int n = n0 + j * 16 + (lane & 15);
-                if (m < a.M && n < a.N) Cz[(size_t)m * a.ldc + n] = Red[(t * 4 + q) * 64 + lane];
-            }
-        }
-        return;
-    }
+    if (nslab > 1) { store_slab<TM, TN>(a, Red, zslab, m0, n0, lane, wave); return; }
     epilogue<TM, TN, EPI_>(a, pre, Red, m0, n0, lane, wave);
 }
 
@@ -267,19 +240,9 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16_kernel(Args a)
     __shared__ __attribute__((aligned(16))) unsigned short Bs[BN * LK];
     __shared__ float Red[3 * TM * TN * 4 * 64];
 
-    if ((int)blockIdx.z < a.job_on) {                    // block-uniform: the prologue's planes of workgroups (dispatched first)
-        const long plane = (long)gridDim.x * gridDim.y;
-        air_step_job_run(a.job, blockIdx.z * plane + (long)blockIdx.y * gridDim.x + blockIdx.x, plane * a.job_on);
-        return;
-    }
-    const int nslab = (int)gridDim.z - a.job_on;
-    const int zslab = (int)blockIdx.z - a.job_on;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tile_m, tile_n;
-    xcd_tile(tile_m, tile_n);
-    const int m0 = tile_m * BM, n0 = tile_n * BN / TN * (a.gstride == 16 ? TN : 1);
-    const int kbeg = zslab * a.kslab;
-    const int kend = min(a.K, kbeg + a.kslab);
+    if (prologue_plane(a)) return;
+    const Frame f = frame_of<TM, TN, false>(a);
+    const int nslab = f.nslab, zslab = f.zslab, tid = f.tid, lane = f.lane, wave = f.wave, m0 = f.m0, n0 = f.n0, kbeg = f.kbeg, kend = f.kend;
 
     float ra[NA], rb[NB];
     auto fetch = [&](int k0) {
@@ -298,12 +261,11 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16_kernel(Args a)
             const int idx = tid + i * THREADS;
             int n, k;
             if (TB) { n = idx / BK; k = idx % BK; } else { k = idx / BN; n = idx % BN; }
-            const int j = n >> 4, c = n & 15;
-            const int cg = n0 + c + (a.gstride == 16 ? j * 16 : 0);
-            const int gn = n0 + j * a.gstride + c, gk = k0 + k;
+            const GroupCol c = group_col(a, n0, n);
+            const int gk = k0 + k;
             float v = 0.0f;
-            if (cg < a.gwidth && gn < a.N && gk < kend)
-                v = TB ? a.B[(size_t)gn * a.ldb + gk] : a.B[(size_t)gk * a.ldb + gn];
+            if (c.cg < a.gwidth && c.gn < a.N && gk < kend)
+                v = TB ? a.B[(size_t)c.gn * a.ldb + gk] : a.B[(size_t)gk * a.ldb + c.gn];
             rb[i] = v;
         }
     };
@@ -325,10 +287,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16_kernel(Args a)
     };
 
     f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     fetch(kbeg);
     for (int k0 = kbeg; k0 < kend; k0 += BK) {
@@ -349,19 +308,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16_kernel(Args a)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv[j], acc[i][j], 0, 0, 0);
     }
     reduce_waves<TM, TN>(acc, Red, lane, wave);
-    if (nslab > 1) {
-        float* Cz = a.C + (size_t)zslab * a.slab_stride;
-        for (int t = wave; t < TM * TN; t += 4) {
-            const int i = t / TN, j = t % TN;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = m0 + i * 16 + (lane >> 4) * 4 + q;
-                const int n = n0 + j * 16 + (lane & 15);
-                if (m < a.M && n < a.N) Cz[(size_t)m * a.ldc + n] = Red[(t * 4 + q) * 64 + lane];
-            }
-        }
-        return;
-    }
+    if (nslab > 1) { store_slab<TM, TN>(a, Red, zslab, m0, n0, lane, wave); return; }
     Pre<TM, TN> pre;
     epilogue_prefetch<TM, TN, -1>(a, pre, m0, n0, lane, wave);
     epilogue<TM, TN, -1>(a, pre, Red, m0, n0, lane, wave);
@@ -654,37 +601,22 @@ __global__ __launch_bounds__(THREADS) void gemm_f32v2_kernel(Args a)
     float* ImgB = ImgA + R * BM * KB;                                    // [R][BN][64]
     float* Red = reinterpret_cast<float*>(Lds);
 
-    if ((int)blockIdx.z < a.job_on) {                    // block-uniform: the prologue's planes of workgroups (dispatched first)
-        const long plane = (long)gridDim.x * gridDim.y;
-        air_step_job_run(a.job, blockIdx.z * plane + (long)blockIdx.y * gridDim.x + blockIdx.x, plane * a.job_on);
-        return;
-    }
-    const int nslab = (int)gridDim.z - a.job_on;
-    const int zslab = (int)blockIdx.z - a.job_on;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tile_m, tile_n;
-    xcd_tile(tile_m, tile_n);
+    if (prologue_plane(a)) return;
     // 16 columns = 4 gates x 4 units: the first-step launch, and (EPI_LSTM_FWD_Q) the later LSTM steps -- 256 workgroups
     // of 16 columns instead of 64 of 64, the same accumulation per element
-    constexpr bool QUADF = EPI_ == AIR_EPI_LSTM_FWD0 || EPI_ == EPI_LSTM_FWD_Q;
-    const int m0 = tile_m * BM, n0 = QUADF ? tile_n * 4 : tile_n * BN / TN * (a.gstride == 16 ? TN : 1);
-    const int kbeg = zslab * a.kslab;
-    const int kend = min(a.K, kbeg + a.kslab);
+    constexpr bool QUADF = quad_epi(EPI_);
+    const Frame f = frame_of<TM, TN, QUADF>(a);
+    const int nslab = f.nslab, zslab = f.zslab, tid = f.tid, lane = f.lane, wave = f.wave, m0 = f.m0, n0 = f.n0, kbeg = f.kbeg, kend = f.kend;
 
     f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     Pre<TM, TN> pre;
     if (nslab == 1) epilogue_prefetch<TM, TN, EPI_>(a, pre, m0, n0, lane, wave);
 
     const char* Ab = reinterpret_cast<const char*>(a.A);
     const char* Bb = reinterpret_cast<const char*>(a.B);
-    const bool a8 = !(((a.lda & 3) == 0) && aligned16(a.A) && ((a.K & 3) == 0));
-    const bool b8 = !(((a.ldb & 3) == 0) && aligned16(a.B) &&
-                      (TB ? ((a.K & 3) == 0) : (((a.N & 3) == 0) && ((a.gstride & 3) == 0) && ((a.gwidth & 3) == 0))));
+    const bool a8 = halves_a(a), b8 = halves_b<TB>(a);
     // tasks of one round.  k-contiguous operand (A, and B when TB): task = (image, row, k-run g) = 2 float4;
     // NN B: task = (image, column quad, k-run g) = the same 4 columns of 8 consecutive rows = 8 float4.
     constexpr int TA_N = (R * BM * 8 + THREADS - 1) / THREADS;           // A tasks per thread
@@ -712,11 +644,10 @@ __global__ __launch_bounds__(THREADS) void gemm_f32v2_kernel(Args a)
             for (int i = 0; i < TBK_N; ++i) {
                 const int t = tid + THREADS * i;
                 const int c = t / (BN * 8), col = (t / 8) % BN, g = t & 7;
-                const int j = col >> 4, cc = col & 15;
-                const int gn = n0 + j * a.gstride + cc, cg = n0 + cc + (a.gstride == 16 ? j * 16 : 0);
+                const GroupCol gc = group_col(a, n0, col);
                 const int gk = kr + c * KB + g * 8;
-                const bool okr = (t < R * BN * 8) && cg < a.gwidth && gn < a.N;
-                const unsigned off = ((unsigned)gn * (unsigned)a.ldb + (unsigned)gk) * 4u;
+                const bool okr = (t < R * BN * 8) && gc.cg < a.gwidth && gc.gn < a.N;
+                const unsigned off = ((unsigned)gc.gn * (unsigned)a.ldb + (unsigned)gk) * 4u;
                 vbk[i][0] = ldg16x<HB>(Bb, off, okr && gk < kend, okr && gk + 2 < kend);
                 vbk[i][1] = ldg16x<HB>(Bb, off + 16u, okr && gk + 4 < kend, okr && gk + 6 < kend);
             }
@@ -725,14 +656,12 @@ __global__ __launch_bounds__(THREADS) void gemm_f32v2_kernel(Args a)
             for (int i = 0; i < TBN_N; ++i) {
                 const int t = tid + THREADS * i;
                 const int c = t / (BN * 2), q = (t / 8) % (BN / 4), g = t & 7;
-                const int col = q * 4, j = col >> 4, cc = col & 15;
-                // (LSTM_FWD0: column quad q = gate q of the four units n0 .. n0+3)
-                const int gn = QUADF ? n0 + q * a.gstride : n0 + j * a.gstride + cc;
-                const int cg = QUADF ? n0 : n0 + cc + (a.gstride == 16 ? j * 16 : 0);
+                // (QUAD: column quad q = gate q of the four units n0 .. n0+3)
+                const GroupCol gc = group_col<QUADF>(a, n0, q * 4);
                 const int gk = kr + c * KB + g * 8;
-                const bool okc = (t < R * BN * 2) && cg < a.gwidth && gn < a.N;
-                const bool okh = okc && cg + 2 < a.gwidth && gn + 2 < a.N;     // upper half of the column quad
-                const unsigned off = ((unsigned)gk * (unsigned)a.ldb + (unsigned)gn) * 4u;
+                const bool okc = (t < R * BN * 2) && gc.cg < a.gwidth && gc.gn < a.N;
+                const bool okh = okc && gc.cg + 2 < a.gwidth && gc.gn + 2 < a.N;     // upper half of the column quad
+                const unsigned off = ((unsigned)gk * (unsigned)a.ldb + (unsigned)gc.gn) * 4u;
 #pragma unroll
                 for (int r = 0; r < 8; ++r)
                     vbn[i][r] = ldg16x<HB>(Bb, off + (unsigned)r * ((unsigned)a.ldb * 4u), okc && gk + r < kend,
@@ -830,19 +759,7 @@ __global__ __launch_bounds__(THREADS) void gemm_f32v2_kernel(Args a)
     }
     __syncthreads();                                                      // Red aliases the images
     reduce_waves<TM, TN>(acc, Red, lane, wave);
-    if (nslab > 1) {
-        float* Cz = a.C + (size_t)zslab * a.slab_stride;
-        for (int t = wave; t < TM * TN; t += 4) {
-            const int i = t / TN, j = t % TN;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = m0 + i * 16 + (lane >> 4) * 4 + q;
-                const int n = n0 + j * 16 + (lane & 15);
-                if (m < a.M && n < a.N) Cz[(size_t)m * a.ldc + n] = Red[(t * 4 + q) * 64 + lane];
-            }
-        }
-        return;
-    }
+    if (nslab > 1) { store_slab<TM, TN>(a, Red, zslab, m0, n0, lane, wave); return; }
     epilogue<TM, TN, EPI_>(a, pre, Red, m0, n0, lane, wave);
 }
 
@@ -905,8 +822,7 @@ void resolve_tile(const air_gemm_t* g, int& tm, int& tn) {
 
 // lean bf16 variant: 8-byte alignment and even K / N / group strides suffice (it splits its 16-byte loads)
 bool use_bf16_v2(const Args& a, bool ta, bool tb) {
-    auto al8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; };
-    return !ta && al8(a.A) && al8(a.B) && (a.lda & 1) == 0 && (a.ldb & 1) == 0 && (a.K & 1) == 0 &&
+    return !ta && aligned8(a.A) && aligned8(a.B) && (a.lda & 1) == 0 && (a.ldb & 1) == 0 && (a.K & 1) == 0 &&
            (tb || ((a.N & 1) == 0 && (a.gstride & 1) == 0 && (a.gwidth & 1) == 0));
 }
 
@@ -941,18 +857,17 @@ int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb) {
     // else needs the row-major twin)
     const bool pnl_tile = !tb && a.B16p != nullptr && ((tm == 1 && tn == 1) || (tm == 2 && tn == 2) || (tm == 1 && tn == 4));
     if (ta || (!a.B16 && !pnl_tile)) return 0;
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     const bool af32 = a.A16 == nullptr;
     // whole 16-byte pieces only: the ragged shapes keep the fp32-operand kernels
     // (the twin-A x.Wx may read a PADDED twin -- air_gemm_t.i0 bit 1 says so; without it A16 is an ordinary twin with the
     // leading dimension of A.  K itself may then be ragged: the 16-byte piece that straddles it ends inside the row's zero
     // pad -- lda >= K rounded up to 8 -- and the panel twin of B is addressed by the true K)
     const bool padded = fwd0_padded(a);
-    if (af32) { if (!al16(a.A) || (a.lda & 3) || (a.K & 3) || (a.kslab & 3) || (a.epi == AIR_EPI_LSTM_FWD0 && !al16(a.C16))) return 0; }
-    else if (padded) { if (!al16(a.A16) || (a.lda & 7) || a.lda < ((a.K + 7) & ~7) || !pnl_tile || tb) return 0; }
-    else if (!al16(a.A16) || (a.lda & 7) || (a.K & 7) || (a.kslab & 7)) return 0;
-    if (pnl_tile) { if (!al16(a.B16p)) return 0; }
-    else if (!al16(a.B16) || (a.ldb & 7)) return 0;
+    if (af32) { if (!aligned16(a.A) || (a.lda & 3) || (a.K & 3) || (a.kslab & 3) || (a.epi == AIR_EPI_LSTM_FWD0 && !aligned16(a.C16))) return 0; }
+    else if (padded) { if (!aligned16(a.A16) || (a.lda & 7) || a.lda < ((a.K + 7) & ~7) || !pnl_tile || tb) return 0; }
+    else if (!aligned16(a.A16) || (a.lda & 7) || (a.K & 7) || (a.kslab & 7)) return 0;
+    if (pnl_tile) { if (!aligned16(a.B16p)) return 0; }
+    else if (!aligned16(a.B16) || (a.ldb & 7)) return 0;
     if (tb) { if ((a.K & 7) || (a.kslab & 7)) return 0; }
     else if ((a.N & 7) || (a.gstride & 7) || (a.gwidth & 7)) return 0;
     const int nimg = images_of(a);
@@ -977,10 +892,9 @@ int twin_rounds(const Args& a, int tm, int tn, bool ta, bool tb) {
 
 // tile (8, 4) of the ABI = the throughput kernel (fp32 A x bf16 shadow, split-K slabs): eligibility
 int xw_tp_ok(const Args& a, int precision, bool ta, bool tb, int ksplit) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     if (precision != 1 || ta || tb || !a.B16 || a.epi != AIR_EPI_GENERIC || ksplit <= 1) return AIR_EINVAL;
     if ((a.M % 64) || (a.N % 64) || (a.kslab % 64) || (a.K % 64)) return AIR_EALIGN;
-    if (!al16(a.A) || !al16(a.B16) || (a.lda & 3) || (a.ldb & 7)) return AIR_EALIGN;
+    if (!aligned16(a.A) || !aligned16(a.B16) || (a.lda & 3) || (a.ldb & 7)) return AIR_EALIGN;
     return 0;
 }
 
@@ -1143,7 +1057,7 @@ static int fill_args(const air_gemm_t* g, Args& a) {
         if (j.n_normal < 0 || j.n_uniform < 0 || (j.n_normal > 0 && !j.normals) || (j.n_uniform > 0 && !j.uniforms)) return AIR_EINVAL;
         a.job_on = 1;
         if (j.twin_n < 0 || (j.twin_n > 0 && (!j.twin_src || !j.twin_dst))) return AIR_EINVAL;
-        if (j.twin_n > 0 && (!aligned16(j.twin_src) || (reinterpret_cast<uintptr_t>(j.twin_dst) & 7) != 0)) return AIR_EALIGN;
+        if (j.twin_n > 0 && (!aligned16(j.twin_src) || !aligned8(j.twin_dst))) return AIR_EALIGN;
         a.job = AirStepJob{j.sched, j.nsched, j.dyn, j.istate, j.normals, (long)j.n_normal, j.uniforms, (long)j.n_uniform,
                            (uint32_t)(j.seed & 0xffffffffu), (uint32_t)(j.seed >> 32), j.twin_src, j.twin_dst, (long)j.twin_n};
     }

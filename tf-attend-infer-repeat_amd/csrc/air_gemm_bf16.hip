@@ -35,8 +35,6 @@ AIR_STAMPS_READER(air_debug_stamps_gemm_tw)
 
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ uint4 ldg16u(const char* base, unsigned off, bool ok) {
     const uint4 t = *reinterpret_cast<const uint4*>(base + (ok ? off : 0u));
     return ok ? t : make_uint4(0u, 0u, 0u, 0u);
@@ -68,27 +66,14 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
     unsigned short* ImgB = ImgA + R * BM * KB;                           // TB: [R][BN][64] swizzled; else [R][64][BN]
     float* Red = reinterpret_cast<float*>(Lds);
 
-    if ((int)blockIdx.z < a.job_on) {                    // block-uniform: the prologue's planes of workgroups (dispatched first)
-        const long plane = (long)gridDim.x * gridDim.y;
-        air_step_job_run(a.job, blockIdx.z * plane + (long)blockIdx.y * gridDim.x + blockIdx.x, plane * a.job_on);
-        return;
-    }
-    const int nslab = (int)gridDim.z - a.job_on;
-    const int zslab = (int)blockIdx.z - a.job_on;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tile_m, tile_n;
-    xcd_tile(tile_m, tile_n);
-    constexpr bool QUAD = EPI_ == EPI_LSTM_FWD_Q || EPI_ == AIR_EPI_LSTM_FWD0;   // 16 columns = 4 gates x 4 units (TN == 1, untransposed B)
-    const int m0 = tile_m * BM, n0 = QUAD ? tile_n * 4 : tile_n * BN / TN * (a.gstride == 16 ? TN : 1);
-    const int kbeg = zslab * a.kslab;
-    const int kend = min(a.K, kbeg + a.kslab);
+    if (prologue_plane(a)) return;
+    constexpr bool QUAD = quad_epi(EPI_);                  // 16 columns = 4 gates x 4 units (TN == 1, untransposed B)
+    const Frame f = frame_of<TM, TN, QUAD>(a);
+    const int nslab = f.nslab, zslab = f.zslab, tid = f.tid, lane = f.lane, wave = f.wave, m0 = f.m0, n0 = f.n0, kbeg = f.kbeg, kend = f.kend;
 
     AIR_STAMP(56);
     f32x4 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     Pre<TM, TN> pre;
 
@@ -115,7 +100,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
     uint4 vb[QUAD ? 1 : (TB ? TBK_N : TBN_N)];
     uint2 vq[QUAD ? 2 * TBQ16_N : 1];
     // AF32 x.Wx: the workgroups of column panel 0 leave their rows behind as the padded bf16 twin (a.C16, row stride ldt)
-    const bool twin_out = AF32 && EPI_ == AIR_EPI_LSTM_FWD0 && a.C16 != nullptr && tile_n == 0;
+    const bool twin_out = AF32 && EPI_ == AIR_EPI_LSTM_FWD0 && a.C16 != nullptr && n0 == 0;
     const int ldt = (a.K + 7) & ~7;
 
     auto issue_loads = [&](int kr) __attribute__((always_inline)) {
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
             for (int i = 0; i < TBQ_N; ++i) {
                 const int t = tid + THREADS * i;
                 const int c = t / (KB * 4), k = (t >> 2) % KB, gate = t & 3;
-                const int gn = gate * a.gstride + n0, gk = kr + c * KB + k;
+                const int gn = group_col<true>(a, n0, gate * 4).gn, gk = kr + c * KB + k;
                 const bool ok = (t < R * KB * 4) && n0 < a.gwidth && gk < kend;
                 const unsigned off = pnl ? (unsigned)(n0 >> 2) * pK16 + (unsigned)gk * 16u + (unsigned)gate * 4u
                                          : (unsigned)gk * (unsigned)a.ldb + (unsigned)gn;
@@ -163,23 +148,21 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
             for (int i = 0; i < TBK_N; ++i) {
                 const int u = tid + THREADS * i;
                 const int c = u / (BN * 8), col = (u / 8) % BN, g = u & 7;
-                const int j = col >> 4, cc = col & 15;
-                const int gn = n0 + j * a.gstride + cc, cg = n0 + cc + (a.gstride == 16 ? j * 16 : 0);
+                const GroupCol gc = group_col(a, n0, col);
                 const int gk = kr + c * KB + g * 8;
-                const bool ok = (u < R * BN * 8) && cg < a.gwidth && gn < a.N && gk < kend;
-                vb[i] = ldg16u(Bb, ((unsigned)gn * (unsigned)a.ldb + (unsigned)gk) * 2u, ok);
+                const bool ok = (u < R * BN * 8) && gc.cg < a.gwidth && gc.gn < a.N && gk < kend;
+                vb[i] = ldg16u(Bb, ((unsigned)gc.gn * (unsigned)a.ldb + (unsigned)gk) * 2u, ok);
             }
         } else {
 #pragma unroll
             for (int i = 0; i < TBN_N; ++i) {
                 const int t = tid + THREADS * i;
                 const int c = t / (KB * (BN / 8)), k = (t / (BN / 8)) % KB, h = t % (BN / 8);
-                const int col = h * 8, j = col >> 4, cc = col & 15;
-                const int gn = n0 + j * a.gstride + cc, cg = n0 + cc + (a.gstride == 16 ? j * 16 : 0);
+                const GroupCol gc = group_col(a, n0, h * 8);
                 const int gk = kr + c * KB + k;
-                const bool ok = (t < R * KB * (BN / 8)) && cg < a.gwidth && gn < a.N && gk < kend;
-                const unsigned off = pnl ? (unsigned)(gn >> 4) * pK16 + (unsigned)gk * 16u + (unsigned)(gn & 15)
-                                         : (unsigned)gk * (unsigned)a.ldb + (unsigned)gn;
+                const bool ok = (t < R * KB * (BN / 8)) && gc.cg < a.gwidth && gc.gn < a.N && gk < kend;
+                const unsigned off = pnl ? (unsigned)(gc.gn >> 4) * pK16 + (unsigned)gk * 16u + (unsigned)(gc.gn & 15)
+                                         : (unsigned)gk * (unsigned)a.ldb + (unsigned)gc.gn;
                 vb[i] = ldg16u(Bb, off * 2u, ok);
             }
         }
@@ -251,7 +234,9 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
         if (kr + R * KB < kend) issue_loads(kr + R * KB);
         __syncthreads();
         AIR_STAMP(58);
-        // ---- MFMAs: wave w owns the images whose index within the slab is w (mod 4), whatever R is
+        // ---- MFMAs: mfma_round_bf16<TM, TN, R, !TB> (air_gemm_common.h), left inline HERE: through the function the
+        // register allocation of the 32 x 32 tiles with R = 8 changes -- same instructions, 164 -> 188 VGPRs, occupancy
+        // 3 -> 2 in <2, 2, false, 0, false, 8>.  Keep the two in step.
         const int cfirst = (wave - ((kr - kbeg) / KB)) & 3;
 #pragma unroll
         for (int cc = 0; cc < (R + 3) / 4; ++cc) {
@@ -273,17 +258,10 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
                             bv[j] = *reinterpret_cast<const bf16x8*>(&ImgB[(c * BN + col) * KB + ((slot ^ (col & 7)) << 3)]);
                         }
                     } else {
-                        // transpose read: lane i of a 16-lane group hands in the address of row 8g + i/4 (+4),
-                        // column quad i%4 of the [k][16] block; it receives k = 8g .. 8g+3 (+4) of column i
                         const int il = lane & 15;
                         const unsigned short* blk = &ImgB[(c * KB + ks * 32 + (lane >> 4) * 8 + (il >> 2)) * BN + (il & 3) * 4];
 #pragma unroll
-                        for (int j = 0; j < TN; ++j) {
-                            typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-                            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + j * 16));
-                            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + j * 16 + 4 * BN));
-                            bv[j] = bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                        }
+                        for (int j = 0; j < TN; ++j) bv[j] = read_tr_bf16x8(blk + j * 16, BN);
                     }
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
@@ -298,19 +276,7 @@ __global__ __launch_bounds__(THREADS) void gemm_bf16tw_kernel(Args a)
     __syncthreads();                                                      // Red aliases the images
     reduce_waves<TM, TN>(acc, Red, lane, wave);
     AIR_STAMP(60);
-    if (nslab > 1) {
-        float* Cz = a.C + (size_t)zslab * a.slab_stride;
-        for (int t = wave; t < TM * TN; t += 4) {
-            const int i = t / TN, j = t % TN;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int m = m0 + i * 16 + (lane >> 4) * 4 + q;
-                const int n = n0 + j * 16 + (lane & 15);
-                if (m < a.M && n < a.N) Cz[(size_t)m * a.ldc + n] = Red[(t * 4 + q) * 64 + lane];
-            }
-        }
-        return;
-    }
+    if (nslab > 1) { store_slab<TM, TN>(a, Red, zslab, m0, n0, lane, wave); return; }
     epilogue<TM, TN, EPI_>(a, pre, Red, m0, n0, lane, wave);
     AIR_STAMP(61);
 }
@@ -374,10 +340,7 @@ __global__ __launch_bounds__(THREADS) void gemm_xw_tp_kernel(Args a)
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * (BN / 2);   // this wave's 32 x BN/2 part, over the whole K slab
 
     f32x4 acc[2][NJ];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     // staging maps: A piece = float4 (4 k) of row (tid >> 4) + 16 i; B piece = 16 bytes (8 columns) of k row tid / PPR + RPP i
     const int ar = tid >> 4, ah = tid & 15, bk = tid / PPR, bh = tid % PPR;
@@ -422,12 +385,7 @@ __global__ __launch_bounds__(THREADS) void gemm_xw_tp_kernel(Args a)
             }
             const unsigned short* blk = &ImgB[buf][(ks * 32 + (lane >> 4) * 8 + (il >> 2)) * BN + wn + (il & 3) * 4];
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + j * 16));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + j * 16 + 4 * BN));
-                bv[j] = bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            }
+            for (int j = 0; j < NJ; ++j) bv[j] = read_tr_bf16x8(blk + j * 16, BN);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -484,19 +442,13 @@ __global__ __launch_bounds__(THREADS) void gemm_xwx_glds_kernel(Args a)
     typedef __attribute__((address_space(3))) unsigned char lds_u8;
     typedef const __attribute__((address_space(1))) unsigned char glb_u8;
 
-    if ((int)blockIdx.z < a.job_on) {                    // the prologue's planes of workgroups (dispatched first)
-        const long plane = (long)gridDim.x * gridDim.y;
-        air_step_job_run(a.job, blockIdx.z * plane + (long)blockIdx.y * gridDim.x + blockIdx.x, plane * a.job_on);
-        return;
-    }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int tile_m, tile_n;
-    xcd_tile(tile_m, tile_n);
-    const int m0 = tile_m * BM, n0 = tile_n * 4;
+    if (prologue_plane(a)) return;
+    const Frame f = frame_of<1, 1, true>(a);
+    const int tid = f.tid, lane = f.lane, wave = f.wave, m0 = f.m0, n0 = f.n0;
     const int kbeg = 0, kend = a.K;                      // one slab (twin_rounds)
 
     f32x4 acc[1][1];
-    acc[0][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     Pre<1, 1> pre;
 
     const char* Ab = reinterpret_cast<const char*>(a.A16);
@@ -541,27 +493,7 @@ __global__ __launch_bounds__(THREADS) void gemm_xwx_glds_kernel(Args a)
         if (kr > kbeg) { __syncthreads(); fill_images(kr); }              // images of the previous round consumed
         __syncthreads();
         AIR_STAMP(58);
-        // ---- MFMAs: wave w owns the images whose index within the slab is w (mod 4), whatever R is
-        const int cfirst = (wave - ((kr - kbeg) / KB)) & 3;
-#pragma unroll
-        for (int cc = 0; cc < (R + 3) / 4; ++cc) {
-            const int c = cfirst + 4 * cc;
-            if (c < R && kr + c * KB < kend) {
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const int slot = ks * 4 + (lane >> 4);
-                    const int row = lane & 15;
-                    const bf16x8 av = *reinterpret_cast<const bf16x8*>(&ImgA[(c * BM + row) * KB + ((slot ^ (row & 7)) << 3)]);
-                    const int il = lane & 15;
-                    const unsigned short* blk = &ImgB[(c * KB + ks * 32 + (lane >> 4) * 8 + (il >> 2)) * BN + (il & 3) * 4];
-                    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + 4 * BN));
-                    const bf16x8 bv = bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, bv, acc[0][0], 0, 0, 0);
-                }
-            }
-        }
+        mfma_round_bf16<1, 1, R, true>(acc, ImgA, ImgB, kr, kbeg, kend, lane, wave);
         if (R >= 40) break;                                               // (twin_rounds: 40 images are the whole contraction)
     }
     AIR_STAMP(59);
@@ -622,7 +554,7 @@ __global__ __launch_bounds__(256) void bf16_twin_kernel(const float* __restrict_
 
 extern "C" int air_bf16_twin(const float* src, uint16_t* dst, int64_t n, void* stream) {
     if (!src || !dst || n <= 0) return AIR_EINVAL;
-    if (((reinterpret_cast<uintptr_t>(src) & 15) != 0) || ((reinterpret_cast<uintptr_t>(dst) & 7) != 0)) return AIR_EALIGN;
+    if (!aligned16(src) || !aligned8(dst)) return AIR_EALIGN;
     long blocks = (n / 4 + 255) / 256;
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
     hipLaunchKernelGGL(bf16_twin_kernel, dim3((unsigned)blocks), dim3(256), 0, air_stream(stream), src, dst, (long)n);

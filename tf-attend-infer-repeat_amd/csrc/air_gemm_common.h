@@ -1,9 +1,11 @@
 // Shared pieces of the GEMM translation units (air_gemm.hip: fp32-operand kernels; air_gemm_bf16.hip:
 // bf16-twin-operand kernels): kernel arguments, the prefetched fused epilogues, the cross-wave reduction
-// and the XCD-aware tile map -- inline device code in namespace airg -- and, at the end, the host's dispatch plan.
+// the XCD-aware tile map and the skeleton around the staging (tile frame, slab store, column map, the bf16 MFMA round)
+// -- inline device code in namespace airg -- and, at the end, the host's dispatch plan.
 #pragma once
 #include "air_common.h"
 #include "air_philox.h"
+#include "air_lstm_cell.h"
 #include <type_traits>
 
 namespace airg {
@@ -16,6 +18,8 @@ constexpr int THREADS = 256;
 // c = gate c >> 2 of unit n0 + (c & 3)) -- four times as many, four times lighter workgroups than the 64-column
 // grouped tiles; same accumulation per element, same epilogue arithmetic (air_gemm_bf16.hip)
 constexpr int EPI_LSTM_FWD_Q = 100;
+// the template epilogues whose 16-column tile is four units x four gates
+constexpr bool quad_epi(int epi) { return epi == AIR_EPI_LSTM_FWD0 || epi == EPI_LSTM_FWD_Q; }
 
 __device__ __forceinline__ unsigned short f32_to_bf16_rne(float f) {
     unsigned int u = __float_as_uint(f);
@@ -215,15 +219,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                     if (a.bias) s += pre.f[32 + j];
                     g[j] = s;
                 }
-                const float si = air_sigmoid(g[0]), tj = tanhf(g[1]);
-                const float sf = air_sigmoid(g[2] + 1.0f), so = air_sigmoid(g[3]);
-                const float cn = pre.f[36] * sf + si * tj;
-                float* ac = a.q0 + (size_t)m * 4 * R;
-                ac[u] = si; ac[R + u] = tj; ac[2 * R + u] = sf; ac[3 * R + u] = so;
-                a.q1[(size_t)m * R + u] = cn;
-                const float hn = tanhf(cn) * so;
-                a.q2[(size_t)m * R + u] = hn;
-                if (a.q2_16) a.q2_16[(size_t)m * R + u] = air_bf16_of(hn);
+                air_lstm_cell_fwd(g, pre.f[36], a.q0 + (size_t)m * 4 * R, a.q1, a.q2, a.q2_16, R, u, (size_t)m * R + u);
             }
         }
         return;
@@ -246,15 +242,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                     if (a.bias) s += pre.f[j];
                     g[j] = s;
                 }
-                const float si = air_sigmoid(g[0]), tj = tanhf(g[1]);
-                const float sf = air_sigmoid(g[2] + 1.0f), so = air_sigmoid(g[3]);
-                const float cn = 0.0f * sf + si * tj;
-                float* ac = a.q0 + (size_t)m * 4 * R;
-                ac[u] = si; ac[R + u] = tj; ac[2 * R + u] = sf; ac[3 * R + u] = so;
-                a.q1[(size_t)m * R + u] = cn;
-                const float hn = tanhf(cn) * so;
-                a.q2[(size_t)m * R + u] = hn;
-                if (a.q2_16) a.q2_16[(size_t)m * R + u] = air_bf16_of(hn);
+                air_lstm_cell_fwd(g, 0.0f, a.q0 + (size_t)m * 4 * R, a.q1, a.q2, a.q2_16, R, u, (size_t)m * R + u);
             }
         }
         return;
@@ -282,15 +270,7 @@ __device__ __forceinline__ void epilogue(const Args& a, const Pre<TM, TN>& pre, 
                     if (a.bias) s += pre.f[32 + j];
                     g[j] = s;
                 }
-                const float si = air_sigmoid(g[0]), tj = tanhf(g[1]);
-                const float sf = air_sigmoid(g[2] + 1.0f), so = air_sigmoid(g[3]);
-                const float cn = pre.f[36] * sf + si * tj;
-                float* ac = a.q0 + (size_t)m * 4 * R;
-                ac[u] = si; ac[R + u] = tj; ac[2 * R + u] = sf; ac[3 * R + u] = so;
-                a.q1[(size_t)m * R + u] = cn;
-                const float hn = tanhf(cn) * so;
-                a.q2[(size_t)m * R + u] = hn;
-                if (a.q2_16) a.q2_16[(size_t)m * R + u] = air_bf16_of(hn);
+                air_lstm_cell_fwd(g, pre.f[36], a.q0 + (size_t)m * 4 * R, a.q1, a.q2, a.q2_16, R, u, (size_t)m * R + u);
             }
         } else if (E == AIR_EPI_REPARAM_FWD) {
             // vae.py:16-24: mean | log_var (+bias), sample = mean + eps*sqrt(exp(lv))
@@ -406,6 +386,148 @@ __device__ __forceinline__ void xcd_tile(int& tile_m, int& tile_n) {
 }
 
 __host__ __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+__host__ __device__ __forceinline__ bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// ---- the skeleton the tiled kernels share.  What differs between families -- the global -> LDS staging -- stays in
+// the family; a new staging variant is one staging function beside the others, around these parts.
+// (gemm_bf16v2_kernel, air_gemm.hip, does not use them: with them its large tiles measured 1.3 .. 3 % slower, DESIGN.md
+// section 23.  Its body is the text these functions were taken from: keep them in step)
+
+// The step prologue's planes of workgroups (grid.z planes [0, job_on): dispatched first) run the carried job.
+// True: this workgroup was one of them and is done (block-uniform).  Called as `if (prologue_plane(a)) return;`
+// -- (measured on the assembly: a form that also fills the Frame below through a reference costs the kernels up
+// to 45 VGPRs and an occupancy step; keep the two apart)
+__device__ __forceinline__ bool prologue_plane(const Args& a) {
+    if ((int)blockIdx.z >= a.job_on) return false;
+    const long plane = (long)gridDim.x * gridDim.y;
+    air_step_job_run(a.job, blockIdx.z * plane + (long)blockIdx.y * gridDim.x + blockIdx.x, plane * a.job_on);
+    return true;
+}
+
+// where a product workgroup stands: its split-K slab and k-range, its wave / lane and the origin of its tile.
+// The kernels copy the members into local ints (`const int m0 = f.m0, ...`) before their staging lambdas capture them:
+// (measured on the assembly, DESIGN.md section 23: with `f.m0` inside the lambdas of a kernel as large as the lean bf16
+// one every instance is scheduled differently -- 12 .. 37 VGPRs fewer, up to 14 % more code, scratch where there was
+// none; with locals the code stays the inline form's)
+struct Frame {
+    int nslab, zslab;             // grid.z planes behind the prologue's: slab count, this workgroup's slab
+    int tid, lane, wave;
+    int m0, n0;                   // tile origin; n0 in UNITS for grouped tiles (Args.gstride)
+    int kbeg, kend;
+};
+// QUAD: 16 columns = 4 gates x 4 units (column c = gate c >> 2 of unit n0 + (c & 3)), TN == 1
+template <int TM, int TN, bool QUAD>
+__device__ __forceinline__ Frame frame_of(const Args& a) {
+    Frame f;
+    f.nslab = (int)gridDim.z - a.job_on;
+    f.zslab = (int)blockIdx.z - a.job_on;
+    f.tid = threadIdx.x; f.lane = f.tid & 63; f.wave = f.tid >> 6;
+    int tile_m, tile_n;
+    xcd_tile(tile_m, tile_n);
+    f.m0 = tile_m * 16 * TM;
+    f.n0 = QUAD ? tile_n * 4 : tile_n * 16 * (a.gstride == 16 ? TN : 1);
+    f.kbeg = f.zslab * a.kslab;
+    f.kend = min(a.K, f.kbeg + a.kslab);
+    return f;
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// the lean kernels load 16 bytes as two 8-byte halves when an operand is only 8-byte aligned (ldg16x<HALF>):
+// row strides / column-group strides that are even but not multiples of 4 (Z = 50)
+__device__ __forceinline__ bool halves_a(const Args& a) { return !(((a.lda & 3) == 0) && aligned16(a.A) && ((a.K & 3) == 0)); }
+template <bool TB>
+__device__ __forceinline__ bool halves_b(const Args& a) {
+    return !(((a.ldb & 3) == 0) && aligned16(a.B) &&
+             (TB ? ((a.K & 3) == 0) : (((a.N & 3) == 0) && ((a.gstride & 3) == 0) && ((a.gwidth & 3) == 0))));
+}
+
+// Grouped column tiles: tile column `col` (16-column tile j = col >> 4, column cc = col & 15 in it) is column gn of
+// B / C; it exists if cg < gwidth and gn < N (cg: the bound-check coordinate -- the unit for grouped tiles).
+// QUAD: col = 4 * gate, of the four units n0 .. n0 + 3.
+struct GroupCol { int gn, cg; };
+template <bool QUAD = false>
+__device__ __forceinline__ GroupCol group_col(const Args& a, int n0, int col) {
+    if (QUAD) return GroupCol{n0 + (col >> 2) * a.gstride, n0};
+    const int j = col >> 4, cc = col & 15;
+    return GroupCol{n0 + j * a.gstride + cc, n0 + cc + (a.gstride == 16 ? j * 16 : 0)};
+}
+
+// split-K slab: plain store of the reduced tile, the consumer sums the slabs
+template <int TM, int TN>
+__device__ __forceinline__ void store_slab(const Args& a, const float* Red, int zslab, int m0, int n0, int lane, int wave) {
+    float* Cz = a.C + (size_t)zslab * a.slab_stride;
+    for (int t = wave; t < TM * TN; t += 4) {
+        const int i = t / TN, j = t % TN;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int m = m0 + i * 16 + (lane >> 4) * 4 + q;
+            const int n = n0 + j * 16 + (lane & 15);
+            if (m < a.M && n < a.N) Cz[(size_t)m * a.ldc + n] = Red[(t * 4 + q) * 64 + lane];
+        }
+    }
+}
+
+// gfx950 transpose read ds_read_b64_tr_b16, twice: from a [k][BN] bf16 image, lane i of a 16-lane group hands in the
+// address of row 8g + i/4 (+4), column quad i%4 of the [k][16] block (blk); it receives k = 8g .. 8g+3 (+4) of
+// column i -- the 8 consecutive k v_mfma_f32_16x16x32_bf16 wants
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ bf16x8 read_tr_bf16x8(const unsigned short* blk, int BN) {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + 4 * BN));
+    return bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+}
+
+// MFMAs of one round of R 64-deep bf16 image pairs, ImgA = [R][BM][64 k] with the 16-byte slots of a row XOR-swizzled by
+// row & 7; ImgB the same over columns (TRB false), or [R][64 k][BN] as the operand lies, read by transpose (TRB).
+// Wave w owns the images whose index WITHIN THE SLAB is w (mod 4) -- independent of the round length R, so every tile
+// configuration and every staging variant sums k in the same order.
+template <int TM, int TN, int R, bool TRB>
+__device__ __forceinline__ void mfma_round_bf16(f32x4 (&acc)[TM][TN], const unsigned short* ImgA, const unsigned short* ImgB,
+                                                int kr, int kbeg, int kend, int lane, int wave) {
+    constexpr int BM = 16 * TM, BN = 16 * TN, KB = 64;
+    const int cfirst = (wave - ((kr - kbeg) / KB)) & 3;
+#pragma unroll
+    for (int cc = 0; cc < (R + 3) / 4; ++cc) {
+        const int c = cfirst + 4 * cc;
+        if (c < R && kr + c * KB < kend) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const int slot = ks * 4 + (lane >> 4);
+                bf16x8 av[TM], bv[TN];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const int row = i * 16 + (lane & 15);
+                    av[i] = *reinterpret_cast<const bf16x8*>(&ImgA[(c * BM + row) * KB + ((slot ^ (row & 7)) << 3)]);
+                }
+                if (!TRB) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        const int col = j * 16 + (lane & 15);
+                        bv[j] = *reinterpret_cast<const bf16x8*>(&ImgB[(c * BN + col) * KB + ((slot ^ (col & 7)) << 3)]);
+                    }
+                } else {
+                    const int il = lane & 15;
+                    const unsigned short* blk = &ImgB[(c * KB + ks * 32 + (lane >> 4) * 8 + (il >> 2)) * BN + (il & 3) * 4];
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) bv[j] = read_tr_bf16x8(blk + j * 16, BN);
+                }
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[i], bv[j], acc[i][j], 0, 0, 0);
+            }
+        }
+    }
+}
 
 // ---- host: the dispatch plan.  plan_gemm (air_gemm.hip) is the ONE place that decides which kernel a descriptor gets;
 // air_gemm launches the plan and air_gemm_kernel_name formats it, so the two cannot disagree.

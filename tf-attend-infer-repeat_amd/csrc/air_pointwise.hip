@@ -4,13 +4,13 @@
 // coalesced accesses and reduces in a fixed order (deterministic).
 #include "air_common.h"
 #include "air_elementwise.h"
+#include "air_lstm_cell.h"
 
 namespace {
 
 constexpr int THREADS = 256;
 
-// BasicLSTMCell (TF 1.3): i, j, f, o = split(gates, 4, 1);
-// c' = c*sigmoid(f + 1) + sigmoid(i)*tanh(j); h' = tanh(c')*sigmoid(o)   (air_model.py:286)
+// BasicLSTMCell (TF 1.3) on stored pre-activations: the cell itself is air_lstm_cell.h
 __global__ __launch_bounds__(THREADS) void lstm_gates_fwd_kernel(
     const float* __restrict__ gp, const float* __restrict__ c_prev, float* __restrict__ acts,
     float* __restrict__ c, float* __restrict__ h, int B, int R)
@@ -18,16 +18,9 @@ __global__ __launch_bounds__(THREADS) void lstm_gates_fwd_kernel(
     const int idx = blockIdx.x * THREADS + threadIdx.x;
     if (idx >= B * R) return;
     const int b = idx / R, u = idx % R;
-    const float* g = gp + (size_t)b * 4 * R;
-    const float si = air_sigmoid(g[u]);
-    const float tj = tanhf(g[R + u]);
-    const float sf = air_sigmoid(g[2 * R + u] + 1.0f);
-    const float so = air_sigmoid(g[3 * R + u]);
-    const float cn = c_prev[idx] * sf + si * tj;
-    float* a = acts + (size_t)b * 4 * R;
-    a[u] = si; a[R + u] = tj; a[2 * R + u] = sf; a[3 * R + u] = so;
-    c[idx] = cn;
-    h[idx] = tanhf(cn) * so;
+    const float* gr = gp + (size_t)b * 4 * R;
+    const float g[4] = {gr[u], gr[R + u], gr[2 * R + u], gr[3 * R + u]};
+    air_lstm_cell_fwd(g, c_prev[idx], acts + (size_t)b * 4 * R, c, h, nullptr, R, u, idx);
 }
 
 // The FIRST step of the recurrence: h_0 = c_0 = 0 (zero_state, air_model.py:540), so [x, h].K reduces to
@@ -70,15 +63,7 @@ __global__ __launch_bounds__(THREADS) void lstm_first_step_kernel(
         if (bias) s += bj[j];
         g[j] = s;
     }
-    const float si = air_sigmoid(g[0]), tj = tanhf(g[1]);
-    const float sf = air_sigmoid(g[2] + 1.0f), so = air_sigmoid(g[3]);
-    const float cn = 0.0f * sf + si * tj;
-    float* a = acts + (size_t)b * 4 * R;
-    a[u] = si; a[R + u] = tj; a[2 * R + u] = sf; a[3 * R + u] = so;
-    c[idx] = cn;
-    const float hn = tanhf(cn) * so;
-    h[idx] = hn;
-    if (h16) h16[idx] = air_bf16_of(hn);
+    air_lstm_cell_fwd(g, 0.0f, acts + (size_t)b * 4 * R, c, h, h16, R, u, idx);     // zero state: c' = 0*sigmoid(f + 1) + ...
 }
 
 __global__ __launch_bounds__(THREADS) void lstm_gates_bwd_kernel(
