@@ -833,6 +833,76 @@ int64_t air_histograms_output_bytes(const air_histogram_desc_t* descs, int count
 int64_t air_histograms_workspace_bytes(const air_histogram_desc_t* descs, int count);
 int air_histograms(const air_histograms_t* a, void* stream);
 
+/* ---- projector export (additive to ABI 6) ------------------------------------------------------------------------------
+ * The middle of the reference's embeddings.py: the ground truth of a test set matched to the objects the model inferred
+ * (embeddings.py:29-59, 86-114), the matched latents and windows gathered into dataset-level arrays, and the sprite sheet
+ * of the windows as matplotlib's grey levels (embeddings.py:117-131).  air/embeddings.py is the caller.
+ *
+ * Ground truth of digit g of image i: the integer top-left corner (x, y) = gt_positions[i][g], the box (w, h) =
+ * gt_boxes[i][g].  In fp64:  cx = (x + x + w - 1.0) / 2.0,  st_cx = cx / ((canvas_size - 1) / 2.0) - 1.0,  cy / st_cy alike
+ * (x + x + w is an int32 sum, as numpy forms it).
+ *
+ * Match, per image, its ground-truth digits in order: over the inferred objects t = 0 .. run_digits[i] - 1 (clamped to T)
+ *   dist = sqrt((x2 - x1) * (x2 - x1) + (y2 - y1) * (y2 - y1))     fp64; (x2, y2) = att[t][i][AIR_ATT_X, AIR_ATT_Y] widened
+ * keep the FIRST strict minimum below min_distance = 3.0; accept it when min_distance <= max_distance and no earlier digit
+ * of the image took that object.  A digit whose closest object is taken gets no second choice.  A digit of an image without
+ * inferred objects is never accepted (the reference's script would index an empty list there when max_distance >= 3).
+ * match[i][g] = the step t, or -1.
+ *
+ * Rows.  The accepted pairs of the chunk, in (image, digit) order, take the rows counters[AIR_EMBED_MATCHED] + 0, 1, ... of
+ * the four outputs: out_latents[row] = ml[t][i][0 .. Z) (the means: what rec_latents returns), out_windows[row] =
+ * vrec[t][i], out_labels / out_ids[row] = gt_labels / gt_ids[i][g].  A row >= capacity is not written; the call sets
+ * counters[AIR_EMBED_OVERFLOW] = 1 instead.  The call then advances the int32 counters, which live on the device across the
+ * chunks of a dataset (the caller zeroes them once): MATCHED (also the row cursor of the next chunk) by the accepted pairs,
+ * PRESENT by the sum of gt_count, INFERRED by the sum of run_digits over the k real images.
+ *
+ * k <= B: the last chunk of a dataset fills only its first k batch rows; the ground-truth arrays have k rows, padded to G
+ * digits per image (gt_count[i] <= G says how many are real).  Two launches (one workgroup that matches and scans, one
+ * workgroup per (image, digit) slot that copies), stream-ordered, no host read, no floating-point atomics; 16-byte copies
+ * where both rows are 16-byte aligned.  The same inputs give the same bits.
+ *
+ * AIR_EINVAL (before any HIP call): a null descriptor, pointer or workspace; T, B, k, G, Z, w or capacity < 1; k > B;
+ * canvas_size < 2; max_distance <= 0 (or NaN).  AIR_ELIMIT: T > AIR_EMBED_MAX_STEPS, G > AIR_EMBED_MAX_DIGITS, w > 256. */
+#define AIR_EMBED_MAX_STEPS 16
+#define AIR_EMBED_MAX_DIGITS 16
+enum { AIR_EMBED_MATCHED = 0, AIR_EMBED_PRESENT = 1, AIR_EMBED_INFERRED = 2, AIR_EMBED_OVERFLOW = 3, AIR_EMBED_COUNTERS = 4 };
+typedef struct {
+    const float* att;                    /* [T, B, AIR_ATT_STRIDE] of the inference pass                                */
+    const int32_t* run_digits;           /* [B] inferred object counts                                                  */
+    const float* ml;                     /* [T, B, 2 Z]: mean | log-variance                                            */
+    const float* vrec;                   /* [T, B, w * w] decoded windows                                               */
+    const int32_t* gt_count;             /* [k]                                                                         */
+    const int32_t* gt_positions;         /* [k, G, 2] (x, y)                                                            */
+    const int32_t* gt_boxes;             /* [k, G, 2] (w, h)                                                            */
+    const int32_t* gt_labels;            /* [k, G]                                                                      */
+    const int32_t* gt_ids;               /* [k, G]                                                                      */
+    int32_t* match;                      /* out [k, G]                                                                  */
+    int32_t* counters;                   /* in / out [AIR_EMBED_COUNTERS]                                               */
+    float* out_latents;                  /* [capacity, Z]                                                               */
+    float* out_windows;                  /* [capacity, w * w]                                                           */
+    int32_t* out_labels;                 /* [capacity]                                                                  */
+    int32_t* out_ids;                    /* [capacity]                                                                  */
+    int32_t T, B, k, G, Z, w, capacity, canvas_size;
+    double max_distance;
+} air_embed_collect_t;
+/* `workspace`: a device buffer of at least air_embed_collect_workspace_ints(T, B, k, G) int32 (the row of every slot) */
+int air_embed_collect(const air_embed_collect_t* args, void* workspace, void* stream);
+/* int32 elements of `workspace`, or AIR_EINVAL / AIR_ELIMIT for a (T, B, k, G) the entry point refuses -- no GPU is touched */
+int64_t air_embed_collect_workspace_ints(int T, int B, int k, int G);
+
+/* The sprite sheet of windows [M, w * w] as grey levels, uint8 plane [dim * w, dim * w], dim = ceil(sqrt(M))
+ * (air_embed_sprite_dim).  The fp64 sheet is 1.0 everywhere, tile i (column i % dim, row i / dim) has window i subtracted;
+ * lo and hi are its minimum and maximum (an empty tile's 1.0 included when dim * dim > M); then, as matplotlib's
+ * imsave(cmap='gray') does:  n = (v - lo) / (hi - lo) in fp64 (0 when hi == lo), index = min(int(n * 256), 255),
+ * grey = uint8(linspace(0, 1, 256)[index] * 255), truncating -- a 256-byte table that is not the identity.
+ * Two launches (per-workgroup min / max partials; fold + plane, four pixels per 32-bit store when dim * w is a multiple of
+ * 4).  workspace: 8-byte aligned, plane: 4-byte aligned (AIR_EALIGN).  AIR_EINVAL: M < 1 (the reference cannot save an empty
+ * sheet either), w < 1, a null pointer.  AIR_ELIMIT: M > 2^22, w > 256. */
+int air_embed_sprites(const float* windows, int M, int w, void* workspace, uint8_t* plane, void* stream);
+int air_embed_sprite_dim(int M);
+/* doubles of `workspace`, or AIR_EINVAL / AIR_ELIMIT -- no GPU is touched */
+int64_t air_embed_sprites_workspace_doubles(int M, int w);
+
 #ifdef __cplusplus
 }
 #endif

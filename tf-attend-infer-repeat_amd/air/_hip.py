@@ -181,6 +181,20 @@ class Histograms(C.Structure):
                 ("out", _p), ("workspace", _p), ("out_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
 
 
+MAX_EMBED_STEPS = MAX_EMBED_DIGITS = 16      # AIR_EMBED_MAX_STEPS, AIR_EMBED_MAX_DIGITS
+EMBED_MATCHED, EMBED_PRESENT, EMBED_INFERRED, EMBED_OVERFLOW, EMBED_COUNTERS = 0, 1, 2, 3, 4
+
+
+class EmbedCollect(C.Structure):
+    """air_embed_collect_t: one inference chunk of the projector export -- the model's buffers, the chunk's padded ground
+    truth, the dataset-level outputs and the device counters that carry the row cursor from chunk to chunk"""
+    _fields_ = [("att", _p), ("run_digits", _p), ("ml", _p), ("vrec", _p),
+                ("gt_count", _p), ("gt_positions", _p), ("gt_boxes", _p), ("gt_labels", _p), ("gt_ids", _p),
+                ("match", _p), ("counters", _p), ("out_latents", _p), ("out_windows", _p), ("out_labels", _p), ("out_ids", _p),
+                ("T", _i), ("B", _i), ("k", _i), ("G", _i), ("Z", _i), ("w", _i), ("capacity", _i), ("canvas_size", _i),
+                ("max_distance", C.c_double)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -247,6 +261,11 @@ _SIGNATURES = {
     "air_histograms_output_bytes": (C.c_int64, [C.POINTER(HistogramDesc), C.c_int]),
     "air_histograms_workspace_bytes": (C.c_int64, [C.POINTER(HistogramDesc), C.c_int]),
     "air_histograms": (C.c_int, [C.POINTER(Histograms), _p]),
+    "air_embed_collect": (C.c_int, [C.POINTER(EmbedCollect), _p, _p]),
+    "air_embed_collect_workspace_ints": (C.c_int64, [C.c_int] * 4),
+    "air_embed_sprites": (C.c_int, [_p, C.c_int, C.c_int, _p, _p, _p]),
+    "air_embed_sprite_dim": (C.c_int, [C.c_int]),
+    "air_embed_sprites_workspace_doubles": (C.c_int64, [C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

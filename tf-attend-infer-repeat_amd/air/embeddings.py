@@ -1,0 +1,167 @@
+"""Projector export -- the middle of the reference's embeddings.py (:29-131) on the device.
+
+``collect(model, *read_test_data(...))`` runs an inference ``AIRModel`` over a test set chunk by chunk and, after each
+forward, ONE call of air_embed_collect: the chunk's ground-truth digits are matched to the objects the model inferred
+(fp64, the reference's order of operations) and the latent and window of every matched object are copied from the model's
+own buffers (``att``, ``ml``, ``vrec``, ``run_digits``, where the forward left them) to the next free rows of four
+dataset-level arrays.  The row cursor and the three totals the reference prints live on the device; the chunks are
+stream-ordered and the host reads four integers once, after the last one.  Reconstructions and unmatched windows never
+leave the device.
+
+``sprite_sheet(windows)`` is create_mnist_sprites (:117-131) including matplotlib's ``imsave(cmap='gray')``: the grey levels
+of the sheet as a uint8 device tensor (air_embed_sprites).
+
+``write_projector(folder, result)`` writes what TensorBoard's embedding projector opens: metadata, sprite PNG, a checkpoint
+with the latents as variable ``air_mnist``, an event file and ``projector_config.pbtxt``.
+
+Eager only: like air.vae and air.cnn the functions refuse to run while the current stream is capturing (DESIGN.md section
+18.5).  There is no CPU fallback."""
+import ctypes as C
+import os
+
+import numpy as np
+import torch
+
+from . import _hip as H
+
+METADATA_FILE = "mnist_metadata.tsv"
+SPRITES_FILE = "mnist_sprites.png"
+CHECKPOINT_NAME = "embeddings"
+
+
+class Embeddings:
+    """latents [M, Z] float32, windows [M, w, w] float32, labels / ids [M] int32 of the matched digits, in (image, digit)
+    order; present / inferred / matched: the totals embeddings.py:190-192 prints; sprites: the uint8 sheet, once made"""
+
+    def __init__(self, latents, windows, labels, ids, present, inferred, matched, sprites=None):
+        self.latents, self.windows, self.labels, self.ids = latents, windows, labels, ids
+        self.present, self.inferred, self.matched = int(present), int(inferred), int(matched)
+        self.sprites = sprites
+
+
+def _padded(lists, counts, G, width):
+    out = np.zeros((len(lists), G, width), np.int32)
+    for i, n in enumerate(counts):
+        if n:
+            out[i, :n] = np.asarray(lists[i], np.int32)[:n * width].reshape(n, width)
+    return out
+
+
+def collect(model, images, digits, indices, positions, boxes, labels, max_distance=0.2):
+    """The six lists of multi_mnist.read_test_data -> Embeddings.  `model`: an inference AIRModel (train=False)."""
+    if getattr(model, "train", True):
+        raise ValueError("embeddings.collect: the model must be built with train=False")
+    dev = model.input_images.device
+    H.require_device(model.input_images, "the model's input buffer", "embeddings.collect", capture_too=True)
+    if not max_distance > 0:
+        raise ValueError("embeddings.collect: max_distance must be positive")
+    n, B, T = len(images), model.batch_size, model.max_steps
+    Z, w, D = model.vae_latent_dimensions, model.windows_size, model.canvas_size ** 2
+    if n < 1:
+        raise ValueError("embeddings.collect: no images")
+    counts = np.asarray(digits, np.int32).reshape(n)
+    G = max(1, int(counts.max()))
+    rc = H.lib().air_embed_collect_workspace_ints(T, B, B, G)
+    if rc < 0:
+        raise NotImplementedError("embeddings.collect: %d steps, %d digits in one image: the kernel holds %d and %d"
+                                  % (T, G, H.MAX_EMBED_STEPS, H.MAX_EMBED_DIGITS))
+    chunks = -(-n // B)
+    rows = chunks * B                              # the last chunk is padded with blank canvases without ground truth
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    flat = np.zeros((rows, D), np.float32)
+    for i, img in enumerate(images):
+        flat[i] = np.asarray(img, np.float32).reshape(-1)
+    gt_count = np.zeros(rows, np.int32)
+    gt_count[:n] = counts
+    pad = [()] * (rows - n)
+    gt = [up(a) for a in (gt_count, _padded(list(positions) + pad, gt_count, G, 2), _padded(list(boxes) + pad, gt_count, G, 2),
+                          _padded(list(labels) + pad, gt_count, G, 1), _padded(list(indices) + pad, gt_count, G, 1))]
+    canvases = up(flat)                            # uploaded once, like the ground truth
+
+    capacity = max(1, int(counts.sum()))           # every ground-truth digit matched: the rows cannot run out
+    out_latents = torch.empty(capacity, Z, dtype=torch.float32, device=dev)
+    out_windows = torch.empty(capacity, w * w, dtype=torch.float32, device=dev)
+    out_labels = torch.empty(capacity, dtype=torch.int32, device=dev)
+    out_ids = torch.empty(capacity, dtype=torch.int32, device=dev)
+    counters = torch.zeros(H.EMBED_COUNTERS, dtype=torch.int32, device=dev)
+    match = torch.empty(B, G, dtype=torch.int32, device=dev)
+    workspace = torch.empty(int(rc), dtype=torch.int32, device=dev)
+    for c in range(chunks):
+        lo, k = c * B, min(B, n - c * B)
+        model.input_images.copy_(canvases[lo:lo + B])
+        model.forward()
+        a = H.EmbedCollect(H.ptr(model.att), H.ptr(model.run_digits), H.ptr(model.ml), H.ptr(model.vrec),
+                           *(H.ptr(t[lo:lo + k]) for t in gt), H.ptr(match), H.ptr(counters),
+                           H.ptr(out_latents), H.ptr(out_windows), H.ptr(out_labels), H.ptr(out_ids),
+                           T, B, k, G, Z, w, capacity, model.canvas_size, float(max_distance))
+        H.launch("air_embed_collect", dev, C.byref(a), H.ptr(workspace))
+    total = counters.cpu().tolist()                # the one read-back
+    if total[H.EMBED_OVERFLOW]:
+        raise H.AirHipError("embeddings.collect: %d matched digits do not fit %d rows" % (total[H.EMBED_MATCHED], capacity))
+    M = total[H.EMBED_MATCHED]
+    return Embeddings(out_latents[:M], out_windows[:M].view(M, w, w), out_labels[:M], out_ids[:M],
+                      total[H.EMBED_PRESENT], total[H.EMBED_INFERRED], M)
+
+
+def sprite_sheet(windows):
+    """windows [M, w, w] (or [M, w * w]) float32 on the device -> uint8 [dim * w, dim * w], dim = ceil(sqrt(M))"""
+    H.require_device(windows, "windows", "embeddings.sprite_sheet", capture_too=True)
+    if windows.dim() not in (2, 3) or windows.dtype != torch.float32:
+        raise ValueError("embeddings.sprite_sheet: windows must be float32 [M, w, w] or [M, w * w]")
+    M = int(windows.shape[0])
+    w = int(windows.shape[1]) if windows.dim() == 3 else int(round(float(windows.shape[1]) ** 0.5))
+    if M < 1 or w < 1 or windows.numel() != M * w * w:
+        raise ValueError("embeddings.sprite_sheet: needs at least one square window (an empty sheet cannot be saved)")
+    n = H.lib().air_embed_sprites_workspace_doubles(M, w)
+    if n < 0:
+        raise NotImplementedError("embeddings.sprite_sheet: %d windows of %d x %d are beyond the kernel's limits" % (M, w, w))
+    dev, x = windows.device, windows.contiguous()
+    side = H.lib().air_embed_sprite_dim(M) * w
+    plane = torch.empty(side, side, dtype=torch.uint8, device=dev)
+    workspace = torch.empty(int(n), dtype=torch.float64, device=dev)
+    H.launch("air_embed_sprites", dev, H.ptr(x), M, w, H.ptr(workspace), H.ptr(plane))
+    return plane
+
+
+def _host(t):
+    return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+
+
+def projector_config(folder, name="air_mnist", window_size=28):
+    """the text ProjectorConfig prints for embeddings.py:207-214 (absolute paths, as the reference builds them)"""
+    folder = os.path.abspath(folder)
+    return ('embeddings {\n  tensor_name: "%s:0"\n  metadata_path: "%s"\n  sprite {\n    image_path: "%s"\n'
+            '    single_image_dim: %d\n    single_image_dim: %d\n  }\n}\n'
+            % (name, os.path.join(folder, METADATA_FILE), os.path.join(folder, SPRITES_FILE), window_size, window_size))
+
+
+def write_projector(folder, result, name="air_mnist"):
+    """Writes the files of embeddings.py:134-142, 201-222 into `folder`; returns their paths.  result.sprites is used when
+    set, otherwise the sheet is made on the device from result.windows."""
+    import tf_checkpoint
+    import tf_events
+    folder = os.path.abspath(folder)
+    os.makedirs(folder, exist_ok=True)
+    sheet = result.sprites if result.sprites is not None else sprite_sheet(result.windows)
+    result.sprites = sheet
+    latents = np.ascontiguousarray(_host(result.latents), dtype=np.float32)
+    paths = {k: os.path.join(folder, v) for k, v in (("metadata", METADATA_FILE), ("sprites", SPRITES_FILE),
+                                                     ("checkpoint", CHECKPOINT_NAME), ("state", "checkpoint"),
+                                                     ("config", "projector_config.pbtxt"))}
+    with open(paths["metadata"], "w") as f:
+        f.write("Index\tLabel\n")
+        for i, label in enumerate(_host(result.labels).tolist()):
+            f.write("%d\t%d\n" % (i, label))
+    with open(paths["sprites"], "wb") as f:
+        f.write(tf_events.encode_png(_host(sheet)))
+    tf_checkpoint.save_checkpoint(paths["checkpoint"], {name: latents})
+    with open(paths["state"], "w") as f:
+        f.write('model_checkpoint_path: "%s"\nall_model_checkpoint_paths: "%s"\n' % (paths["checkpoint"], paths["checkpoint"]))
+    writer = tf_events.EventFileWriter(folder)     # tf.summary.FileWriter(RESULTS_FOLDER): the version record alone
+    writer.close()
+    paths["events"] = writer.path
+    with open(paths["config"], "w") as f:
+        f.write(projector_config(folder, name, int(result.windows.shape[-1])))
+    return paths
