@@ -733,8 +733,9 @@ int air_reparam_bwd_plain(const float* d_z, const float* ml, const float* eps, c
  * air_model.py:510-533, the block in front of the LSTM when cnn=True, generalised from the 50 x 50 canvas to S x S:
  *   conv1 (5x5, stride 1, SAME, 1 -> F, + bias, ReLU) -> pool1 (2x2, stride 2, VALID: S1 = S / 2, an odd last row and column
  *   are dropped) -> conv2 (F -> F, ReLU) -> pool2 (S2 = S1 / 2) -> conv3 (F -> F, ReLU) -> [B, S2 * S2 * F], (y, x, channel).
- * fp32 throughout, NHWC tensors, kernels [5, 5, Cin, F] and biases [F] as tf.layers.conv2d stores them.  The train step
- * does not call these entry points (AIRModel(cnn=True) is not wired yet); they serve air/cnn.py of this package.
+ * fp32 throughout, NHWC tensors, kernels [5, 5, Cin, F] and biases [F] as tf.layers.conv2d stores them.  air/cnn.py calls
+ * air_cnn_fwd / air_cnn_bwd; the train step of AIRModel(cnn=True) calls air_cnn_fwd in front of x.Wx and air_cnn_bwd_sq
+ * behind the data gradient of x.Wx.
  *
  * Max-pool routing: the pooled value is the maximum of the four ReLU outputs of its window, its code 2 dy + dx names the
  * FIRST maximum in row-major window order (what TF's MaxPoolGrad and torch's CPU max_pool2d route the gradient to), one
@@ -777,6 +778,14 @@ int air_cnn_bwd(const air_cnn_bwd_t* args, void* stream);
 /* floats of `workspace` (the per-image partials of the six variable gradients), or AIR_EINVAL / AIR_ELIMIT for a
  * (B, S, F) the entry points refuse -- no GPU is touched */
 int64_t air_cnn_workspace_floats(int B, int S, int F);
+/* air_cnn_bwd whose batch reduction ALSO leaves sums of squares for the global-norm clip: workgroup i of the reduction
+ * writes sq_partials[i] = the sum of the squares of the gradient elements it stored (the last workgroup counts nothing
+ * past the last element), i in [0, air_cnn_num_sq_partials(F)).  The six gradients have the bits air_cnn_bwd gives; the
+ * sums are taken in a fixed order without atomics (the same inputs give the same bits), so air_adam_clip_step can read
+ * them behind air_wgrad_grouped's partials.  Errors as air_cnn_bwd, plus AIR_EINVAL for a null sq_partials. */
+int air_cnn_bwd_sq(const air_cnn_bwd_t* args, float* sq_partials, void* stream);
+/* how many floats air_cnn_bwd_sq writes: a function of F alone (AIR_EINVAL for F < 1, AIR_ELIMIT for F > 8); no GPU is touched */
+int air_cnn_num_sq_partials(int F);
 
 /* ---- histogram summaries (additive to ABI 6) --------------------------------------------------------------------------
  * tf.summary.histogram of the reference's variables and gradients (air_model.py:642-687, written by training.py:144-218):

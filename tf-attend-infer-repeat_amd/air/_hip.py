@@ -254,6 +254,8 @@ _SIGNATURES = {
     "air_cnn_fwd": (C.c_int, [C.POINTER(CnnFwd), _p]),
     "air_cnn_bwd": (C.c_int, [C.POINTER(CnnBwd), _p]),
     "air_cnn_workspace_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "air_cnn_bwd_sq": (C.c_int, [C.POINTER(CnnBwd), _p, _p]),
+    "air_cnn_num_sq_partials": (C.c_int, [C.c_int]),
     "air_histogram_num_buckets": (C.c_int, []),
     "air_histogram_limits": (C.c_int, [C.POINTER(C.c_double)]),
     "air_histogram_chunk": (C.c_int, []),

@@ -52,15 +52,31 @@ def reset_default_graph():
     _SCOPES.clear()
 
 
+def saved_cnn_arguments(path):
+    """dict(cnn=, cnn_filters=) of the model saved at `path` -- a torch.save'd state dict, or the prefix of a TensorFlow
+    bundle --, read off its conv variables (cnn/conv1/bias holds one element per filter).  cnn=False for a model saved
+    without the front-end, which is every checkpoint written before it existed."""
+    if os.path.exists(path + ".index"):
+        import tf_checkpoint as tfc
+        entry = tfc.read_index(path + ".index")[1].get(tfc.CNN_SCOPE + "conv1/bias")
+        filters = int(np.prod(entry["shape"])) if entry is not None else 0
+    else:
+        bias = torch.load(path, map_location="cpu").get("cnn/conv1/bias")
+        filters = int(np.prod(np.shape(bias))) if bias is not None else 0
+    return dict(cnn=filters > 0, cnn_filters=filters if filters > 0 else 8)
+
+
 def _align8(n):
     return (n + 7) & ~7
 
 
-def xavier_uniform_(variables, seed=0):
+def xavier_uniform_(variables, seed=0, rng=None):
     """Fills every 2-D tensor of the name -> tensor mapping with Glorot-uniform values, limit sqrt(6 / (fan_in + fan_out)), from
-    ONE numpy stream seeded by `seed`, in the mapping's order (layers.xavier_initializer, the TF 1.3 default of
-    fully_connected and BasicLSTMCell); 1-D tensors (biases: zeros) are left alone."""
-    rng = np.random.RandomState(seed)
+    ONE numpy stream seeded by `seed` (or the stream `rng`, continued), in the mapping's order (layers.xavier_initializer, the
+    TF 1.3 default of fully_connected and BasicLSTMCell); 1-D tensors (biases: zeros) are left alone, and so are the 4-D
+    conv kernels (VariableStore.initialize draws them)."""
+    if rng is None:
+        rng = np.random.RandomState(seed)
     with torch.no_grad():
         for v in variables.values():
             if v.dim() == 2:
@@ -81,17 +97,27 @@ class VariableStore:
         R, Z = hp["rnn_units"], hp["vae_latent_dimensions"]
         Hs, Hh, Hz = hp["scale_hidden_units"], hp["shift_hidden_units"], hp["z_pres_hidden_units"]
         HT, Hmax = 2 * Hs + 2 * Hh + Hz, max(Hs, Hh, Hz)
-        self.dims = dict(D=D, d=d, R=R, Z=Z, Hs=Hs, Hh=Hh, Hz=Hz, HT=HT, Hmax=Hmax)
+        # the LSTM's input: the canvas, or the [S // 4, S // 4, F] output of the conv front-end (reference :510-535)
+        cnn, F = bool(hp.get("cnn", False)), int(hp.get("cnn_filters", 0))
+        Din = (hp["canvas_size"] // 4) ** 2 * F if cnn else D
+        self.dims = dict(D=D, d=d, R=R, Z=Z, Hs=Hs, Hh=Hh, Hz=Hz, HT=HT, Hmax=Hmax, Din=Din)
         self.vae_layers = VaeLayers(d, hp["vae_recognition_units"], Z, hp["vae_generative_units"])
 
         fused = OrderedDict()           # fused device tensors: name -> shape
-        fused["lstm_kernel"] = (D + R, 4 * R)
+        fused["lstm_kernel"] = (Din + R, 4 * R)
         fused["lstm_bias"] = (4 * R,)
         fused["whid"] = (R, HT)
         fused["bhid"] = (HT,)
         fused["wout"] = (7, Hmax)
         fused["bout"] = (8,)
         fused.update(self.vae_layers.shapes())
+        # the conv variables BEHIND every other entry: the offsets of a cnn=False store are those of every earlier build
+        self.cnn_names = []
+        if cnn:
+            from .cnn import CNN
+            self.cnn_names = CNN.variable_names()
+            for i, name in enumerate(self.cnn_names):
+                fused[name] = (5, 5, (1 if i < 2 else F), F) if i % 2 == 0 else (F,)
 
         self.offsets = OrderedDict()
         off = 0
@@ -121,7 +147,8 @@ class VariableStore:
         # panels (the four gates of four units in 32 contiguous bytes per row), in two pieces (Wx rows, Wh rows).
         # Maintained by Adam next to the row-major shadow (which the transposed data-gradient products keep reading);
         # Wx has no other reader than the hoisted x.Wx, so its row-major shadow is dropped ("exclusive") unless the
-        # canvas is large (the throughput tiling of D > 4096 reads row-major lines) or the shape cannot fuse the first step.
+        # canvas is large (the throughput tiling of D > 4096 reads row-major lines) or the shape cannot fuse the first step --
+        # or the conv front-end is on: the data gradient d rnn_input = dgsum . Wx^T reads the row-major shadow of Wx.
         pan, poff = [], 0
         self.panel_off = {}
 
@@ -135,9 +162,9 @@ class VariableStore:
         o = self.offsets["lstm_kernel"]
         # (its one reader is the x.Wx launch that also runs the first step -- which needs D % 4 == 0 and R % 4 == 0: a shape that
         # cannot fuse keeps the row-major shadow of Wx; the throughput tiling of a large canvas reads row-major lines: no panel)
-        if D <= 4096 and D % 4 == 0 and R % 4 == 0:
-            add_panel("Wx", o, D, 4 * R, True, exclusive=True)
-        add_panel("Wh", o + D * 4 * R, R, 4 * R, True)
+        if Din <= 4096 and Din % 4 == 0 and R % 4 == 0:
+            add_panel("Wx", o, Din, 4 * R, True, exclusive=not cnn)
+        add_panel("Wh", o + Din * 4 * R, R, 4 * R, True)
         for k, shp in fused.items():
             if k.endswith("_w") and k not in ("ml_w", "gen0_w") or k == "whid":
                 add_panel(k, self.offsets[k], shp[0], shp[1], False)
@@ -171,6 +198,8 @@ class VariableStore:
                 o[head + "/output/biases"] = V["bout"][r0:r1]
                 seg += wid
             o.update(self.vae_layers.tf_views(V))
+            for name in self.cnn_names:                  # scope cnn/ sits beside rnn/ (reference :511 against :537)
+                o[name] = V[name]
             return o
         self.variables = named(self.P)
         self.gradients = named(self.G)
@@ -183,7 +212,14 @@ class VariableStore:
         BasicLSTMCell / layers.fully_connected (limits sqrt(6/(in+out)) as in
         air-model.meta's initializer constants); zero Adam slots, step 0."""
         self.params.zero_()
-        xavier_uniform_(self.variables, seed)
+        rng = np.random.RandomState(seed)
+        # the reference creates the conv layers first (:511-533): their kernels come first from the store's one stream,
+        # Glorot-uniform over fan_in = 25 Cin, fan_out = 25 F (tf.layers.conv2d's default), zero biases
+        for name in self.cnn_names[::2]:
+            k = self.variables[name]
+            limit = math.sqrt(6.0 / (25 * k.shape[2] + 25 * k.shape[3]))
+            k.copy_(torch.from_numpy(rng.uniform(-limit, limit, size=tuple(k.shape)).astype(np.float32)))
+        xavier_uniform_(self.variables, rng=rng)
         self.m.zero_(); self.v.zero_(); self.grads.zero_(); self.istate.zero_()
         self.shadow_stale = True
 
@@ -368,13 +404,16 @@ class AIRModel:
                  vae_prior_mean=0.0, vae_prior_variance=1.0, vae_likelihood_std=0.3,
                  scale_hidden_units=64, shift_hidden_units=64, z_pres_hidden_units=64,
                  z_pres_prior_log_odds=-2.0, z_pres_temperature=1.0, stopping_threshold=0.99,
-                 learning_rate=1e-3, gradient_clipping_norm=100.0, cnn=True, cnn_filters=8,
+                 learning_rate=1e-3, gradient_clipping_norm=100.0, cnn=None, cnn_filters=8,
                  num_summary_images=60, train=False, reuse=False, scope="air",
                  annealing_schedules=None, seed=0, gemm_precision=None, backward="reference", noise_seed=None,
                  bf16_twins=None, dp_exchange=None, xw_tile=None, xwx_twin_staging="lds_dma", step0_fusion=None):
-        if cnn:
-            # reference :510-533; every caller passes cnn=False (training.py:108, demo.py:24)
-            raise NotImplementedError("cnn=True front-end is outside the accelerated hot path; pass cnn=False")
+        if cnn is None:
+            # The reference's default is cnn=True (:21) and every caller of the reference passes cnn=False.  A call that leaves
+            # `cnn` out has always been refused here, and still is: which LSTM input a model has (and with it the layout of
+            # its variables and checkpoints) is chosen by the caller, not met by accident.  cnn=True builds the front-end.
+            raise NotImplementedError("pass cnn explicitly: cnn=True (the reference's default: the conv front-end in front of the "
+                                      "LSTM) or cnn=False (what the reference's training.py, demo.py and embeddings.py pass)")
         if not (torch.is_tensor(input_images) and input_images.is_cuda):
             raise H.AirHipError("input_images must be a CUDA/HIP device tensor: this path has no CPU fallback")
         self.lib = H.lib()
@@ -393,6 +432,16 @@ class AIRModel:
         for name, val, cap, why in limits:
             if val > cap:
                 raise NotImplementedError("%s = %d exceeds the HIP path's limit of %d (%s)" % (name, val, cap, why))
+        cnn = bool(cnn)
+        if cnn:
+            # the conv front-end (reference :510-533): the limits of its kernels, as the library answers them
+            rc = self.lib.air_cnn_workspace_floats(self.batch_size, int(canvas_size), int(cnn_filters))
+            if rc == -2:
+                raise NotImplementedError("cnn=True: canvas_size = %d with cnn_filters = %d exceeds the HIP path's limits (cnn_filters "
+                                          "<= 8; canvas_size <= 77 at 8 filters .. <= 128 at 1 or 2: the planes of an image live "
+                                          "in LDS)" % (canvas_size, cnn_filters))
+            if rc < 0:
+                raise ValueError("cnn=True needs canvas_size >= 4 and cnn_filters >= 1, got %d and %d" % (canvas_size, cnn_filters))
 
         self.max_steps = max_steps
         self.max_digits = max_digits
@@ -423,7 +472,7 @@ class AIRModel:
         self.train = train
         self.scope = scope
         self.annealing_schedules = annealing_schedules
-        self.rnn_input = self.input_images            # reference :535
+        self.rnn_input = self.input_images            # reference :535 (cnn=True: the conv block's output, _alloc)
         # (the reference's var_summaries / grad_summaries lists of summary ops are the methods of that name here)
         self.num_summaries, self.img_summaries = [], []
         self._hist_plans = {}
@@ -464,6 +513,12 @@ class AIRModel:
         self._xw_tile_arg = xw_tile
         self._step0_fusion_arg = step0_fusion
         # (before the variables exist: a refused shape leaves no variable scope behind)
+        self._dp_exchange = dp_exchange or os.environ.get("AIR_DP_EXCHANGE", "flat")
+        if self._dp_exchange not in ("flat", "factors"):
+            raise ValueError("dp_exchange must be 'flat' or 'factors'")
+        if cnn and self._dp_exchange == "factors":
+            # (the factors of dWx would be rnn_input and sum_t dgates; the conv gradients would still need the all-reduce)
+            raise NotImplementedError("dp_exchange='factors' is not implemented for cnn=True; use dp_exchange='flat'")
         self._check_lds((self._schedule[:2] if self._schedule else (backward,)) if train else ())
 
         dev = input_images.device
@@ -479,7 +534,7 @@ class AIRModel:
                   vae_latent_dimensions=vae_latent_dimensions,
                   vae_recognition_units=self.vae_recognition_units, vae_generative_units=self.vae_generative_units,
                   scale_hidden_units=scale_hidden_units, shift_hidden_units=shift_hidden_units,
-                  z_pres_hidden_units=z_pres_hidden_units)
+                  z_pres_hidden_units=z_pres_hidden_units, cnn=cnn, cnn_filters=int(cnn_filters) if cnn else 0)
         # tf.variable_scope(scope, reuse=reuse), reference :68
         if reuse:
             if scope not in _SCOPES:
@@ -503,9 +558,6 @@ class AIRModel:
         # the gradient elements, rank <= B per GPU -- is never reduced: its FACTORS (X and sum_t dgates, 0.9 MB per
         # rank) are all-gathered and every rank contracts the gathered rows itself; only the other 36 % is
         # all-reduced.  Same sum up to the fp32 order of the contraction (tests/test_gpu_dp.py).
-        self._dp_exchange = dp_exchange or os.environ.get("AIR_DP_EXCHANGE", "flat")
-        if self._dp_exchange not in ("flat", "factors"):
-            raise ValueError("dp_exchange must be 'flat' or 'factors'")
         self._dp_factor_ops = None
         # test hook: run the data-parallel protocol (gradient exchange + separate norm pass + Adam) on a process group of
         # ONE rank -- all a 1-GPU box can give RCCL -- so that its captured form is exercised on hardware
@@ -540,6 +592,7 @@ class AIRModel:
         dm = st.dims
         B, N = self.batch_size, self.max_steps
         D, d, R, Z, HT = dm["D"], dm["d"], dm["R"], dm["Z"], dm["HT"]
+        Din = dm["Din"]                                      # the LSTM's input width: D, or the conv block's output
         f, h16 = self._f32, self._i16
 
         # dynamic scalars + annealing table (reference :76-82, 94-121)
@@ -589,8 +642,8 @@ class AIRModel:
         # 0.1968 ms per step against 8 slabs), 64x32 for the 128x128 canvases (0.923 -> 0.898 ms) -- measured sweeps
         # (bf16 twins, large canvases: 64x64 tiles -- the image batch is re-read by 16 instead of 32 column tiles and the
         # row-major Wx shadow is fetched in whole 128-byte lines: [256x1024x16384] 59.6 -> 42.2 us, tools/exp/gemm_twin_bench.py)
-        self._xw_ksplit, self._xw_tile = 4, ((2, 2) if D <= 4096 else ((4, 4) if self._twins else (4, 2)))
-        if self._twins and D > 4096 and B % 64 == 0 and R % 16 == 0 and D % 512 == 0:
+        self._xw_ksplit, self._xw_tile = 4, ((2, 2) if Din <= 4096 else ((4, 4) if self._twins else (4, 2)))
+        if self._twins and Din > 4096 and B % 64 == 0 and R % 16 == 0 and Din % 512 == 0:
             # full batches of a large canvas: the throughput tiling (64 x 64 per workgroup, 8 K-slabs), gemm_xw_tp_kernel
             self._xw_ksplit, self._xw_tile = 8, (8, 4)
         xw_tile = self._xw_tile_arg
@@ -604,9 +657,9 @@ class AIRModel:
         # (VariableStore.panels) the tile's rows are 32 contiguous bytes: default for the bf16 path now (and for its
         # twins-off form, so that the two stay bit-identical); the fp32 path keeps the split-K product.
         # AIRModel(step0_fusion=False / True) forces it off / on, where the shape allows it.
-        want0 = (self._prec == 1 and D <= 4096) if self._step0_fusion_arg is None else bool(self._step0_fusion_arg)
-        self._fuse_step0 = want0 and R % 4 == 0 and D % 4 == 0 and xw_tile is None
-        self._xw_slabs = 1 if self._fuse_step0 else self.lib.air_gemm_slabs(D, self._xw_ksplit)
+        want0 = (self._prec == 1 and Din <= 4096) if self._step0_fusion_arg is None else bool(self._step0_fusion_arg)
+        self._fuse_step0 = want0 and R % 4 == 0 and Din % 4 == 0 and xw_tile is None
+        self._xw_slabs = 1 if self._fuse_step0 else self.lib.air_gemm_slabs(Din, self._xw_ksplit)
         self.xw = f(self._xw_slabs, B, 4 * R)            # x.Wx (split-K slabs when not fused)
         self.gates_pre = f(B, 4 * R)
         self.acts = f(N, B, 4 * R)
@@ -646,12 +699,14 @@ class AIRModel:
             self.d_hid16 = h16(N, B, HT)
             self.dgates16 = h16(N, B, 4 * R)
             self.dgsum16 = h16(B, 4 * R)
-            # twin of the image batch (the caller's fp32 tensor): written by the step prologue, read by the input-weight gradient
-            self.images16 = h16(B, D)
+            # twin of the LSTM's input (the caller's fp32 image batch, or rnn_input): written by the step prologue, read by the
+            # input-weight gradient
+            self.images16 = h16(B, Din)
             # a SECOND twin of the batch with rows padded to a multiple of 8 elements (every row 16-byte aligned, pad
             # columns zero): side output of the fp32-operand x.Wx launch, A operand of the x.Wx launches that follow it
             # inside one captured replay (capture_graph)
-            self.images16p = h16(B, (D + 7) & ~7)
+            # (not with the conv front-end: the LSTM's input is recomputed by every step)
+            self.images16p = None if self.cnn else h16(B, (Din + 7) & ~7)
         if self.train:
             self.d_recon = f(B, D)
             self.d_genpre = f(N, B, d)
@@ -667,6 +722,18 @@ class AIRModel:
             self.dc = [f(B, R), f(B, R)]
             self.dgates = f(N, B, 4 * R)
             self.dgsum = f(B, 4 * R)
+        if self.cnn:
+            # the conv front-end (reference :510-533): its output is the LSTM's input; a train model keeps what the backward
+            # reads (the pooled planes and their argmax codes) and the per-image partials of the six gradients
+            S, F = self.canvas_size, self.cnn_filters
+            self.rnn_input = f(B, Din)
+            self._cnn_saved = (None,) * 4
+            if self.train:
+                u8 = lambda *shape: torch.zeros(*shape, dtype=torch.uint8, device=dv)
+                S1, S2 = S // 2, S // 4
+                self._cnn_saved = (f(B, S1, S1, F), f(B, S2, S2, F), u8(B, S1, S1, F), u8(B, S2, S2, F))
+                self._cnn_ws = f(int(self.lib.air_cnn_workspace_floats(B, S, F)))
+                self.d_rnn_input = f(B, Din)
 
     # ------------------------------------------------------------- launch lists
     def _gemm(self, A, Bm, Cm, M, N, K, lda, ldb, ldc, ta=0, tb=0, bias=None, addend=None, ldadd=0,
@@ -699,6 +766,7 @@ class AIRModel:
                   "air_grad_sqnorm": "grad_sqnorm_kernel", "air_adam_clip_step": "adam_clip_kernel",
                   "air_adam_clip_step_panels": "adam_panels_kernel", "air_scene_records": "scene_records_kernel",
                   "air_render": "render_kernel", "air_philox_fill": "philox_fill_kernel"}
+    # (air_cnn_fwd: cnn_fwd_kernel<F>; air_cnn_bwd_sq is two launches, cnn_bwd_kernel<F> and cnn_reduce_sq_kernel: _call)
 
     def _call(self, name, *args, nbytes=0, flops=0, tag=None):
         fn = getattr(self.lib, name)
@@ -709,6 +777,8 @@ class AIRModel:
             kernel = "bottleneck_%s_kernel<256, %s>" % (name[-3:], "true" if self._twins else "false")
         if name == "air_wgrad_grouped":
             kernel = "wgrad_grouped_bf16_kernel" if self._prec else "wgrad_grouped_kernel"
+        if name in ("air_cnn_fwd", "air_cnn_bwd_sq"):        # (the backward's second launch is cnn_reduce_sq_kernel)
+            kernel = "cnn_%s_kernel<%d>" % (name[8:11], self.cnn_filters)
         return _Op(tag or name, lambda s, fn=fn, args=args, name=name: H.check(fn(*args, s), name),
                    nbytes=nbytes, flops=flops, kernel=kernel)
 
@@ -723,9 +793,9 @@ class AIRModel:
 
     def _lstm_weights(self):
         """(Wx, Wh, Wx16, Wh16): the input and the recurrent rows of the LSTM kernel and of its row-major bf16 shadow"""
-        D, K = self.store.dims["D"], self.store.P["lstm_kernel"]
+        Din, K = self.store.dims["Din"], self.store.P["lstm_kernel"]
         K16 = self._T("lstm_kernel")
-        return (K[:D], K[D:]) + ((K16[:D], K16[D:]) if K16 is not None else (None, None))
+        return (K[:Din], K[Din:]) + ((K16[:Din], K16[Din:]) if K16 is not None else (None, None))
 
     def _generative_ops(self, x, x16, act, act16, out, eps_x, aux_scale, first=0):
         """The generative layers from index `first` on and gen_mean (vae.py:26-41), reading x (twin x16), the input of layer
@@ -766,12 +836,22 @@ class AIRModel:
         Cc, w = self.canvas_size, self.windows_size
         tw, T, TP = self._twins, self._T, self._TP
         Wx, Wh, Wx16, Wh16 = self._lstm_weights()
-        imgs = self.input_images
+        imgs = self.input_images                # the canvas side: attend, compose
+        xin, Din = self.rnn_input, dm["Din"]    # the LSTM side: the same tensor unless the conv front-end is on
         keep = self._keep
 
         NB = N * B
         fwd = []
         self._xwx_twin_op = None
+        # the conv front-end, an op of its own IN FRONT of the list (self._fwd[0] stays the x.Wx launch): fp32 in both precisions
+        self._cnn_fwd = None
+        if self.cnn:
+            S, F = self.canvas_size, self.cnn_filters
+            cv = [P[k] for k in st.cnn_names]
+            cf = H.CnnFwd(_ptr(imgs), *[_ptr(v) for v in cv], _ptr(xin), *[_ptr(t) for t in self._cnn_saved], B, S, F)
+            keep.append(cf)
+            self._cnn_fwd = self._call("air_cnn_fwd", C.byref(cf), nbytes=4 * (B * (D + Din) + sum(v.numel() for v in cv)),
+                                       flops=2 * 25 * B * F * (S * S + F * ((S // 2) ** 2 + (S // 4) ** 2)), tag="cnn_fwd")
         if self._gen is not None:
             self._gen["ops"] = None             # (the generation launch list is rebuilt with these; its buffers stay)
 
@@ -780,8 +860,8 @@ class AIRModel:
         # hoisted x.W_x (the reference recomputes it every step, :286); split-K slabs
         job = H.StepJob(_ptr(self.sched), self._nsched, _ptr(self.dyn), _ptr(st.istate),
                         _ptr(self.normals), self.normals.numel(), _ptr(self.uniforms), self.uniforms.numel(),
-                        self._seed, _ptr(imgs if self.images16 is not None else None), _ptr(self.images16),
-                        imgs.numel() if self.images16 is not None else 0)
+                        self._seed, _ptr(xin if self.images16 is not None else None), _ptr(self.images16),
+                        xin.numel() if self.images16 is not None else 0)
         noise_bytes = 4 * (self.normals.numel() + self.uniforms.numel())
         if tw and st.wx_exclusive and not self._fuse_step0:
             # the store keeps ONLY the panel twin of Wx (VariableStore: "exclusive"), and this model cannot read it: its
@@ -802,24 +882,26 @@ class AIRModel:
             # Only the bf16-twin kernel of this launch writes the twin, and only it has the twin-operand form (R % 8 == 0, a
             # 16-byte aligned batch, ...: twin_rounds in csrc/air_gemm_bf16.hip).  The library is asked, not second-guessed:
             # the plain descriptor is built first, and the twin is offered only where THAT dispatches to the twin kernel.
-            op0 = self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R, tag="xWx+lstm0", **step0)
-            if wx_pan is not None and self.train and op0.kernel.startswith("gemm_bf16tw_kernel<1, 1, false, %d, true," % H.EPI_LSTM_FWD0):
+            op0 = self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, tag="xWx+lstm0", **step0)
+            # (not with the conv front-end: its output changes with every step of a replay, so no step may read a twin an
+            # earlier step left behind -- every x.Wx launch is the fp32-operand one)
+            if wx_pan is not None and self.train and not self.cnn and op0.kernel.startswith("gemm_bf16tw_kernel<1, 1, false, %d, true," % H.EPI_LSTM_FWD0):
                 x16p = self.images16p
-                op0 = self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R, tag="xWx+lstm0", C16=x16p, **step0)
-                self._xwx_twin_op = self._gemm(imgs, Wx, self.xw, B, 4 * R, D, x16p.shape[1], 4 * R, 4 * R, tag="xWx16+lstm0",
+                op0 = self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, tag="xWx+lstm0", C16=x16p, **step0)
+                self._xwx_twin_op = self._gemm(xin, Wx, self.xw, B, 4 * R, Din, x16p.shape[1], 4 * R, 4 * R, tag="xWx16+lstm0",
                                                A16=x16p, i0=(3 if self._xwx_twin_staging == "registers" else 2), **step0)
             fwd.append(op0)
             step0["extra_bytes"] += noise_bytes
-            self._begin_host = (0, self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R,
+            self._begin_host = (0, self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R,
                                               tag="xWx+lstm0+step_begin", step_job=job, **step0))
         else:
             if st.wx_exclusive:
                 Wx16 = None         # (the row-major shadow of Wx is not maintained on this scope: fp32 operand)
-            fwd.append(self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R, ksplit=self._xw_ksplit,
+            fwd.append(self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, ksplit=self._xw_ksplit,
                                   tile=self._xw_tile, tag="xWx", B16=Wx16))
             # the same launch carrying the step prologue (schedules + Philox noise) as an extra plane of
             # workgroups: x.Wx reads neither, so the train step needs no prologue launch of its own
-            self._begin_host = (0, self._gemm(imgs, Wx, self.xw, B, 4 * R, D, D, 4 * R, 4 * R, ksplit=self._xw_ksplit,
+            self._begin_host = (0, self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, ksplit=self._xw_ksplit,
                                               tile=self._xw_tile, tag="xWx+step_begin", step_job=job,
                                               extra_bytes=noise_bytes, B16=Wx16))
             # step 0 starts from zero_state (:540): h_0 . Wh = 0, the gates are x.Wx + b -- a pointwise launch
@@ -899,7 +981,7 @@ class AIRModel:
                                     _ptr(self.target_num_digits), _ptr(self.run_digits), _ptr(self._loss_item),
                                     _ptr(self.scalars), B)
         self._fwd = fwd
-        twin_job = ((_ptr(imgs), _ptr(self.images16), imgs.numel()) if self.images16 is not None else (None, None, 0))
+        twin_job = ((_ptr(xin), _ptr(self.images16), xin.numel()) if self.images16 is not None else (None, None, 0))
         self._begin_sched_only = self._call(
             "air_step_begin", _ptr(self.sched), self._nsched, _ptr(self.dyn), _ptr(st.istate),
             None, 0, None, 0, C.c_uint64(self._seed), *twin_job)
@@ -915,8 +997,8 @@ class AIRModel:
         st, G, L = self.store, self.store.G, self.store.vae_layers
         dm = st.dims
         B, NB = self.batch_size, self.max_steps * self.batch_size
-        D, R, HT = dm["D"], dm["R"], dm["HT"]
-        Gx, Gh = G["lstm_kernel"][:D], G["lstm_kernel"][D:]
+        Din, R, HT = dm["Din"], dm["R"], dm["HT"]
+        Gx, Gh = G["lstm_kernel"][:Din], G["lstm_kernel"][Din:]
         probs = []
 
         def wg(A, dY, dW, db, M, Nn, K, A16=None, dY16=None, lda=None):
@@ -938,7 +1020,7 @@ class AIRModel:
                              head_pack=1, Hs=dm["Hs"], Hh=dm["Hh"], Hz=dm["Hz"]))
         # the input-weight gradient contracts over B rows only (sum_t dgates): its many light
         # workgroups go LAST so that they fill the tail of the launch behind the K = N*B ones
-        wg(self.input_images, self.dgsum, Gx, G["lstm_bias"], D, 4 * R, B, self.images16, self.dgsum16)
+        wg(self.rnn_input, self.dgsum, Gx, G["lstm_bias"], Din, 4 * R, B, self.images16, self.dgsum16)
         assert len(probs) == _NON_VAE_WGRAD_PROBLEMS + len(L.products()) <= H.MAX_WGRAD_PROBLEMS      # (constructor: the limit)
         arr = (H.Wgrad * len(probs))(*probs)
         self._keep.append(arr)
@@ -955,8 +1037,13 @@ class AIRModel:
         self._wgrad_blocks = self.lib.air_wgrad_num_blocks(arr, len(probs))
         if self._wgrad_blocks <= 0:
             H.check(self._wgrad_blocks, "air_wgrad_num_blocks")
-        if st.partials.numel() < self._wgrad_blocks:
-            raise NotImplementedError("weight-gradient launch of %d workgroups exceeds the partial-sum buffer" % self._wgrad_blocks)
+        # (the conv gradients come from a launch of their own: its partials sit directly behind this launch's)
+        self._cnn_sq = self.lib.air_cnn_num_sq_partials(self.cnn_filters) if self.cnn else 0
+        if self._cnn_sq < 0:
+            H.check(self._cnn_sq, "air_cnn_num_sq_partials")
+        if st.partials.numel() < self._wgrad_blocks + self._cnn_sq:
+            raise NotImplementedError("weight-gradient launch of %d workgroups%s exceeds the partial-sum buffer"
+                                      % (self._wgrad_blocks, " + %d of the conv gradients" % self._cnn_sq if self.cnn else ""))
         # (Adam rebuilding dWx = X^T.(sum_t dgates) from its factors instead of reading the stored 10 MB -- bit-identical, the
         # tiles rebuilt inside Adam cost ~7 us against ~1 us saved in this launch -- was an option until round 5: removed)
         self._wgrad_fused = self._call("air_wgrad_grouped", arr, len(probs), self._prec, _ptr(st.partials),
@@ -1052,6 +1139,19 @@ class AIRModel:
                                   extra_bytes=4 * B * R * 15, tag="bptt_lstm_bwd",
                                   A16=_row16(self.dgates16, t + 1), B16=Wh16, q0_16=_row16(self.dgates16, t),
                                   q2_16=(self.dgsum16 if t == 0 else None)))
+        if self.cnn:
+            # dgsum = sum_t dgates is complete: d loss / d rnn_input = dgsum . Wx^T (the row-major shadow of Wx on the twin path),
+            # then the conv block's backward straight into the flat gradient buffer, with its global-norm partials
+            Wx, _, Wx16, _ = self._lstm_weights()
+            Din, S, F = dm["Din"], self.canvas_size, self.cnn_filters
+            bwd.append(self._gemm(self.dgsum, Wx, self.d_rnn_input, B, Din, 4 * R, 4 * R, 4 * R, Din, tb=1,
+                                  tag="dgrad_rnn_input", A16=self.dgsum16, B16=Wx16))
+            cv, cg = [P[k] for k in st.cnn_names], [st.G[k] for k in st.cnn_names]
+            cb = H.CnnBwd(_ptr(self.d_rnn_input), _ptr(self.rnn_input), _ptr(imgs), *[_ptr(t) for t in self._cnn_saved],
+                          _ptr(cv[0]), _ptr(cv[2]), _ptr(cv[4]), _ptr(self._cnn_ws), *[_ptr(g) for g in cg], None, B, S, F)
+            keep.append(cb)
+            bwd.append(self._call("air_cnn_bwd_sq", C.byref(cb), _ptr(st.partials[self._wgrad_blocks:]),
+                                  nbytes=4 * (B * (D + 2 * Din) + (B + 1) * sum(g.numel() for g in cg)), tag="cnn_bwd"))
         self._bwd = bwd
 
     # ------------------------------------------------------------------ running
@@ -1149,6 +1249,8 @@ class AIRModel:
             if self._xwx_twin_op is None:
                 raise RuntimeError("this model has no twin-operand x.Wx launch")
             fwd = [self._xwx_twin_op] + fwd[1:]
+        if self._cnn_fwd is not None:
+            self._cnn_fwd(s)                         # (first: x.Wx and the prologue's bf16 twin read its output)
         if self._injected_noise:
             self._begin_sched_only(s)                # (parity tests: the schedules only, the noise buffers hold what was injected)
             run = list(fwd)
@@ -1207,7 +1309,7 @@ class AIRModel:
         if self._opt_world != (world, self._dp()):
             st = self.store
             fused = not self._dp()
-            npart = self._wgrad_blocks if fused else self.lib.air_optim_num_partials(st.n)
+            npart = self._wgrad_blocks + self._cnn_sq if fused else self.lib.air_optim_num_partials(st.n)
             if self._twins and len(st.panels):
                 # (with the panels whether or not THIS model reads them: another model on the scope may)
                 adam = self._call("air_adam_clip_step_panels", _ptr(st.params), _ptr(st.grads), _ptr(st.m), _ptr(st.v),
@@ -1291,7 +1393,8 @@ class AIRModel:
         """The launches of one single-GPU train step, in order (bench / profiling tools): the EAGER step, whose x.Wx reads
         the caller's fp32 image batch.  Steps 1 .. G-1 of a captured G-step replay without a between_steps hook run the same
         list with the twin-operand x.Wx launch (gemm_xwx_glds_kernel, captured_xwx_kernels()) in its first place."""
-        return self._fwd_with_prologue() + [self._write_bwd_fin] + self._bwd[1:] + [self._wgrad_fused] + self._optimizer_ops()
+        return ([self._cnn_fwd] if self._cnn_fwd is not None else []) + self._fwd_with_prologue() + [self._write_bwd_fin] + \
+            self._bwd[1:] + [self._wgrad_fused] + self._optimizer_ops()
 
     def captured_xwx_kernels(self):
         """Kernel name of the x.Wx launch of every step of the captured replay, in order (None: no train graph): the names
@@ -1358,6 +1461,8 @@ class AIRModel:
         # leaves its padded bf16 twin behind; nothing inside the graph writes the batch unless a between_steps hook does, so
         # the steps behind it read the twin: half the A bytes of x.Wx, both operands by LDS-DMA.  (Not where the x.Wx launch
         # itself carries the step prologue -- max_steps == 1: that launch is the fp32-operand one.)
+        # (Nor with the conv front-end, whose model builds no twin-operand launch: Adam moves the conv variables, so the LSTM's
+        # input differs from step to step.)
         can_twin = between_steps is None and self._xwx_twin_op is not None and self._begin_host[0] != 0
         xwx = []
         ga = torch.cuda.CUDAGraph()
@@ -1638,16 +1743,23 @@ class AIRModel:
         from .summaries import summary_tags
         return summary_tags(self.max_steps, self.max_digits, self.vae_recognition_units, self.vae_generative_units, self.scope)
 
+    def _no_cnn_histograms(self):
+        if self.cnn:
+            raise NotImplementedError("the histogram summaries of a cnn=True model are not implemented (its tag lists are a "
+                                      "follow-up: DESIGN.md section 25); numeric_summaries() works")
+
     def var_summary_names(self):
         """Tags of var_summaries(), the reference's 36 at its shapes: "<scope>_1/summaries/<scope>/rnn/<variable>_0" in
         tf.trainable_variables() order (the name scope of the variable-sharing test model, which training.py fetches
         them from)."""
+        self._no_cnn_histograms()
         return self._summary_tags().variables
 
     def grad_summary_names(self):
         """Tags of the histograms of grad_summaries(): "<scope>/training/<scope>/rnn/<variable>_0_grad_original" for every
         variable, then "..._grad_applied" (air_model.py:657-687).  air.summaries.gradient_summaries() adds the _norm / _avg
         scalars the reference writes beside each."""
+        self._no_cnn_histograms()
         return self._summary_tags().gradients[::3]
 
     def _histogram_plan(self, which):
@@ -1688,6 +1800,7 @@ class AIRModel:
         var_summary_names(), as ONE call of air_histograms (include/air_hip.h) on the current stream over the strided views
         of the flat variable buffer -- nothing is copied out variable by variable.  `out`: a uint8 device vector
         (allocated when None) that air.summaries.decode_histograms() reads once fetched.  No host synchronisation."""
+        self._no_cnn_histograms()
         return self._histograms("var", out)
 
     def grad_summaries(self, out=None):
@@ -1698,6 +1811,7 @@ class AIRModel:
         Train models only.  No host synchronisation."""
         if not self.train:
             raise H.AirHipError("grad_summaries: the model was built with train=False and has no gradients")
+        self._no_cnn_histograms()
         return self._histograms("grad", out)
 
     @property

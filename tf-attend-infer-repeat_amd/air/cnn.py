@@ -17,7 +17,9 @@ codes) are not allocated and the launch is the inference forward -- same bits.  
 Stream capture is NOT supported, for the reason air.vae gives: the op refuses to run while the
 current stream is capturing.
 
-AIRModel(cnn=True) does not use this module yet."""
+AIRModel(cnn=True) does not go through this module: its launch lists call air_cnn_fwd and air_cnn_bwd_sq themselves, from the
+thread that captures the step, and own the six variables in the model's flat buffer under the names variable_names() gives
+(DESIGN.md section 25).  CNN.load_variables(model.variables) reproduces the model's rnn_input bit for bit."""
 import ctypes as C
 from collections import OrderedDict
 

@@ -1,6 +1,8 @@
 // The CNN front-end of the reference (air/air_model.py:510-533) as launches of their own: three 5x5 SAME convolutions +
 // ReLU with a 2x2 / stride-2 VALID max-pool after the first two, fp32, one input channel, F <= 8 filters, any canvas S >= 4
-// (include/air_hip.h, "stand-alone CNN front-end").  Nothing of the train step calls these kernels.
+// (include/air_hip.h, "stand-alone CNN front-end").  air/cnn.py calls air_cnn_fwd / air_cnn_bwd; the train step of
+// AIRModel(cnn=True) calls air_cnn_fwd and air_cnn_bwd_sq (the same backward, its batch reduction also leaving the
+// sums of squares the global-norm clip needs).
 //
 // PLAN.  One workgroup per image, everything between the image and `out` stays in LDS.
 //   forward (cnn_fwd_kernel, 256 threads): the zero-haloed image, the three kernels + biases and the zero-haloed pool1 /
@@ -18,6 +20,8 @@
 //     C  dk1 / db1 as sums over the windows at their argmax sites;  d_images (only when asked for) gathers, per pixel,
 //        from the <= 3x3 windows whose site can reach it.
 //   cnn_reduce_kernel: one thread per variable element sums the per-image partials in ascending image order.
+//   cnn_reduce_sq_kernel (air_cnn_bwd_sq): the same sums, same order, same bits; every workgroup also leaves the sum of
+//     squares of the <= 256 elements it stored (wave sums, then the four waves left to right: air_block_sum_256).
 //
 // ACCUMULATION ORDER (fixed; no executed reference graph exists for this block, so none is mirrored).  Every inner
 // product is ONE chain of fmaf:
@@ -444,6 +448,43 @@ __global__ __launch_bounds__(256) void cnn_reduce_kernel(const float* __restrict
     d_b3[r - n2] = s;
 }
 
+// where element j of an image's partials (dk1 | db1 | dk2 | db2 | dk3 | db3) lives among the six gradients
+__device__ __forceinline__ float* cnn_grad_slot(int j, int F, float* d_k1, float* d_b1, float* d_k2, float* d_b2, float* d_k3, float* d_b3) {
+    const int n1 = 25 * F, n2 = 25 * F * F;
+    if (j < n1) return d_k1 + j;
+    j -= n1;
+    if (j < F) return d_b1 + j;
+    j -= F;
+    if (j < n2) return d_k2 + j;
+    j -= n2;
+    if (j < F) return d_b2 + j;
+    j -= F;
+    if (j < n2) return d_k3 + j;
+    return d_b3 + (j - n2);
+}
+
+// cnn_reduce_kernel's sums (image 0, then + image 1, ...: the same bits) and, per workgroup, the sum of squares of the
+// elements it stored: a thread past the last element contributes an exact zero.  Workgroup i writes sq_partials[i].
+__global__ __launch_bounds__(256) void cnn_reduce_sq_kernel(const float* __restrict__ ws, int B, int F, float* d_k1, float* d_b1,
+                                                            float* d_k2, float* d_b2, float* d_k3, float* d_b3,
+                                                            float* __restrict__ sq_partials) {
+    __shared__ float red[4];
+    const int np = cnn_num_partials(F);
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    float sq = 0.0f;
+    if (j < np) {
+        float s = ws[j];
+#pragma unroll 8                                     // eight images' loads in flight; the adds keep their order (same bits)
+        for (int b = 1; b < B; ++b) s += ws[(size_t)b * np + j];
+        *cnn_grad_slot(j, F, d_k1, d_b1, d_k2, d_b2, d_k3, d_b3) = s;
+        sq = s * s;
+    }
+    sq = air_block_sum_256(sq, red);
+    if (threadIdx.x == 0) sq_partials[blockIdx.x] = sq;
+}
+
+constexpr int cnn_reduce_blocks(int F) { return (25 * F + 50 * F * F + 3 * F + 255) / 256; }
+
 // AIR_EINVAL / AIR_ELIMIT of a (B, S, F), the same answer for both entry points and the workspace query
 int cnn_check(int B, int S, int F) {
     if (B < 1 || S < 4 || F < 1) return AIR_EINVAL;
@@ -462,16 +503,37 @@ int launch_fwd(const air_cnn_fwd_t* a, void* stream) {
     return 0;
 }
 
+// sq_partials == NULL: air_cnn_bwd (cnn_reduce_kernel); else air_cnn_bwd_sq (cnn_reduce_sq_kernel)
 template <int F>
-int launch_bwd(const air_cnn_bwd_t* a, void* stream) {
+int launch_bwd(const air_cnn_bwd_t* a, float* sq_partials, void* stream) {
     const size_t bytes = sizeof(float) * (size_t)cnn_lds(a->S, F).b_total;
     if (int rc = air_grant_lds(reinterpret_cast<const void*>(&cnn_bwd_kernel<F>), bytes)) return rc;
     hipLaunchKernelGGL(cnn_bwd_kernel<F>, dim3(a->B), dim3(BWD_NT), bytes, air_stream(stream), *a);
     AIR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cnn_reduce_kernel, dim3((cnn_num_partials(F) + 255) / 256), dim3(256), 0, air_stream(stream),
-                       a->workspace, a->B, F, a->d_k1, a->d_b1, a->d_k2, a->d_b2, a->d_k3, a->d_b3);
+    if (sq_partials)
+        hipLaunchKernelGGL(cnn_reduce_sq_kernel, dim3(cnn_reduce_blocks(F)), dim3(256), 0, air_stream(stream),
+                           a->workspace, a->B, F, a->d_k1, a->d_b1, a->d_k2, a->d_b2, a->d_k3, a->d_b3, sq_partials);
+    else
+        hipLaunchKernelGGL(cnn_reduce_kernel, dim3((cnn_num_partials(F) + 255) / 256), dim3(256), 0, air_stream(stream),
+                           a->workspace, a->B, F, a->d_k1, a->d_b1, a->d_k2, a->d_b2, a->d_k3, a->d_b3);
     AIR_CHECK_LAUNCH();
     return 0;
+}
+
+int cnn_bwd_dispatch(const air_cnn_bwd_t* a, float* sq_partials, void* stream) {
+    if (!a || !a->d_out || !a->out || !a->images || !a->pool1 || !a->pool2 || !a->arg1 || !a->arg2 || !a->k1 || !a->k2 ||
+        !a->k3 || !a->workspace || !a->d_k1 || !a->d_b1 || !a->d_k2 || !a->d_b2 || !a->d_k3 || !a->d_b3) return AIR_EINVAL;
+    if (int rc = cnn_check(a->B, a->S, a->F)) return rc;
+    switch (a->F) {
+        case 1: return launch_bwd<1>(a, sq_partials, stream);
+        case 2: return launch_bwd<2>(a, sq_partials, stream);
+        case 3: return launch_bwd<3>(a, sq_partials, stream);
+        case 4: return launch_bwd<4>(a, sq_partials, stream);
+        case 5: return launch_bwd<5>(a, sq_partials, stream);
+        case 6: return launch_bwd<6>(a, sq_partials, stream);
+        case 7: return launch_bwd<7>(a, sq_partials, stream);
+        default: return launch_bwd<8>(a, sq_partials, stream);
+    }
 }
 
 }  // namespace
@@ -498,18 +560,15 @@ extern "C" int air_cnn_fwd(const air_cnn_fwd_t* a, void* stream) {
     }
 }
 
-extern "C" int air_cnn_bwd(const air_cnn_bwd_t* a, void* stream) {
-    if (!a || !a->d_out || !a->out || !a->images || !a->pool1 || !a->pool2 || !a->arg1 || !a->arg2 || !a->k1 || !a->k2 ||
-        !a->k3 || !a->workspace || !a->d_k1 || !a->d_b1 || !a->d_k2 || !a->d_b2 || !a->d_k3 || !a->d_b3) return AIR_EINVAL;
-    if (int rc = cnn_check(a->B, a->S, a->F)) return rc;
-    switch (a->F) {
-        case 1: return launch_bwd<1>(a, stream);
-        case 2: return launch_bwd<2>(a, stream);
-        case 3: return launch_bwd<3>(a, stream);
-        case 4: return launch_bwd<4>(a, stream);
-        case 5: return launch_bwd<5>(a, stream);
-        case 6: return launch_bwd<6>(a, stream);
-        case 7: return launch_bwd<7>(a, stream);
-        default: return launch_bwd<8>(a, stream);
-    }
+extern "C" int air_cnn_bwd(const air_cnn_bwd_t* a, void* stream) { return cnn_bwd_dispatch(a, nullptr, stream); }
+
+extern "C" int air_cnn_num_sq_partials(int F) {
+    if (F < 1) return AIR_EINVAL;
+    if (F > MAX_F) return AIR_ELIMIT;
+    return cnn_reduce_blocks(F);
+}
+
+extern "C" int air_cnn_bwd_sq(const air_cnn_bwd_t* a, float* sq_partials, void* stream) {
+    if (!sq_partials) return AIR_EINVAL;
+    return cnn_bwd_dispatch(a, sq_partials, stream);
 }

@@ -17,7 +17,7 @@ import shutil
 import torch
 
 from air import embeddings
-from air.air_model import AIRModel
+from air.air_model import AIRModel, saved_cnn_arguments
 from multi_mnist import read_test_data
 
 CANVAS_SIZE = 50
@@ -48,7 +48,7 @@ def main():
         max_steps=3, rnn_units=256, canvas_size=CANVAS_SIZE, windows_size=WINDOW_SIZE,
         vae_latent_dimensions=50, vae_recognition_units=(512, 256), vae_generative_units=(256, 512),
         vae_likelihood_std=0.3, scale_hidden_units=64, shift_hidden_units=64, z_pres_hidden_units=64,
-        z_pres_temperature=1.0, stopping_threshold=0.99, cnn=False,
+        z_pres_temperature=1.0, stopping_threshold=0.99, **saved_cnn_arguments(args.model),
         train=False, reuse=False, scope="air", gemm_precision=args.precision,
     )
     print("Restoring model...")

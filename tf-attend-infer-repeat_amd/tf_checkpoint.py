@@ -6,7 +6,7 @@ The reference restores `model/air-model` with tf.train.Saver (demo.py:33) and sa
                                  BundleEntryProto {dtype, shape, shard_id, offset, size, masked crc32c}
   <prefix>.data-00000-of-00001   the raw little-endian tensor bytes, in key order
 (layout decoded from the reference's own model/air-model.index).  Variable names
-follow the reference graph: trainables under `air/rnn/`, Adam slots `air/training/<var>/Adam`
+follow the reference graph: trainables under `air/rnn/` (the conv front-end's, cnn=True, under `air/cnn/`), Adam slots `air/training/<var>/Adam`
 (m) and `/Adam_1` (v), `air/training/beta{1,2}_power`, `air/global_step`.
 """
 import struct
@@ -175,6 +175,12 @@ def save_checkpoint(prefix, tensors, block_size=4096):
 
 # ----------------------------------------------------------------------------- AIRModel <-> TF names
 SCOPE = "air/rnn/"
+CNN_SCOPE = "air/cnn/"        # the conv front-end's variables (cnn=True): the scope cnn sits BESIDE rnn (air_model.py:511 against :537)
+
+
+def _scoped(name):
+    """graph name of the model's variable `name`: conv variables ("cnn/...") under air/, everything else under air/rnn/"""
+    return ("air/" if name.startswith("cnn/") else SCOPE) + name
 
 
 def model_to_tensors(state_dict, variables_shapes, beta1=0.9, beta2=0.999):
@@ -183,11 +189,12 @@ def model_to_tensors(state_dict, variables_shapes, beta1=0.9, beta2=0.999):
     out = {}
     step = int(state_dict.get("global_step", 0))
     for name in variables_shapes:
-        out[SCOPE + name] = np.asarray(state_dict[name], np.float32)
+        full = _scoped(name)
+        out[full] = np.asarray(state_dict[name], np.float32)
         for slot in ("Adam", "Adam_1"):
             key = name + "/" + slot
             a = np.asarray(state_dict[key], np.float32) if key in state_dict else np.zeros(variables_shapes[name], np.float32)
-            out["air/training/" + SCOPE + name + "/" + slot] = a
+            out["air/training/" + full + "/" + slot] = a
     out["air/global_step"] = np.asarray(step, np.int32)
     out["air/training/beta1_power"] = np.asarray(beta1 ** (step + 1), np.float32)    # TF keeps beta^(t+1)
     out["air/training/beta2_power"] = np.asarray(beta2 ** (step + 1), np.float32)
@@ -202,6 +209,10 @@ def tensors_to_state_dict(tensors):
             sd[name[len(SCOPE):]] = a
         elif name.startswith("air/training/" + SCOPE):
             sd[name[len("air/training/" + SCOPE):]] = a
+        elif name.startswith(CNN_SCOPE):
+            sd[name[len("air/"):]] = a
+        elif name.startswith("air/training/" + CNN_SCOPE):
+            sd[name[len("air/training/air/"):]] = a
         elif name == "air/global_step":
             sd["global_step"] = int(a)
     return sd

@@ -228,7 +228,13 @@ def main():
     parser.add_argument("--late-backward-from", type=int, default=5000,
                         help="(opt-in: over 48 seeds per precision no switch point keeps the reference order's success rate within 60 000 "
                              "iterations; over the full 276 300 the two end alike and this saves ~3 s -- DESIGN.md section 11.1)")
+    parser.add_argument("--cnn", action="store_true",
+                        help="the reference's conv front-end in front of the LSTM (AIRModel(cnn=True); the reference's own "
+                             "training.py passes cnn=False)")
+    parser.add_argument("--cnn-filters", type=int, default=8)
     args = parser.parse_args()
+    if args.cnn and args.tensorboard:
+        parser.error("--tensorboard writes histogram summaries, which a --cnn model does not have yet")
 
     # results folder handling, training.py:41-61
     if os.path.exists(args.results_folder):
@@ -274,7 +280,7 @@ def main():
                 vae_prior_mean=0.0, vae_prior_variance=1.0, vae_likelihood_std=0.3,
                 scale_hidden_units=64, shift_hidden_units=64, z_pres_hidden_units=64,
                 z_pres_prior_log_odds=-0.01, z_pres_temperature=1.0, stopping_threshold=0.99,
-                learning_rate=1e-4, gradient_clipping_norm=1.0, cnn=False, cnn_filters=8,
+                learning_rate=1e-4, gradient_clipping_norm=1.0, cnn=args.cnn, cnn_filters=args.cnn_filters,
                 num_summary_images=NUM_IMAGES_TO_SAVE, train=(i == 0), reuse=(i == 1), scope="air",
                 annealing_schedules={
                     "z_pres_prior_log_odds": {
