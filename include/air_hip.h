@@ -912,6 +912,80 @@ int air_embed_sprite_dim(int M);
 /* doubles of `workspace`, or AIR_EINVAL / AIR_ELIMIT -- no GPU is touched */
 int64_t air_embed_sprites_workspace_doubles(int M, int w);
 
+/* ---- scene source (additive to ABI 6) -----------------------------------------------------------------------------------
+ * The default path of the reference's generate_multi_image (multi_mnist.py:82-183: use_pixel_overlap=True, no scale or
+ * rotation jitter) as ONE launch that composes a fresh batch of B canvases straight into the caller's buffers -- the train
+ * model's inputs -- so that a run needs no data set.  multi_mnist.DeviceSceneSource is the caller.
+ *
+ * Inputs.  glyphs [G, gd * gd] fp32, values >= 0 (ink is value > 0).  crops [G, 4] int32: x0, y0, w, h of each glyph's
+ * non-empty box, computed once on the host (crop_non_empty, multi_mnist.py:36-43).  bg, nullable [C * C].  counts, nullable
+ * [B] int32: the number of digits of each scene (clamped to 0 .. max_digits); null: drawn uniformly from 0 .. max_digits.
+ *
+ * One scene, by one workgroup, the canvas and an occupancy plane in LDS:
+ *   for each of its n digits in turn: draw a glyph index g; then up to max_attempts times draw x uniform in
+ *   [margin, C - w - margin] and y uniform in [margin, C - h - margin].  The first digit takes its first draw.  A later digit
+ *   is accepted when no ink pixel of the glyph lies within Chebyshev distance `gap` of an ink pixel already on the canvas
+ *   (the reference's max(image, window) == image + window against the add_buffer-dilated canvas, :44-65).  An accepted
+ *   glyph's box is added to the canvas: inks are disjoint and everything else adds zero, so the sums are exact.
+ *   A digit that finds no place in max_attempts draws, or whose box does not fit (w + 2 margin > C or h + 2 margin > C; also
+ *   a crop box that is empty or leaves its gd x gd frame), RESTARTS the scene with an empty canvas.  status[b] is the number
+ *   of restarts.  At the end, with bg: image = min(max(canvas + bg, 0), 1) (:189-190); without: the canvas as it is.
+ * Two deviations from the reference:
+ *   - the glyph index is drawn uniformly from 0 .. G-1 instead of walking a permutation of the glyph set (:84-85, 108-112);
+ *   - the reference restarts without a bound; here, when the restart count reaches max_restarts (the scene has failed
+ *     max_restarts times) the scene is written as an EMPTY canvas (bg alone), digits = 0, status = -1, its metadata zero.
+ *
+ * Random numbers: integers only.  Draw j of scene b is word j & 3 of Philox4x32-10(key = (seed low, seed high), counter =
+ * (b, j >> 2, (uint32_t)batch, 0x5343454E)); an integer in [lo, hi) is lo + umulhi(word, hi - lo).  Draw 0 is the count
+ * (only when counts is null); then per digit the glyph index and, per attempt, x then y.  j keeps counting across restarts.
+ * A scene makes at most 1 + max_restarts * max_digits * (1 + 2 * max_attempts) draws: every loop of the kernel has a trip
+ * count bounded by a range-checked argument, control flow is uniform across the workgroup (every thread computes the same
+ * draws, the overlap test ends in a workgroup-wide OR), and there are no global atomics and no grid-wide waits.
+ * batch = *batch_counter + step_in_replay: air_scene_source_advance (one thread: *counter += by) runs once per eager batch,
+ * or once behind the last compose of a captured replay with by = its steps, so replays continue the sequence without the
+ * host and batch k is the same scene set however it was made.
+ *
+ * Outputs (every element is written): images [B, C * C]; digits [B] (the glyphs on the canvas); indices [B, max_digits];
+ * positions [B, 2 * max_digits] (x, y of each box's top-left corner); boxes [B, 2 * max_digits] (w, h); status [B]; slots
+ * behind digits[b] are zero.  gave_up, nullable [B] int32: gave_up[b] += (status[b] == -1) -- a running per-slot count
+ * (its sum is the number of scenes given up so far), read and written by workgroup b alone.
+ *
+ * Limits, answered on the host before any HIP call.  AIR_EINVAL: a null descriptor; B, G, gd, C or max_digits < 1; margin,
+ * gap or step_in_replay < 0; max_attempts or max_restarts < 1; 2 * margin + 1 > C (no glyph can fit); then a null required
+ * pointer.  AIR_ELIMIT: C > 128, gd > 32, max_digits > 6, gap > 4, max_attempts > 100, max_restarts > 64.  An invalid size
+ * is reported before a limit, a limit before a null pointer; AIR_EALIGN: crops not 16-byte aligned.  Dynamic LDS: air_scene_source_lds(C, gd) = 4 C C (canvas) +
+ * 4 gd gd (the glyph being placed) + C C (occupancy), each part rounded up to 16 bytes, + 160 (metadata): 86 176 bytes at
+ * the limits, granted once per device (air_scene_source_prepare does it without a launch: call it before a capture whose
+ * first compose would otherwise be the first). */
+typedef struct {
+    const float* glyphs;                 /* [G, gd * gd]                                                                */
+    const int32_t* crops;                /* [G, 4] x0, y0, w, h                                                         */
+    const float* bg;                     /* nullable [C * C]                                                            */
+    const int32_t* counts;               /* nullable [B]                                                                */
+    const int64_t* batch_counter;        /* one device int64: batches made before this replay / this eager batch        */
+    float* images;                       /* out [B, C * C]                                                              */
+    int32_t* digits;                     /* out [B]                                                                     */
+    int32_t* indices;                    /* out [B, max_digits]                                                         */
+    int32_t* positions;                  /* out [B, 2 * max_digits]                                                     */
+    int32_t* boxes;                      /* out [B, 2 * max_digits]                                                     */
+    int32_t* status;                     /* out [B]: restarts, or -1                                                    */
+    int32_t* gave_up;                    /* in / out, nullable [B]                                                      */
+    int32_t B, G, gd, C, margin, gap, max_digits, max_attempts, max_restarts;
+    uint64_t seed;
+} air_scene_source_t;
+#define AIR_SCENE_MAX_CANVAS 128
+#define AIR_SCENE_MAX_GLYPH 32
+#define AIR_SCENE_MAX_DIGITS 6
+#define AIR_SCENE_MAX_GAP 4
+#define AIR_SCENE_MAX_ATTEMPTS 100
+#define AIR_SCENE_MAX_RESTARTS 64
+int air_scene_source_compose(const air_scene_source_t* a, int step_in_replay, void* stream);
+int air_scene_source_advance(int64_t* counter, int by, void* stream);    /* AIR_EINVAL: null counter, by < 0 */
+/* the checks and the LDS grant of air_scene_source_compose(a, 0, ..) without its launch */
+int air_scene_source_prepare(const air_scene_source_t* a);
+/* bytes of dynamic LDS per workgroup, or AIR_EINVAL / AIR_ELIMIT for a (C, gd) the entry point refuses -- no GPU is touched */
+int64_t air_scene_source_lds(int C, int gd);
+
 #ifdef __cplusplus
 }
 #endif

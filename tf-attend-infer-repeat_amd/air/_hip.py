@@ -195,6 +195,19 @@ class EmbedCollect(C.Structure):
                 ("max_distance", C.c_double)]
 
 
+SCENE_MAX_CANVAS, SCENE_MAX_GLYPH, SCENE_MAX_DIGITS, SCENE_MAX_GAP, SCENE_MAX_ATTEMPTS, SCENE_MAX_RESTARTS = 128, 32, 6, 4, 100, 64
+
+
+class SceneSource(C.Structure):
+    """air_scene_source_t: glyphs and their crop boxes in, one composed batch (canvases, counts, metadata, status) out;
+    batch_counter is a device int64 that air_scene_source_advance moves"""
+    _fields_ = [("glyphs", _p), ("crops", _p), ("bg", _p), ("counts", _p), ("batch_counter", _p),
+                ("images", _p), ("digits", _p), ("indices", _p), ("positions", _p), ("boxes", _p), ("status", _p),
+                ("gave_up", _p),
+                ("B", _i), ("G", _i), ("gd", _i), ("C", _i), ("margin", _i), ("gap", _i), ("max_digits", _i),
+                ("max_attempts", _i), ("max_restarts", _i), ("seed", C.c_uint64)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -268,6 +281,10 @@ _SIGNATURES = {
     "air_embed_sprites": (C.c_int, [_p, C.c_int, C.c_int, _p, _p, _p]),
     "air_embed_sprite_dim": (C.c_int, [C.c_int]),
     "air_embed_sprites_workspace_doubles": (C.c_int64, [C.c_int, C.c_int]),
+    "air_scene_source_compose": (C.c_int, [C.POINTER(SceneSource), C.c_int, _p]),
+    "air_scene_source_advance": (C.c_int, [_p, C.c_int, _p]),
+    "air_scene_source_prepare": (C.c_int, [C.POINTER(SceneSource)]),
+    "air_scene_source_lds": (C.c_int64, [C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

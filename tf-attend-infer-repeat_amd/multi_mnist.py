@@ -14,6 +14,10 @@ follows the reference.
 
   python multi_mnist.py [--max-digits 2] [--images-per-digit 20000] [--test-set-size 1000]
                         [--digit-gap 0] [--canvas-margin 0] [--bg-path X --bg-max-intensity 1.0]
+  python multi_mnist.py --device 60000 [--seed 0] [...]     the same files, composed on the GPU (DeviceSceneSource)
+
+DeviceSceneSource is that default path as device work: one HIP launch composes a fresh batch of canvases into the train
+model's input buffers (training.py --online-data), eagerly or inside a captured replay.
 """
 import argparse
 import gzip
@@ -312,6 +316,168 @@ class ShuffleBatchQueue:
         return between_steps, None
 
 
+def crop_boxes(glyphs, image_dim):
+    """[G, 4] int32 (x0, y0, w, h): the box crop_non_empty keeps of every glyph of [G, image_dim * image_dim]"""
+    g = np.asarray(glyphs, np.float32).reshape(len(glyphs), image_dim, image_dim)
+    out = np.zeros((len(g), 4), np.int32)
+    for i, im in enumerate(g):
+        cols = np.nonzero(np.sum(im, axis=0))[0]
+        rows = np.nonzero(np.sum(im, axis=1))[0]
+        if len(cols) == 0:
+            raise ValueError("glyph %d is empty: crop_non_empty has no box for it" % i)
+        out[i] = (cols[0], rows[0], cols[-1] - cols[0] + 1, rows[-1] - rows[0] + 1)
+    return out
+
+
+class DeviceSceneSource:
+    """generate_multi_image (:82-183) on the device, default path only (pixel overlap with the optional gap buffer, margin,
+    background): every batch is COMPOSED by one launch (air_scene_source_compose, one workgroup per canvas) straight into
+    the caller's `out_images` [B, canvas_dim^2] float32 / `out_digits` [B] int32 -- the train model's input buffers -- so a
+    run needs no data set and never sees a canvas twice.  `glyphs` [G, gd * gd] (numpy or tensor, values >= 0, gd <= 32);
+    `bg` [canvas_dim, canvas_dim] or None; `counts` [B] int32 fixes the digit count of every slot of a batch (None: drawn
+    uniformly from 0 .. max_digits, the mix of the strata of generate_dataset).
+
+    The methods of ShuffleBatchQueue, with its contracts: next_batch() makes one batch on the current stream (compose +
+    the one-thread launch that advances the device batch counter); graph_hooks(steps) is the form for
+    AIRModel.capture_graph(steps, between_steps=): one compose in front of every step, the counter advanced by `steps`
+    behind the last, so replays continue the sequence without the host.  Batch k holds the same scenes either way: its
+    draws are Philox4x32-10 words keyed by (seed; slot, draw, k) -- include/air_hip.h has the draw order.
+    meta(): the device tensors indices / positions / boxes / status of the last batch (status: restarts of the rejection
+    sampler, -1 = given up after max_restarts: an empty canvas with 0 digits).  gave_up(): a device scalar, the number of
+    such canvases over all batches so far; nothing here synchronises.
+
+    Against the host generator: glyph indices are drawn uniformly instead of walking a permutation, and the restart loop
+    is bounded.  Scale / rotation jitter and bounding-box overlap exist only there (Generator.multi_image)."""
+
+    def __init__(self, glyphs, batch_size, out_images, out_digits, canvas_dim=CANVAS_SIZE, max_digits=2, margin=0, gap=0,
+                 bg=None, counts=None, seed=0, max_attempts=100, max_restarts=32, use_pixel_overlap=True, **jitter):
+        import ctypes as C
+        import torch
+        from air import _hip as H
+        neutral = dict(min_w=1.0, max_w=1.0, min_h=1.0, max_h=1.0, min_ang=0.0, max_ang=0.0)
+        unknown = sorted(set(jitter) - set(neutral))
+        if unknown:
+            raise TypeError("unexpected arguments: %s" % ", ".join(unknown))
+        if any(float(jitter[k]) != v for k, v in neutral.items() if k in jitter):
+            raise NotImplementedError("scale / rotation jitter is not composed on the device (the reference's order-5 splines): "
+                                      "use the host generator, multi_mnist.Generator.multi_image")
+        if not use_pixel_overlap:
+            raise NotImplementedError("bounding-box overlap is not composed on the device: use the host generator, "
+                                      "multi_mnist.Generator.multi_image(use_pixel_overlap=False)")
+        H.require_device(out_images, "out_images", "DeviceSceneSource")
+        H.require_device(out_digits, "out_digits", "DeviceSceneSource")
+        self._C, self._torch, self._H = C, torch, H
+        dev = self.device = out_images.device
+        g = glyphs.detach().cpu().numpy() if torch.is_tensor(glyphs) else np.asarray(glyphs)
+        g = np.ascontiguousarray(g.reshape(len(g), -1), np.float32)
+        gd = int(round(np.sqrt(g.shape[1])))
+        if gd * gd != g.shape[1]:
+            raise ValueError("glyphs must be [G, gd * gd]")
+        if g.min() < 0:
+            raise ValueError("glyph values must be >= 0")
+        self.batch, self.canvas_dim, self.max_digits = int(batch_size), int(canvas_dim), int(max_digits)
+        B, D, md = self.batch, self.canvas_dim ** 2, self.max_digits
+        if tuple(out_images.shape) != (B, D) or out_images.dtype != torch.float32 or not out_images.is_contiguous():
+            raise ValueError("out_images must be a contiguous float32 [%d, %d]" % (B, D))
+        if tuple(out_digits.shape) != (B,) or out_digits.dtype != torch.int32:
+            raise ValueError("out_digits must be an int32 [%d]" % B)
+        crops = crop_boxes(g, gd)
+        if not np.any((crops[:, 2] + 2 * margin <= canvas_dim) & (crops[:, 3] + 2 * margin <= canvas_dim)):
+            raise ValueError("no glyph fits a %d x %d canvas with margin %d" % (canvas_dim, canvas_dim, margin))
+        self.out_images, self.out_digits = out_images, out_digits
+        self.glyphs = torch.tensor(g, device=dev)
+        self.crops = torch.tensor(crops, device=dev)
+        self.bg = None if bg is None else torch.tensor(np.ascontiguousarray(bg, np.float32).reshape(-1), device=dev)
+        if self.bg is not None and self.bg.numel() != D:
+            raise ValueError("bg must be [%d, %d]" % (canvas_dim, canvas_dim))
+        self.counts = None
+        if counts is not None:
+            self.counts = torch.as_tensor(counts).to(device=dev, dtype=torch.int32).contiguous()
+            if tuple(self.counts.shape) != (B,):
+                raise ValueError("counts must be [%d]" % B)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)          # batches made so far (device: replays move it)
+        self.indices = torch.zeros(B, md, dtype=torch.int32, device=dev)
+        self.positions = torch.zeros(B, 2 * md, dtype=torch.int32, device=dev)
+        self.boxes = torch.zeros(B, 2 * md, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._gave_up = torch.zeros(B, dtype=torch.int32, device=dev)         # per slot; gave_up() sums it
+        self._steps = None          # steps per replay once graph_hooks has been taken
+        self._a = H.SceneSource(
+            self.glyphs.data_ptr(), self.crops.data_ptr(), self.bg.data_ptr() if self.bg is not None else None,
+            self.counts.data_ptr() if self.counts is not None else None, self.counter.data_ptr(),
+            out_images.data_ptr(), out_digits.data_ptr(), self.indices.data_ptr(), self.positions.data_ptr(),
+            self.boxes.data_ptr(), self.status.data_ptr(), self._gave_up.data_ptr(),
+            B, len(g), gd, self.canvas_dim, int(margin), int(gap), md, int(max_attempts), int(max_restarts),
+            int(seed) & 0xFFFFFFFFFFFFFFFF)
+        # the argument checks and the LDS grant now: the first compose may be enqueued under stream capture
+        with torch.cuda.device(dev):
+            H.check(H.lib().air_scene_source_prepare(C.byref(self._a)), "air_scene_source_prepare")
+
+    def _s(self):
+        return self._H.stream(self.device)
+
+    def _compose(self, step_in_replay):
+        H = self._H
+        H.check(H.lib().air_scene_source_compose(self._C.byref(self._a), step_in_replay, self._s()), "air_scene_source_compose")
+
+    def _advance(self, by):
+        H = self._H
+        H.check(H.lib().air_scene_source_advance(self.counter.data_ptr(), by, self._s()), "air_scene_source_advance")
+
+    def next_batch(self, _i=0):
+        if self._steps is not None:
+            raise RuntimeError("this source feeds a captured graph (graph_hooks): batches come out of its replays")
+        self._compose(0)
+        self._advance(1)
+
+    def graph_hooks(self, steps):
+        """-> (between_steps, after_steps) for AIRModel.capture_graph"""
+        if steps < 1:
+            raise ValueError("steps per replay must be positive")
+        if self._steps is None:
+            self._steps = steps
+        elif self._steps != steps:
+            raise ValueError("graph_hooks was set up for %d steps per replay" % self._steps)
+
+        def between_steps(i):
+            self._compose(i)
+            if i == steps - 1:                           # behind the last compose of the replay: the next replay goes on
+                self._advance(steps)
+        return between_steps, None
+
+    def meta(self):
+        return dict(indices=self.indices, positions=self.positions, boxes=self.boxes, status=self.status)
+
+    def gave_up(self):
+        return self._gave_up.sum()
+
+
+def compose_on_device(num_images, max_digits=2, canvas_dim=CANVAS_SIZE, bg=None, gap=0, margin=0, seed=0, batch_size=1000,
+                      **generator_options):
+    """`num_images` canvases from DeviceSceneSource (cuda:0), with the metadata generate_strata keeps: -> (dict of numpy
+    arrays images [n, canvas_dim^2], digits, indices, positions, boxes, labels [n, max_digits] (slots behind digits[i] are
+    0) and status [n], glyph source).  generator_options: what the device does not compose is refused by the source."""
+    import torch
+    glyphs, labels, source = load_glyphs()
+    dev = torch.device("cuda", 0)
+    B = min(batch_size, num_images)
+    images = torch.zeros(B, canvas_dim * canvas_dim, device=dev)
+    digits = torch.zeros(B, dtype=torch.int32, device=dev)
+    src = DeviceSceneSource(glyphs, B, images, digits, canvas_dim=canvas_dim, max_digits=max_digits, margin=margin, gap=gap,
+                            bg=bg, seed=seed, **generator_options)
+    out = {k: [] for k in ("images", "digits", "indices", "positions", "boxes", "status")}
+    for _ in range((num_images + B - 1) // B):
+        src.next_batch()
+        out["images"].append(images.cpu().numpy())
+        out["digits"].append(digits.cpu().numpy())
+        for k, v in src.meta().items():
+            out[k].append(v.cpu().numpy())
+    out = {k: np.concatenate(v)[:num_images] for k, v in out.items()}
+    used = np.arange(max_digits)[None, :] < out["digits"][:, None]
+    out["labels"] = np.where(used, labels[out["indices"]], 0).astype(np.int32)
+    return out, source
+
+
 def read_test_data(filename, shift_zero_digits_images=False):
     """:254-296 -- reads a .tfrecords file written by the reference (or by write_to_records)."""
     import tfrecord
@@ -367,9 +533,25 @@ if __name__ == "__main__":
     parser.add_argument("--canvas-size", type=int, default=CANVAS_SIZE)
     parser.add_argument("--tfrecords", action="store_true",
                         help="also write the reference's files: <n>.tfrecords per stratum, common.tfrecords, test.tfrecords")
+    parser.add_argument("--device", type=int, default=0, metavar="N",
+                        help="compose N canvases on the GPU instead (DeviceSceneSource: 0 .. --max-digits digits each, drawn "
+                             "uniformly) and write them with their metadata to common.npz / test.npz")
+    parser.add_argument("--seed", type=int, default=0, help="--device: the seed of the scene source")
     args = parser.parse_args()
     os.makedirs(MULTI_MNIST_FOLDER, exist_ok=True)
     bg = read_image(args.bg_path, args.bg_max_intensity) if args.bg_path else None
+    if args.device:
+        jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
+                      max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
+        ds, source = compose_on_device(args.device, max_digits=args.max_digits, canvas_dim=args.canvas_size, bg=bg,
+                                       gap=args.digit_gap, margin=args.canvas_margin, seed=args.seed,
+                                       use_pixel_overlap=not args.use_bounding_box_overlap, **jitter)
+        T = min(args.test_set_size, args.device)
+        np.savez(MULTI_MNIST_FOLDER + "common.npz", **{k: v[T:] for k, v in ds.items()})
+        np.savez(MULTI_MNIST_FOLDER + "test.npz", **{k: v[:T] for k, v in ds.items()})
+        print("glyph source: %s; composed on the device: wrote %d train / %d test images, %d given up" % (
+            source, args.device - T, T, int((ds["status"] < 0).sum())))
+        raise SystemExit(0)
     strata, rng, source = generate_strata(
         args.max_digits, args.images_per_digit, bg=bg, canvas_dim=args.canvas_size, verbose=True,
         min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale, max_h=args.max_height_scale,

@@ -15,6 +15,11 @@ device (multi_mnist.ShuffleBatchQueue; multi_mnist.py:240-249: capacity 10 000 +
 buffer; with --print-every 0 fifty train steps and their batches are one hipGraph replay (the queue's picks for the
 fifty batches in its first launch, a row gather in front of every step), and the evaluation every 50 iterations is one replay of the
 test model's forward + one summaries launch whose numbers are fetched without blocking (SummaryWriter).
+
+--online-data replaces the queue and the train set by multi_mnist.DeviceSceneSource: the generator's default path as one
+launch per step that composes a fresh batch into the train model's input buffers (inside the replay when there is one), so
+no canvas is trained on twice; the evaluation set stays the fixed one.  The run ends with a line that says how many
+batches were composed and how many canvases the bounded rejection sampler gave up on.
 """
 import argparse
 import json
@@ -25,7 +30,7 @@ import time
 import numpy as np
 import torch
 
-from multi_mnist import ShuffleBatchQueue, generate_dataset, shift_zero_digits_images
+from multi_mnist import DeviceSceneSource, ShuffleBatchQueue, generate_dataset, load_glyphs, shift_zero_digits_images
 from air.air_model import AIRModel
 
 EPOCHS = 300
@@ -46,6 +51,20 @@ TRAIN_DATA_FILE = "multi_mnist_data/common.npz"
 TEST_DATA_FILE = "multi_mnist_data/test.npz"
 
 
+def load_background(bg_path="", bg_max_intensity=1.0):
+    """clutter (multi_mnist.py --bg-path / --bg-max-intensity): a png, or "<file>.npz:<key>", an already decoded background"""
+    if not bg_path:
+        return None
+    if ".npz:" in bg_path:
+        f, key = bg_path.rsplit(":", 1)
+        bg = np.load(f)[key].astype(np.float32)
+        if bg.max() > 0:
+            bg = bg / bg.max() * min(bg_max_intensity, 1.0)
+        return bg
+    from multi_mnist import read_image
+    return read_image(bg_path, bg_max_intensity)
+
+
 def load_data(bg_path="", bg_max_intensity=1.0):
     if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
         tr, te = np.load(TRAIN_DATA_FILE), np.load(TEST_DATA_FILE)
@@ -59,17 +78,7 @@ def load_data(bg_path="", bg_max_intensity=1.0):
         tei, ted, *_ = read_test_data(rec_te)
         return tri, trd.astype(np.int32), tei, ted.astype(np.int32)
     print("Generating multi-digit dataset in memory (multi_mnist.py defaults)...")
-    bg = None
-    if bg_path:                                            # clutter (multi_mnist.py --bg-path / --bg-max-intensity)
-        if ".npz:" in bg_path:                             # "<file>.npz:<key>": an already decoded background
-            f, key = bg_path.rsplit(":", 1)
-            bg = np.load(f)[key].astype(np.float32)
-            if bg.max() > 0:
-                bg = bg / bg.max() * min(bg_max_intensity, 1.0)
-        else:
-            from multi_mnist import read_image
-            bg = read_image(bg_path, bg_max_intensity)
-    ds = generate_dataset(bg=bg)
+    ds = generate_dataset(bg=load_background(bg_path, bg_max_intensity))
     return ds["train_images"], ds["train_digits"], ds["test_images"], ds["test_digits"]
 
 
@@ -232,6 +241,13 @@ def main():
                         help="the reference's conv front-end in front of the LSTM (AIRModel(cnn=True); the reference's own "
                              "training.py passes cnn=False)")
     parser.add_argument("--cnn-filters", type=int, default=8)
+    parser.add_argument("--online-data", action="store_true",
+                        help="compose every train batch on the device (multi_mnist.DeviceSceneSource: the generator's default "
+                             "path, a fresh batch per step, no canvas seen twice) instead of drawing it from the fixed train set; "
+                             "--bg-path applies; the evaluation set stays the fixed one")
+    parser.add_argument("--online-max-digits", type=int, default=2, help="--online-data: scenes hold 0 .. this many digits")
+    parser.add_argument("--digit-gap", type=int, default=0, help="--online-data: empty pixels kept between two digits")
+    parser.add_argument("--canvas-margin", type=int, default=0, help="--online-data: empty border of the canvas")
     args = parser.parse_args()
     if args.cnn and args.tensorboard:
         parser.error("--tensorboard writes histogram summaries, which a --cnn model does not have yet")
@@ -255,8 +271,9 @@ def main():
     print("Creating input pipeline...")
     tr_im, tr_dg, te_im, te_dg = load_data(args.bg_path, args.bg_max_intensity)
     te_im, te_dg = shift_zero_digits_images(te_im, te_dg)
-    train_images = torch.tensor(tr_im, device=dev)
-    train_digits = torch.tensor(tr_dg.astype(np.int32), device=dev)
+    if not args.online_data:
+        train_images = torch.tensor(tr_im, device=dev)
+        train_digits = torch.tensor(tr_dg.astype(np.int32), device=dev)
     test_data = torch.tensor(np.ascontiguousarray(te_im), device=dev)
     test_targets = torch.tensor(np.ascontiguousarray(te_dg).astype(np.int32), device=dev)
     train_data = torch.zeros(BATCH_SIZE, CANVAS_SIZE ** 2, device=dev)
@@ -293,15 +310,22 @@ def main():
             )
         )
     train_model, test_model = models
-    n_train = train_images.shape[0]
+    n_train = tr_im.shape[0]
     total = args.iterations if args.iterations > 0 else (n_train // BATCH_SIZE) * EPOCHS
 
     # The input queue is device work too (read_and_decode, multi_mnist.py:228-249): the RandomShuffleQueue's resident
     # record indices and the stream position live in HBM.  When nothing is printed per step, --graph-steps train steps
     # are captured per hipGraph replay together with their batches: one launch at the head of the replay makes the picks of
     # all its batches, one row gather sits in front of every step.
-    batches = ShuffleBatchQueue(train_images, train_digits, BATCH_SIZE, train_data, train_targets,
-                                seed=0x5348554646 + args.seed, min_after_dequeue=MIN_AFTER_DEQUEUE)
+    # --online-data: no queue and no train set -- one launch in front of every step composes the step's batch from the
+    # glyphs (same hooks: next_batch() eagerly, graph_hooks() inside the replay).
+    if args.online_data:
+        batches = DeviceSceneSource(load_glyphs()[0], BATCH_SIZE, train_data, train_targets, canvas_dim=CANVAS_SIZE,
+                                    max_digits=args.online_max_digits, margin=args.canvas_margin, gap=args.digit_gap,
+                                    bg=load_background(args.bg_path, args.bg_max_intensity), seed=0x5343454E45 + args.seed)
+    else:
+        batches = ShuffleBatchQueue(train_images, train_digits, BATCH_SIZE, train_data, train_targets,
+                                    seed=0x5348554646 + args.seed, min_after_dequeue=MIN_AFTER_DEQUEUE)
     gsteps = 1
     if not args.no_graph:
         if args.print_every == 0 and NUM_SUMMARIES_EACH_ITERATIONS % args.graph_steps == 0 and args.graph_steps > 1:
@@ -359,6 +383,9 @@ def main():
     print("training has ended")
     print("test accuracy {:.4f}  test loss {:.3f}  ({} iterations, {:.1f} s)".format(
         float(test_model.accuracy), float(test_model.loss), step, time.perf_counter() - t0))
+    if args.online_data:
+        print("online data: {} batches composed on the device, {} canvases given up".format(
+            int(batches.counter), int(batches.gave_up())))
     torch.save(train_model.state_dict(), models_folder + "air-model-%d.pt" % step)
     if args.tf_checkpoints:
         train_model.save_tf_checkpoint(models_folder + "air-model-%d" % step)
