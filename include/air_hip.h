@@ -78,9 +78,10 @@ enum {
 /* one annealing schedule (air_model.py:94-121), evaluated on device each step */
 typedef struct {
     int32_t slot;        /* AIR_DYN_* written                               */
-    int32_t flags;       /* bit0 staircase, bit1 has_min, bit2 has_max, bit3 log */
+    int32_t flags;       /* AIR_SCHED_* bits                                 */
     float init, iters, factor, vmin, vmax;
 } air_schedule_t;
+enum { AIR_SCHED_STAIRCASE = 1, AIR_SCHED_HAS_MIN = 2, AIR_SCHED_HAS_MAX = 4, AIR_SCHED_LOG = 8 };
 
 /* ---- per-step records ---------------------------------------------------
  * att[t][b][AIR_ATT_STRIDE] -- per-item scalars of one time step. */
@@ -277,7 +278,8 @@ int air_wgrad_num_blocks(const air_wgrad_t* probs, int count);
  * For a problem of >= 512 tiles (any precision) the tile that sums db of column tile nt is the one in block-row nt % 16,
  * not block-row 0.  Diagnostic; AIR_WGRAD_STRIP=<tiles per workgroup, 0 = off> overrides. */
 int air_wgrad_num_workgroups(const air_wgrad_t* probs, int count, int precision);
-int air_wgrad_grouped(const air_wgrad_t* probs /*HOST array, <= 16*/, int count, int precision,
+#define AIR_MAX_WGRAD_PROBLEMS 16
+int air_wgrad_grouped(const air_wgrad_t* probs /*HOST array, <= AIR_MAX_WGRAD_PROBLEMS*/, int count, int precision,
                       float* sq_partials, int32_t* istate, void* stream);
 
 /* column sums db[n] = sum_r dY[r*ld + n]  (BiasAdd_grad nodes) for `count` problems */

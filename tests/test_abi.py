@@ -1,79 +1,131 @@
-"""CPU-side checks of the C-ABI boundary: the library builds for gfx950, loads,
-exports every symbol include/air_hip.h declares, the ctypes structs match the C
-layout, argument errors are reported without touching a GPU, and the product
-path refuses to run without the HIP library / on CPU tensors (no fallback)."""
+"""CPU-side checks of the C-ABI boundary: the library builds for gfx950, loads and exports every symbol include/air_hip.h
+declares; the WHOLE of the ctypes mirror air/_hip.py -- every struct, field, constant and signature -- equals the header
+(tests/abi_check.py reads it), and that comparison reports a doctored header or mirror by name; argument errors are
+reported without touching a GPU, and the product path refuses to run without the HIP library / on CPU tensors (no
+fallback)."""
 import ctypes as C
 import os
 import re
 import subprocess
 import sys
+import types
 
-import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "air_hip.h")
+import abi_check as abi
+
+ROOT = abi.ROOT
 
 
 @pytest.fixture(scope="module")
 def H():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("air_build", os.path.join(ROOT, "tf-attend-infer-repeat_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.build(verbose=False)
-    from air import _hip
-    _hip.lib()
-    return _hip
-
-
-def _declared_symbols():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(air_[a-z0-9_]+)\s*\(", src)))
+    return abi.hip()
 
 
 def test_every_declared_symbol_is_exported_and_bound(H):
-    declared = _declared_symbols()
-    assert len(declared) >= 20
+    """declared == exported == bound, and load() gave every function the restype and argtypes of its _SIGNATURES row"""
+    declared = sorted(abi.read_header().prototypes)
+    src = re.sub(r"/\*.*?\*/", "", open(abi.HEADER).read(), flags=re.S)
+    assert declared == sorted(set(re.findall(r"\b(air_[a-z0-9_]+)\s*\(", src)))      # the reader misses no air_*( of the header
+    assert len(declared) >= 74
     lib = C.CDLL(H.LIB_PATH)
     for name in declared:
         assert hasattr(lib, name), name
     assert sorted(H.EXPORTED_SYMBOLS) == declared
+    for name, (res, args) in H._SIGNATURES.items():
+        fn = getattr(H.lib(), name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
 
 
 def test_abi_version_and_strerror(H):
-    assert H.lib().air_abi_version() == H.ABI_VERSION == 6
-    assert b"invalid argument" in H.lib().air_strerror(-1)
+    assert H.lib().air_abi_version() == H.ABI_VERSION == 6           # every feature since has been additive: the version stays
+    assert b"invalid argument" in H.lib().air_strerror(H.EINVAL)
     assert H.lib().air_strerror(0) == b"success"
+    assert (H.EINVAL, H.ELIMIT, H.EALIGN) == (-1, -2, -3)
 
 
-def test_struct_layout_matches_c(H, tmp_path):
-    """sizeof/offsetof from a C compile of the header == ctypes."""
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "air_hip.h"\nint main(){'
-                    'printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(air_gemm_t), offsetof(air_gemm_t, bias),'
-                    'offsetof(air_gemm_t, aux), offsetof(air_gemm_t, precision), offsetof(air_gemm_t, p0), offsetof(air_gemm_t, q2), sizeof(air_schedule_t),'
-                    'sizeof(air_attend_fwd_t), offsetof(air_attend_fwd_t, B), sizeof(air_attend_bwd_t),'
-                    'sizeof(air_write_fwd_t), sizeof(air_write_bwd_t)); printf("%zu %zu %zu %zu %zu\\n", sizeof(air_colsum_t),'
-                    'sizeof(air_bottleneck_fwd_t), offsetof(air_bottleneck_fwd_t, ldx), sizeof(air_bottleneck_bwd_t), offsetof(air_bottleneck_bwd_t, H));'
-                    'printf("%zu %zu %zu %zu %d\\n", sizeof(air_panel_t), offsetof(air_panel_t, K), offsetof(air_panel_t, exclusive), offsetof(air_gemm_t, B16p),'
-                    'AIR_MAX_PANELS);'
-                    'printf("%zu %zu %zu %zu\\n", sizeof(air_summaries_t), offsetof(air_summaries_t, out), offsetof(air_summaries_t, B),'
-                    'sizeof(air_shuffle_batch_t));'
-                    'return 0;}')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    out = subprocess.check_output([str(exe)]).decode().split()
-    got = [int(x) for x in out]
-    exp = [C.sizeof(H.Gemm), H.Gemm.bias.offset, H.Gemm.aux.offset, H.Gemm.precision.offset, H.Gemm.p0.offset, H.Gemm.q2.offset,
-           C.sizeof(H.Schedule), C.sizeof(H.AttendFwd), H.AttendFwd.B.offset, C.sizeof(H.AttendBwd),
-           C.sizeof(H.WriteFwd), C.sizeof(H.WriteBwd), C.sizeof(H.Colsum),
-           C.sizeof(H.BottleneckFwd), H.BottleneckFwd.ldx.offset, C.sizeof(H.BottleneckBwd), H.BottleneckBwd.H.offset,
-           C.sizeof(H.Panel), H.Panel.K.offset, H.Panel.exclusive.offset, H.Gemm.B16p.offset, H.MAX_PANELS,
-           C.sizeof(H.Summaries), H.Summaries.out.offset, H.Summaries.B.offset, C.sizeof(H.ShuffleBatch)]
-    assert got == exp, (got, exp)
+# ---- the mirror equals the header ---------------------------------------------------------------------------------------
+def test_the_reader_finds_the_whole_header():
+    h, num = abi.read_header(), abi.compile_numbers()
+    assert len(h.structs) >= 24 and len(h.prototypes) >= 74 and len(h.constants) >= 74
+    assert len(num.sizeof) == len(h.structs) and len(num.fields) == sum(len(f) for f in h.structs.values()) >= 350
+    assert sorted(num.values) == sorted(h.constants)
+    assert h.structs["air_schedule_t"] == ["slot", "flags", "init", "iters", "factor", "vmin", "vmax"]
+    assert h.prototypes["air_bf16_twin"] == ("int", ["const float*", "uint16_t*", "int64_t", "void*"])
+    assert h.prototypes["air_strerror"] == ("const char*", ["int"]) and h.prototypes["air_abi_version"] == ("int", [])
+    assert num.values["AIR_MAX_PANELS"] == 16 and num.values["AIR_EINVAL"] == -1
+
+
+def test_structs_fields_and_layout_match_the_header(H):
+    """both directions of the struct set; per struct the field names in order and the size; per field its offset and size"""
+    assert abi.check_structs(abi.read_header(), abi.compile_numbers(), H) == []
+
+
+def test_constants_match_the_header(H):
+    """every upper-case integer X of _hip.py is AIR_X with the compiled value: ABI_VERSION and the error codes included, and
+    no list of exceptions"""
+    assert len(abi.constants(H)) >= 73 and {"ABI_VERSION", "EINVAL", "ELIMIT", "EALIGN", "DYN_COUNT"} <= set(abi.constants(H))
+    assert abi.check_constants(abi.read_header(), abi.compile_numbers(), H) == []
+
+
+def test_signatures_match_the_prototypes(H):
+    """per prototype the restype and, element by element, the argtypes (abi_check.ctypes_of is the mapping)"""
+    assert abi.check_signatures(abi.read_header(), H) == []
+
+
+def _swap_wgrad_fields(src):
+    assert "int32_t head_pack, Hs, Hh, Hz;" in src
+    return src.replace("int32_t head_pack, Hs, Hh, Hz;", "int32_t head_pack, Hh, Hs, Hz;")
+
+
+def _append_render_field(src):
+    assert "    int32_t B, N, C, w;\n} air_render_t;" in src
+    return src.replace("    int32_t B, N, C, w;\n} air_render_t;", "    int32_t B, N, C, w;\n    int32_t extra;\n} air_render_t;")
+
+
+def _renumber_clip_norm(src):
+    assert "AIR_DYN_CLIP_NORM      = 4," in src
+    return src.replace("AIR_DYN_CLIP_NORM      = 4,", "AIR_DYN_CLIP_NORM      = 12,")
+
+
+def _narrow_twin_count(src):
+    assert "int air_bf16_twin(const float* src, uint16_t* dst, int64_t n, void* stream);" in src
+    return src.replace("int air_bf16_twin(const float* src, uint16_t* dst, int64_t n, void* stream);",
+                       "int air_bf16_twin(const float* src, uint16_t* dst, int n, void* stream);")
+
+
+def _add_prototype(src):
+    return src.replace("int air_abi_version(void);", "int air_abi_version(void);\nint air_new_thing(int x, void* stream);")
+
+
+@pytest.mark.parametrize("doctor, item, names", [
+    (_swap_wgrad_fields, "air_wgrad_t", ["air_wgrad_t: field 11 is Hh in the header, Hs in Wgrad",
+                                         "air_wgrad_t.Hs: (offset, size) (64, 4) in C, (60, 4) in Wgrad",
+                                         "air_wgrad_t.Hh: (offset, size) (60, 4) in C, (64, 4) in Wgrad"]),
+    (_append_render_field, "air_render_t", ["air_render_t: field 8 is extra in the header, nothing in Render",
+                                            "air_render_t: sizeof 56 in C, 48 in Render"]),
+    (_renumber_clip_norm, "DYN_CLIP_NORM", ["DYN_CLIP_NORM = 4: AIR_DYN_CLIP_NORM is 12 in the header"]),
+    (_narrow_twin_count, "air_bf16_twin", ["air_bf16_twin: argument 2 is int, bound as c_long"]),
+    (_add_prototype, "air_new_thing", ["air_new_thing: declared in the header, no _SIGNATURES row"])])
+def test_a_doctored_header_is_reported_by_name(H, tmp_path, doctor, item, names):
+    """the checker catches what it is for: a copy of the header with one change gives exactly the mismatches of the changed
+    item, each naming it (the repository's header is read, never written)"""
+    path = tmp_path / "air_hip.h"
+    path.write_text(doctor(open(abi.HEADER).read()))
+    got = abi.check_abi(H, str(path))
+    assert sorted(got) == sorted(names) and all(msg.startswith(item) for msg in got)
+
+
+def test_a_doctored_mirror_is_reported_by_name(H):
+    class Render(C.Structure):                                   # one field renamed
+        _fields_ = [(n if n != "canvas" else "image", t) for n, t in H.Render._fields_]
+    sigs = dict(H._SIGNATURES, air_render=(C.c_int, [C.POINTER(Render), C.c_void_p]))
+    sigs["air_colsum"] = (C.c_int, sigs["air_colsum"][1][:-1])   # one argument dropped
+    patched = types.SimpleNamespace(**dict(vars(H), Render=Render, _SIGNATURES=sigs))
+    assert abi.check_abi(patched) == ["air_render_t: field 2 is canvas in the header, image in Render",
+                                      "air_colsum: 3 parameters in the header, 2 argtypes"]
+    assert abi.check_abi(types.SimpleNamespace(**dict(vars(H), NEW_LIMIT=5))) == ["NEW_LIMIT = 5: the header has no AIR_NEW_LIMIT"]
 
 
 def test_argument_errors_without_gpu(H):
@@ -87,10 +139,7 @@ def test_argument_errors_without_gpu(H):
     assert lib.air_colsum(None, 0, None) == -1
     assert lib.air_vae_bottleneck_fwd(C.byref(H.BottleneckFwd()), None) == -1
     assert lib.air_vae_bottleneck_bwd(None, None) == -1
-    buf = (C.c_float * 64)()
-    base = C.addressof(buf)
-    base += (-base) % 16
-    A = C.c_void_p(base)
+    A = abi.host_ptr()
     # a norm-only weight-gradient problem (dW NULL) needs the partial-sum output
     nul = (H.Wgrad * 1)(H.Wgrad(A, A, None, None, 2, 4, 2, 2, 4, 4, 0, 0, 0, 0))
     assert lib.air_wgrad_grouped(nul, 1, 1, None, None, None) == -1

@@ -1,16 +1,13 @@
-"""CPU-side checks of the stand-alone CNN front-end (include/air_hip.h, air/cnn.py): the entry points are exported and
-bound under ABI 6, the two descriptors match a C compile of the header, argument errors are answered on the host before
-any HIP call, the module's variables carry tf.layers.conv2d's names, and the Python op refuses CPU tensors and sizes the
-library cannot hold.  (What the kernels compute: tests/test_gpu_cnn.py.)"""
+"""CPU-side checks of the stand-alone CNN front-end (include/air_hip.h, air/cnn.py): argument errors are answered on the host
+before any HIP call, the module's variables carry tf.layers.conv2d's names, and the Python op refuses CPU tensors and sizes
+the library cannot hold.  (What the kernels compute: tests/test_gpu_cnn.py.)"""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"air_cnn_fwd": (C.c_int, 2), "air_cnn_bwd": (C.c_int, 2), "air_cnn_workspace_floats": (C.c_int64, 3)}
+import abi_check as abi
+
 FWD_REQUIRED = ("images", "k1", "b1", "k2", "b2", "k3", "b3", "out")
 FWD_SAVED = ("pool1", "pool2", "arg1", "arg2")
 BWD_REQUIRED = ("d_out", "out", "images", "pool1", "pool2", "arg1", "arg2", "k1", "k2", "k3", "workspace",
@@ -19,54 +16,12 @@ BWD_REQUIRED = ("d_out", "out", "images", "pool1", "pool2", "arg1", "arg2", "k1"
 
 @pytest.fixture(scope="module")
 def H():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("air_build", os.path.join(ROOT, "tf-attend-infer-repeat_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.build(verbose=False)
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.hip()
 
 
 @pytest.fixture()
 def ptr():
-    """a 16-byte aligned non-null address (never dereferenced: every call below returns before a launch)"""
-    buf = (C.c_char * 272)()
-    base = C.addressof(buf)
-    yield C.c_void_p(base + (-base) % 16)
-    del buf
-
-
-def test_entry_points_are_exported_and_bound(H):
-    raw = C.CDLL(H.LIB_PATH)
-    for name, (res, nargs) in NEW.items():
-        assert hasattr(raw, name), name
-        assert name in H.EXPORTED_SYMBOLS
-        fn = getattr(H.lib(), name)
-        assert fn.restype is res and len(fn.argtypes) == nargs, name
-    assert H.lib().air_abi_version() == H.ABI_VERSION == 6
-
-
-def test_descriptor_layout_matches_c(H, tmp_path):
-    fields = {"air_cnn_fwd_t": (H.CnnFwd, ("images", "b1", "out", "pool1", "arg1", "arg2", "B", "S", "F")),
-              "air_cnn_bwd_t": (H.CnnBwd, ("d_out", "images", "arg1", "k1", "workspace", "d_k1", "d_b3", "d_images", "B", "S", "F"))}
-    items, exp = [], []
-    for cname, (struct, names) in fields.items():
-        items.append("sizeof(%s)" % cname)
-        exp.append(C.sizeof(struct))
-        for n in names:
-            items.append("offsetof(%s, %s)" % (cname, n))
-            exp.append(getattr(struct, n).offset)
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "air_hip.h"\nint main(){'
-                    + "".join('printf("%%zu\\n", (size_t)%s);' % it for it in items) + "return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
-    assert got == exp, (got, exp)
-    assert [n for n, _ in H.CnnFwd._fields_] == list(FWD_REQUIRED + FWD_SAVED) + ["B", "S", "F"]
-    assert [n for n, _ in H.CnnBwd._fields_] == list(BWD_REQUIRED) + ["d_images", "B", "S", "F"]
+    return abi.host_ptr()
 
 
 def _fwd(H, ptr, B=2, S=50, F=8, saved=True, **override):

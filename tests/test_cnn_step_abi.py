@@ -1,8 +1,7 @@
-"""CPU-side checks of what AIRModel(cnn=True) adds below the model: the two entry points
-air_cnn_bwd_sq / air_cnn_num_sq_partials are declared, exported and bound under ABI 6 and answer argument errors on the
-host before any HIP call, in the cases air_cnn_bwd does; the VariableStore keeps every cnn=False offset, puts the six conv
-variables behind everything else and draws them first from its one stream.  (What the step computes:
-tests/test_gpu_cnn_model.py.)"""
+"""CPU-side checks of what AIRModel(cnn=True) adds below the model: the two entry points air_cnn_bwd_sq
+/ air_cnn_num_sq_partials answer argument errors on the host before any HIP call, in the cases air_cnn_bwd does; the
+VariableStore keeps every cnn=False offset, puts the six conv variables behind everything else and draws them first from its
+one stream.  (What the step computes: tests/test_gpu_cnn_model.py.)"""
 import ctypes as C
 import json
 import os
@@ -10,6 +9,8 @@ import os
 import numpy as np
 import pytest
 import torch
+
+import abi_check as abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BWD_REQUIRED = ("d_out", "out", "images", "pool1", "pool2", "arg1", "arg2", "k1", "k2", "k3", "workspace",
@@ -20,23 +21,12 @@ HP = dict(canvas_size=50, windows_size=28, rnn_units=256, vae_latent_dimensions=
 
 @pytest.fixture(scope="module")
 def H():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("air_build", os.path.join(ROOT, "tf-attend-infer-repeat_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.build(verbose=False)
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.hip()
 
 
 @pytest.fixture()
 def ptr():
-    """a 16-byte aligned non-null address (never dereferenced: every call below returns before a launch)"""
-    buf = (C.c_char * 272)()
-    base = C.addressof(buf)
-    yield C.c_void_p(base + (-base) % 16)
-    del buf
+    return abi.host_ptr()
 
 
 def _bwd(H, ptr, B=2, S=50, F=8, **override):
@@ -47,18 +37,6 @@ def _bwd(H, ptr, B=2, S=50, F=8, **override):
     for k, v in override.items():
         setattr(a, k, v)
     return a
-
-
-def test_entry_points_are_declared_exported_and_bound(H):
-    raw = C.CDLL(H.LIB_PATH)
-    header = open(os.path.join(ROOT, "include", "air_hip.h")).read()
-    for name, (res, nargs) in {"air_cnn_bwd_sq": (C.c_int, 3), "air_cnn_num_sq_partials": (C.c_int, 1)}.items():
-        assert "int %s(" % name in header, name
-        assert hasattr(raw, name), name
-        assert name in H.EXPORTED_SYMBOLS
-        fn = getattr(H.lib(), name)
-        assert fn.restype is res and len(fn.argtypes) == nargs, name
-    assert H.lib().air_abi_version() == H.ABI_VERSION == 6
 
 
 def test_partial_count_depends_on_filters_only(H):

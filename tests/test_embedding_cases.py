@@ -1,6 +1,5 @@
-"""CPU-side checks of the projector export (include/air_hip.h "projector export", air/embeddings.py): the entry points are
-exported and bound under ABI 6, the struct matches a C compile of the header, argument errors are answered on the host
-before any HIP call; the restatement of tests/embedding_cases.py gives the hand-worked answers and matplotlib's grey levels
+"""CPU-side checks of the projector export (include/air_hip.h "projector export", air/embeddings.py): argument errors are
+answered on the host before any HIP call; the restatement of tests/embedding_cases.py gives the hand-worked answers and matplotlib's grey levels
 (tests/golden/sprite_levels.npz, written by tests/golden/make_sprite_levels.py); write_projector's files read back; and the
 random cases the GPU tests compare exactly keep clear of rounding ties.  (What the kernels compute:
 tests/test_gpu_embeddings.py.)"""
@@ -8,64 +7,26 @@ import ctypes as C
 import math
 import os
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
+import abi_check as abi
 import embedding_cases as ec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"air_embed_collect": (C.c_int, 3), "air_embed_collect_workspace_ints": (C.c_int64, 4), "air_embed_sprites": (C.c_int, 6),
-       "air_embed_sprite_dim": (C.c_int, 1), "air_embed_sprites_workspace_doubles": (C.c_int64, 2)}
-
-
 ZEROS = dict(latents=0, windows=0, labels=0, ids=0)
 
 
 @pytest.fixture(scope="module")
 def H():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("air_build", os.path.join(ROOT, "tf-attend-infer-repeat_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.build(verbose=False)
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.hip()
 
 
-# ------------------------------------------------------------------------------------------------- symbols and structs
-def test_entry_points_are_exported_and_bound(H):
-    raw = C.CDLL(H.LIB_PATH)
-    for name, (res, nargs) in NEW.items():
-        assert hasattr(raw, name), name
-        assert name in H.EXPORTED_SYMBOLS
-        fn = getattr(H.lib(), name)
-        assert fn.restype is res and len(fn.argtypes) == nargs, name
-    assert H.lib().air_abi_version() == H.ABI_VERSION == 6
-
-
-def test_struct_layout_matches_c(H, tmp_path):
-    names = [n for n, _ in H.EmbedCollect._fields_]
-    assert names == ["att", "run_digits", "ml", "vrec", "gt_count", "gt_positions", "gt_boxes", "gt_labels", "gt_ids", "match",
-                     "counters", "out_latents", "out_windows", "out_labels", "out_ids", "T", "B", "k", "G", "Z", "w", "capacity",
-                     "canvas_size", "max_distance"]
-    items = ["AIR_EMBED_MAX_STEPS", "AIR_EMBED_MAX_DIGITS", "AIR_EMBED_MATCHED", "AIR_EMBED_PRESENT", "AIR_EMBED_INFERRED",
-             "AIR_EMBED_OVERFLOW", "AIR_EMBED_COUNTERS", "AIR_ATT_STRIDE", "AIR_ATT_X", "AIR_ATT_Y", "sizeof(air_embed_collect_t)"]
-    exp = [H.MAX_EMBED_STEPS, H.MAX_EMBED_DIGITS, H.EMBED_MATCHED, H.EMBED_PRESENT, H.EMBED_INFERRED, H.EMBED_OVERFLOW,
-           H.EMBED_COUNTERS, ec.ATT_STRIDE, ec.ATT_X, ec.ATT_Y, C.sizeof(H.EmbedCollect)]
-    for n in names:
-        items.append("offsetof(air_embed_collect_t, %s)" % n)
-        exp.append(getattr(H.EmbedCollect, n).offset)
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "air_hip.h"\nint main(){'
-                    + "".join('printf("%%zu\\n", (size_t)%s);' % it for it in items) + "return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
-    assert got == exp, (got, exp)
+# ------------------------------------------------------------------------------------------------- the library's answers
+def test_restatement_reads_the_record_slots_of_the_binding(H):
+    """(which are the header's: tests/test_abi.py)"""
     assert (H.ATT_STRIDE, H.ATT_X, H.ATT_Y) == (ec.ATT_STRIDE, ec.ATT_X, ec.ATT_Y)
 
 

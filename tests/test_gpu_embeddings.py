@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
 import embedding_cases as ec
 from oracle import air_oracle as ao
 from oracle.synth import blob_canvases
@@ -30,11 +31,7 @@ CASES = ec.gpu_cases()
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 def _dev(a):

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
 import gemm_edge_cases as gec
 from test_gpu_kernels import _bf16_round, _ref_gemm
 
@@ -34,11 +35,7 @@ MAXERR = {}                                       # group -> largest error / tol
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 def _stream():

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -64,11 +66,7 @@ def check(got, ref, what):
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 def records(H, raw, count):

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
+
 pytestmark = pytest.mark.gpu
 
 from oracle import air_oracle as ao  # noqa: E402
@@ -14,11 +16,7 @@ from oracle import air_oracle as ao  # noqa: E402
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 def _p(t):

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
 from oracle import air_oracle as ao
 from test_gpu_kernels import _panel_ref
 
@@ -42,11 +43,7 @@ LR, B1, B2, EPS = (float(np.float32(x)) for x in (1e-2, 0.9, 0.999, 1e-8))      
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 @pytest.fixture(scope="module")

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
 import step_limit_cases as slc
 from oracle import air_oracle as ao
 from oracle import air_oracle_torch as at
@@ -16,16 +17,10 @@ from oracle.synth import blob_canvases
 
 pytestmark = pytest.mark.gpu
 
-AIR_EINVAL = -1
-
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 @pytest.fixture(scope="module")
@@ -154,7 +149,7 @@ def test_wout_stride_below_the_widest_head_is_refused(H):
     (every output keeps what it held)"""
     case, ref = slc.attend_case_and_reference(50, 28, (5, 17, 33), 1)
     short = dict(case, wout_ld=32, wout=np.zeros((7, 33), np.float32))
-    got = _attend_fwd(H, short, expect=AIR_EINVAL)
+    got = _attend_fwd(H, short, expect=H.EINVAL)
     assert np.isnan(got["out7"]).all() and np.isnan(got["att"]).all() and np.isnan(got["window"]).all()
     assert (got["window16"] == SENTINEL16).all()
     N, B, w, HT = case["N"], case["B"], case["w"], case["HT"]
@@ -165,9 +160,9 @@ def test_wout_stride_below_the_widest_head_is_refused(H):
     d_hid, d_out7 = torch.full((N, B, HT), 7.0, device="cuda"), torch.full((N, B, H.OUT_STRIDE), 7.0, device="cuda")
     ab = H.AttendBwd(_p(d["hid"]), _p(wout), _p(d["canvas"]), _p(d["eps_scale"]), _p(d["eps_shift"]), _p(d["dyn"]), _p(out7),
                      _p(att), _p(d_win), _p(d_sxy), _p(d_hid), _p(d_out7), B, N, 50, w, 5, 17, 33, 32, 0)
-    assert H.lib().air_attend_bwd(C.byref(ab), _stream()) == AIR_EINVAL
+    assert H.lib().air_attend_bwd(C.byref(ab), _stream()) == H.EINVAL
     dwout, dbout = torch.full((7, 33), 7.0, device="cuda"), torch.full((7,), 7.0, device="cuda")
-    assert H.lib().air_heads_out_wgrad(_p(d_out7), _p(d["hid"]), _p(dwout), _p(dbout), N * B, 5, 17, 33, 32, _stream()) == AIR_EINVAL
+    assert H.lib().air_heads_out_wgrad(_p(d_out7), _p(d["hid"]), _p(dwout), _p(dbout), N * B, 5, 17, 33, 32, _stream()) == H.EINVAL
     torch.cuda.synchronize()
     for t in (d_hid, d_out7, dwout, dbout):
         assert bool((t == 7.0).all())

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
 import step_prologue_cases as spc
 import test_gpu_gemm_edges as tge
 from oracle import air_oracle as ao
@@ -43,11 +44,7 @@ SCHED_DTYPE = [("slot", "<i4"), ("flags", "<i4"), ("init", "<f4"), ("iters", "<f
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 def _p(t):

@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
+
 pytestmark = pytest.mark.gpu
 
 from oracle import air_oracle as ao  # noqa: E402
@@ -21,11 +23,7 @@ PADDED, PADDED_REGISTERS = 2, 3                  # air_gemm_t.i0 of AIR_EPI_LSTM
 
 @pytest.fixture(scope="module")
 def H():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.gpu_hip()
 
 
 @pytest.fixture(scope="module")

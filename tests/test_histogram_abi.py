@@ -1,44 +1,25 @@
-"""CPU-side checks of the histogram summaries (include/air_hip.h "histogram summaries", air/summaries.py): the entry points
-are exported and bound under ABI 6, the bucket limits are TensorFlow 1.3's bit for bit, the two structs match a C compile of
-the header, argument errors are answered on the host before any HIP call and alike by all three descriptor-taking calls, and
+"""CPU-side checks of the histogram summaries (include/air_hip.h "histogram summaries", air/summaries.py): the bucket limits
+are TensorFlow 1.3's bit for bit, argument errors are answered on the host before any HIP call and alike by all three
+descriptor-taking calls, and
 the tag function gives the four tag lists of the reference's graph (tests/golden/summary_tags.json, written by
 tests/golden/make_summary_tags.py).  (What the kernels compute: tests/test_gpu_histograms.py.)"""
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_check as abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"air_histogram_num_buckets": (C.c_int, 0), "air_histogram_limits": (C.c_int, 1), "air_histogram_chunk": (C.c_int, 0),
-       "air_histogram_record_bytes": (C.c_int64, 0), "air_histograms_output_bytes": (C.c_int64, 2),
-       "air_histograms_workspace_bytes": (C.c_int64, 2), "air_histograms": (C.c_int, 2)}
 
 
 @pytest.fixture(scope="module")
 def H():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("air_build", os.path.join(ROOT, "tf-attend-infer-repeat_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.build(verbose=False)
-    from air import _hip
-    _hip.lib()
-    return _hip
-
-
-def test_entry_points_are_exported_and_bound(H):
-    raw = C.CDLL(H.LIB_PATH)
-    for name, (res, nargs) in NEW.items():
-        assert hasattr(raw, name), name
-        assert name in H.EXPORTED_SYMBOLS
-        fn = getattr(H.lib(), name)
-        assert fn.restype is res and len(fn.argtypes) == nargs, name
-    assert H.lib().air_abi_version() == H.ABI_VERSION == 6
+    return abi.hip()
 
 
 def test_limits_are_tensorflows(H):
@@ -63,26 +44,8 @@ def test_limits_are_tensorflows(H):
     assert H.lib().air_histogram_chunk() % 4 == 0 and H.lib().air_histogram_chunk() >= 256
 
 
-def test_struct_layout_matches_c(H, tmp_path):
-    fields = {"air_histogram_desc_t": (H.HistogramDesc, ("base", "rows", "cols", "ld", "scale_kind")),
-              "air_histograms_t": (H.Histograms, ("descs", "count", "prescale", "dyn", "gnorm", "out", "workspace", "out_bytes",
-                                                  "workspace_bytes"))}
-    items, exp = ["AIR_HISTOGRAM_MAX"], [H.MAX_HISTOGRAMS]
-    for cname, (struct, names) in fields.items():
-        assert [n for n, _ in struct._fields_] == list(names)
-        items.append("sizeof(%s)" % cname)
-        exp.append(C.sizeof(struct))
-        for n in names:
-            items.append("offsetof(%s, %s)" % (cname, n))
-            exp.append(getattr(struct, n).offset)
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "air_hip.h"\nint main(){'
-                    + "".join('printf("%%zu\\n", (size_t)%s);' % it for it in items) + "return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
-    assert got == exp, (got, exp)
-    assert C.sizeof(H.HistogramDesc) == 24
+def test_descriptor_is_24_bytes(H):
+    assert C.sizeof(H.HistogramDesc) == 24            # the documented size (its layout: tests/test_abi.py, with every other)
 
 
 def _descs(H, n=2, **override):

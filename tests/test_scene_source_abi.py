@@ -1,62 +1,26 @@
-"""CPU-side checks of the scene source (include/air_hip.h: air_scene_source_*, multi_mnist.DeviceSceneSource): the entry
-points are exported and bound, the descriptor matches a C compile of the header, every refusal is answered on the host
-before any launch (null device pointers throughout), the Python class refuses what only the host generator has, and the
+"""CPU-side checks of the scene source (include/air_hip.h: air_scene_source_*, multi_mnist.DeviceSceneSource): every refusal
+is answered on the host before any launch (null device pointers throughout), the Python class refuses what only the host
+generator has, and the
 device's overlap rule -- as tests/scene_source_cases.py restates it -- accepts exactly the placements the generator's
 pixels_overlap / add_buffer accept.  (What the kernel computes: tests/test_gpu_scene_source.py.)"""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_check as abi
 import scene_source_cases as sc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"air_scene_source_compose": (C.c_int, 3), "air_scene_source_advance": (C.c_int, 3),
-       "air_scene_source_prepare": (C.c_int, 1), "air_scene_source_lds": (C.c_int64, 2)}
-FIELDS = ["glyphs", "crops", "bg", "counts", "batch_counter", "images", "digits", "indices", "positions", "boxes", "status",
-          "gave_up", "B", "G", "gd", "C", "margin", "gap", "max_digits", "max_attempts", "max_restarts", "seed"]
-EINVAL, ELIMIT = -1, -2
 
 
 @pytest.fixture(scope="module")
 def H():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("air_build", os.path.join(ROOT, "tf-attend-infer-repeat_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.build(verbose=False)
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.hip()
 
 
-def test_entry_points_are_exported_and_bound(H):
-    raw = C.CDLL(H.LIB_PATH)
-    for name, (res, nargs) in NEW.items():
-        assert hasattr(raw, name), name
-        assert name in H.EXPORTED_SYMBOLS
-        fn = getattr(H.lib(), name)
-        assert fn.restype is res and len(fn.argtypes) == nargs, name
-    assert H.lib().air_abi_version() == H.ABI_VERSION == 6          # additive: the version stays
-
-
-def test_descriptor_layout_matches_c(H, tmp_path):
-    items = ["sizeof(air_scene_source_t)"] + ["offsetof(air_scene_source_t, %s)" % n for n in FIELDS]
-    exp = [C.sizeof(H.SceneSource)] + [getattr(H.SceneSource, n).offset for n in FIELDS]
-    limits = ["AIR_SCENE_MAX_CANVAS", "AIR_SCENE_MAX_GLYPH", "AIR_SCENE_MAX_DIGITS", "AIR_SCENE_MAX_GAP",
-              "AIR_SCENE_MAX_ATTEMPTS", "AIR_SCENE_MAX_RESTARTS"]
-    exp += [H.SCENE_MAX_CANVAS, H.SCENE_MAX_GLYPH, H.SCENE_MAX_DIGITS, H.SCENE_MAX_GAP, H.SCENE_MAX_ATTEMPTS, H.SCENE_MAX_RESTARTS]
-    prog = tmp_path / "layout.c"
-    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "air_hip.h"\nint main(){'
-                    + "".join('printf("%%zu\\n", (size_t)%s);' % it for it in items + limits) + "return 0;}")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
-    got = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
-    assert got == exp, (got, exp)
-    assert [n for n, _ in H.SceneSource._fields_] == FIELDS
-    assert exp[-6:] == [128, 32, 6, 4, 100, 64]
+def test_limits_are_the_documented_ones(H):
+    """(that they are the header's, and the descriptor's layout: tests/test_abi.py, with every other)"""
+    assert [H.SCENE_MAX_CANVAS, H.SCENE_MAX_GLYPH, H.SCENE_MAX_DIGITS, H.SCENE_MAX_GAP, H.SCENE_MAX_ATTEMPTS,
+            H.SCENE_MAX_RESTARTS] == [128, 32, 6, 4, 100, 64]
 
 
 def _desc(H, **override):
@@ -71,44 +35,43 @@ def _desc(H, **override):
 def test_every_refusal_comes_before_a_launch(H):
     lib = H.lib()
     for fn in (lambda a: lib.air_scene_source_compose(C.byref(a), 0, None), lambda a: lib.air_scene_source_prepare(C.byref(a))):
-        assert fn(_desc(H, C=129)) == ELIMIT
-        assert fn(_desc(H, gd=33)) == ELIMIT
-        assert fn(_desc(H, max_digits=7)) == ELIMIT
-        assert fn(_desc(H, gap=5)) == ELIMIT
-        assert fn(_desc(H, max_attempts=0)) == EINVAL
-        assert fn(_desc(H, max_attempts=101)) == ELIMIT
-        assert fn(_desc(H, max_restarts=0)) == EINVAL
-        assert fn(_desc(H, max_restarts=65)) == ELIMIT
-        assert fn(_desc(H, B=0)) == EINVAL
-        assert fn(_desc(H, B=-4)) == EINVAL
-        assert fn(_desc(H, margin=25)) == EINVAL                    # 2 * 25 + 1 > 50: not even one pixel fits
-        assert fn(_desc(H, C=16, margin=8)) == EINVAL
+        assert fn(_desc(H, C=129)) == H.ELIMIT
+        assert fn(_desc(H, gd=33)) == H.ELIMIT
+        assert fn(_desc(H, max_digits=7)) == H.ELIMIT
+        assert fn(_desc(H, gap=5)) == H.ELIMIT
+        assert fn(_desc(H, max_attempts=0)) == H.EINVAL
+        assert fn(_desc(H, max_attempts=101)) == H.ELIMIT
+        assert fn(_desc(H, max_restarts=0)) == H.EINVAL
+        assert fn(_desc(H, max_restarts=65)) == H.ELIMIT
+        assert fn(_desc(H, B=0)) == H.EINVAL
+        assert fn(_desc(H, B=-4)) == H.EINVAL
+        assert fn(_desc(H, margin=25)) == H.EINVAL                    # 2 * 25 + 1 > 50: not even one pixel fits
+        assert fn(_desc(H, C=16, margin=8)) == H.EINVAL
         for k in ("G", "gd", "C", "max_digits"):
-            assert fn(_desc(H, **{k: 0})) == EINVAL, k
-        assert fn(_desc(H, margin=-1)) == EINVAL and fn(_desc(H, gap=-1)) == EINVAL
-        assert fn(_desc(H, B=0, C=129)) == EINVAL                   # an invalid size is reported before a limit
+            assert fn(_desc(H, **{k: 0})) == H.EINVAL, k
+        assert fn(_desc(H, margin=-1)) == H.EINVAL and fn(_desc(H, gap=-1)) == H.EINVAL
+        assert fn(_desc(H, B=0, C=129)) == H.EINVAL                   # an invalid size is reported before a limit
         # the limits themselves pass the size checks: what is left to refuse is the null pointers
-        assert fn(_desc(H, C=128, gd=32, max_digits=6, gap=4, max_attempts=100, max_restarts=64, margin=63)) == EINVAL
-    assert lib.air_scene_source_compose(None, 0, None) == EINVAL and lib.air_scene_source_prepare(None) == EINVAL
-    assert lib.air_scene_source_compose(C.byref(_desc(H)), -1, None) == EINVAL
-    assert lib.air_scene_source_advance(None, 1, None) == EINVAL
+        assert fn(_desc(H, C=128, gd=32, max_digits=6, gap=4, max_attempts=100, max_restarts=64, margin=63)) == H.EINVAL
+    assert lib.air_scene_source_compose(None, 0, None) == H.EINVAL and lib.air_scene_source_prepare(None) == H.EINVAL
+    assert lib.air_scene_source_compose(C.byref(_desc(H)), -1, None) == H.EINVAL
+    assert lib.air_scene_source_advance(None, 1, None) == H.EINVAL
     buf = (C.c_int64 * 1)()
-    assert lib.air_scene_source_advance(C.addressof(buf), -1, None) == EINVAL
+    assert lib.air_scene_source_advance(C.addressof(buf), -1, None) == H.EINVAL
 
 
 def test_each_required_pointer_is_required(H):
     """with every size in range, each null required pointer alone is AIR_EINVAL (bg, counts and gave_up are optional); the
     call with all of them set is not made here -- it would launch"""
     lib = H.lib()
-    buf = (C.c_char * 64)()
-    p = C.addressof(buf) + (-C.addressof(buf)) % 16
+    p = abi.host_ptr().value
     required = ("glyphs", "crops", "batch_counter", "images", "digits", "indices", "positions", "boxes", "status")
     for missing in required:
         a = _desc(H, **{k: p for k in required if k != missing})
-        assert lib.air_scene_source_compose(C.byref(a), 0, None) == EINVAL, missing
+        assert lib.air_scene_source_compose(C.byref(a), 0, None) == H.EINVAL, missing
     a = _desc(H, **{k: p for k in required})
     a.crops = p + 4
-    assert lib.air_scene_source_compose(C.byref(a), 0, None) == -3       # a crop box is one 16-byte load
+    assert lib.air_scene_source_compose(C.byref(a), 0, None) == H.EALIGN      # a crop box is one 16-byte load
 
 
 def test_lds_query(H):
@@ -117,7 +80,7 @@ def test_lds_query(H):
     for Cv, gd in ((50, 28), (16, 8), (15, 7), (128, 32), (1, 1)):
         assert lds(Cv, gd) == up16(4 * Cv * Cv) + up16(4 * gd * gd) + up16(Cv * Cv) + 160, (Cv, gd)
     assert lds(128, 32) == 86176
-    assert lds(129, 8) == ELIMIT and lds(50, 33) == ELIMIT and lds(0, 8) == EINVAL and lds(50, 0) == EINVAL
+    assert lds(129, 8) == H.ELIMIT and lds(50, 33) == H.ELIMIT and lds(0, 8) == H.EINVAL and lds(50, 0) == H.EINVAL
 
 
 def test_python_class_refuses_jitter_and_box_overlap(H):

@@ -1,54 +1,32 @@
-"""CPU-side checks of the multi-channel transformer entry points (air_transformer_nc_fwd, air_transformer_nc_bwd): exported
-and bound, argument and limit errors reported on the host before any launch, the Python ops importable and without a CPU
-fallback.  (That a shape with more channels than fit the LDS at once is accepted needs a launch: it is
+"""CPU-side checks of the multi-channel transformer entry points (air_transformer_nc_fwd, air_transformer_nc_bwd): argument and
+limit errors reported on the host before any launch, the Python ops importable and without a CPU fallback.  (That a shape
+with more channels than fit the LDS at once is accepted needs a launch: it is
 tests/test_gpu_transformer_channels.py::test_more_channels_than_a_workgroup_holds.)"""
 import ctypes as C
-import os
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("air_transformer_nc_fwd", "air_transformer_nc_bwd")
+import abi_check as abi
+
 SIZES = ("B", "T", "Hi", "Wi", "C", "Ho", "Wo")
 GOOD = dict(B=3, T=2, Hi=9, Wi=11, C=3, Ho=7, Wo=8)
 
 
 @pytest.fixture(scope="module")
 def H():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("air_build", os.path.join(ROOT, "tf-attend-infer-repeat_amd", "build.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.build(verbose=False)
-    from air import _hip
-    _hip.lib()
-    return _hip
+    return abi.hip()
 
 
 @pytest.fixture()
 def ptr():
-    """a 16-byte aligned non-null address (never dereferenced: every call below returns before a launch)"""
-    buf = (C.c_char * 272)()
-    base = C.addressof(buf)
-    yield C.c_void_p(base + (-base) % 16)
-    del buf
+    return abi.host_ptr()
 
 
 def _sizes(**kw):
     s = dict(GOOD)
     s.update(kw)
     return [s[k] for k in SIZES]
-
-
-def test_entry_points_are_exported_and_bound(H):
-    raw = C.CDLL(H.LIB_PATH)
-    for name in NEW:
-        assert hasattr(raw, name), name
-        assert name in H.EXPORTED_SYMBOLS
-        fn = getattr(H.lib(), name)
-        assert fn.restype is C.c_int and fn.argtypes is not None and len(fn.argtypes) == (11 if name.endswith("fwd") else 13)
-    assert H.lib().air_abi_version() == H.ABI_VERSION == 6
 
 
 def test_forward_argument_errors(H, ptr):

@@ -15,9 +15,10 @@ import torch  # noqa: F401  -- FIRST: torch brings its own libamdhip64; loading 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AIR_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libair_hip.so")   # override: A/B builds in tools/
 
+# Every upper-case integer constant X below is AIR_X of include/air_hip.h, and every Structure the CamelCase of its
+# air_*_t: tests/test_abi.py compares all of them, and _SIGNATURES, with the header.
 ABI_VERSION = 6
-
-# enums (keep in sync with include/air_hip.h)
+EINVAL, ELIMIT, EALIGN = -1, -2, -3
 DYN_PRIOR_LOG_ODDS, DYN_TEMPERATURE, DYN_STOP_THRESHOLD, DYN_LEARNING_RATE, DYN_CLIP_NORM = 0, 1, 2, 3, 4
 DYN_SCALE_PM, DYN_SCALE_PV, DYN_SHIFT_PM, DYN_SHIFT_PV, DYN_VAE_PM, DYN_VAE_PV = 5, 6, 7, 8, 9, 10
 DYN_LIK_STD, DYN_GRAD_SCALE, DYN_COUNT = 11, 12, 16
@@ -166,7 +167,7 @@ class CnnBwd(C.Structure):
                 ("B", _i), ("S", _i), ("F", _i)]
 
 
-MAX_HISTOGRAMS = 128          # AIR_HISTOGRAM_MAX
+HISTOGRAM_MAX = 128
 
 
 class HistogramDesc(C.Structure):
@@ -181,7 +182,7 @@ class Histograms(C.Structure):
                 ("out", _p), ("workspace", _p), ("out_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
 
 
-MAX_EMBED_STEPS = MAX_EMBED_DIGITS = 16      # AIR_EMBED_MAX_STEPS, AIR_EMBED_MAX_DIGITS
+EMBED_MAX_STEPS = EMBED_MAX_DIGITS = 16
 EMBED_MATCHED, EMBED_PRESENT, EMBED_INFERRED, EMBED_OVERFLOW, EMBED_COUNTERS = 0, 1, 2, 3, 4
 
 

@@ -436,7 +436,7 @@ class AIRModel:
         if cnn:
             # the conv front-end (reference :510-533): the limits of its kernels, as the library answers them
             rc = self.lib.air_cnn_workspace_floats(self.batch_size, int(canvas_size), int(cnn_filters))
-            if rc == -2:
+            if rc == H.ELIMIT:
                 raise NotImplementedError("cnn=True: canvas_size = %d with cnn_filters = %d exceeds the HIP path's limits (cnn_filters "
                                           "<= 8; canvas_size <= 77 at 8 filters .. <= 128 at 1 or 2: the planes of an image live "
                                           "in LDS)" % (canvas_size, cnn_filters))

@@ -37,7 +37,7 @@ def _check_sizes(canvas_size, filters):
     """the library's own answer for (S, F) -- no GPU is touched"""
     S, F = int(canvas_size), int(filters)
     rc = H.lib().air_cnn_workspace_floats(1, S, F)
-    if rc == -2:
+    if rc == H.ELIMIT:
         raise NotImplementedError("cnn: canvas_size = %d with filters = %d is beyond what the kernels hold in LDS "
                                   "(filters <= 8; canvas_size <= 77 at 8 filters, <= 128 at 1 or 2)" % (S, F))
     if rc < 0:

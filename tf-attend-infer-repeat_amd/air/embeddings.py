@@ -64,7 +64,7 @@ def collect(model, images, digits, indices, positions, boxes, labels, max_distan
     rc = H.lib().air_embed_collect_workspace_ints(T, B, B, G)
     if rc < 0:
         raise NotImplementedError("embeddings.collect: %d steps, %d digits in one image: the kernel holds %d and %d"
-                                  % (T, G, H.MAX_EMBED_STEPS, H.MAX_EMBED_DIGITS))
+                                  % (T, G, H.EMBED_MAX_STEPS, H.EMBED_MAX_DIGITS))
     chunks = -(-n // B)
     rows = chunks * B                              # the last chunk is padded with blank canvases without ground truth
 

@@ -33,11 +33,11 @@ __device__ __forceinline__ float air_u01_half_open(uint32_t x) { return (float)(
 // air_model.py:94-121: exponential_decay(init, step, iters, factor, staircase) -> max(min) -> min(max) -> log(.+eps)
 __device__ __forceinline__ float air_eval_schedule(const air_schedule_t& s, int step) {
     float p = (float)step / s.iters;
-    if (s.flags & 1) p = floorf(p);
+    if (s.flags & AIR_SCHED_STAIRCASE) p = floorf(p);
     float v = s.init * powf(s.factor, p);
-    if (s.flags & 2) v = fmaxf(v, s.vmin);
-    if (s.flags & 4) v = fminf(v, s.vmax);
-    if (s.flags & 8) v = logf(v + AIR_EPS);
+    if (s.flags & AIR_SCHED_HAS_MIN) v = fmaxf(v, s.vmin);
+    if (s.flags & AIR_SCHED_HAS_MAX) v = fminf(v, s.vmax);
+    if (s.flags & AIR_SCHED_LOG) v = logf(v + AIR_EPS);
     return v;
 }
 
