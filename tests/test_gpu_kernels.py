@@ -1132,7 +1132,12 @@ def test_gemm_ragged_shapes_keep_the_fp32_operand_kernels(H):
                                                   [(784, 512, 1280), (104, 200, 400), (64, 64, 384), (72, 136, 520)],
                                                   # the gathered-factor contraction of dp_exchange="factors" at world 8:
                                                   # dWx over K = 8 x 64 rows (configs[2]) and 8 x 256 (stress canvases)
-                                                  [(2500, 1024, 512)], [(16384, 1024, 2048)]])
+                                                  [(2500, 1024, 512)], [(16384, 1024, 2048)]] +
+                                                 # every strip instance at the smallest strip problem (512 tiles): K / 32
+                                                 # pieces per thread for K = 64 .. 256, the A block in 16-byte pieces with
+                                                 # the per-XCD tile map (M = 2048: 32 block-rows) and in masked 8-byte
+                                                 # pieces with a ragged last block-row (M = 2052: 33 block-rows)
+                                                 [[(2048, 1024, K), (2052, 1024, K)] for K in (64, 128, 192, 256)])
 def test_wgrad_grouped_bf16_twins_bit_identical(H, shapes):
     """air_wgrad_grouped(precision=1) with bf16 twins of A and dY (air_wgrad_t.A16 / dY16) against the same
     launch without them: dW, db and the global-norm partials BIT-IDENTICAL.  Covers 16-byte rows (ld % 8 == 0),

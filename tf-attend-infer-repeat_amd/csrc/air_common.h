@@ -73,6 +73,16 @@ __device__ __forceinline__ unsigned air_pack_bf16(float lo, float hi) {
 }
 __device__ __forceinline__ unsigned short air_bf16_of(float v) { return (unsigned short)(air_pack_bf16(v, 0.0f) & 0xffffu); }
 
+// The seven output units of the heads (air_model.py:294-316, 376): unit -> head, head -> (offset, width) of its segment of
+// the packed hidden row [Hs | Hs | Hh | Hh | Hz].  As arithmetic: a table in constant memory indexed per lane, then a
+// dynamically indexed segment table (which the compiler keeps in scratch memory) were two dependent memory round trips on
+// attend_fwd's critical path
+__device__ __forceinline__ constexpr int air_out_head(int o) { return o < 2 ? o : (o < 4 ? 2 : (o < 6 ? 3 : 4)); }
+__device__ __forceinline__ int air_head_wid(int Hs, int Hh, int Hz, int h) { return h < 2 ? Hs : (h < 4 ? Hh : Hz); }
+__device__ __forceinline__ int air_head_off(int Hs, int Hh, int h) {
+    return h == 0 ? 0 : h == 1 ? Hs : h == 2 ? 2 * Hs : h == 3 ? 2 * Hs + Hh : 2 * Hs + 2 * Hh;
+}
+
 // wave64 butterfly sum: every lane ends with the total
 __device__ __forceinline__ float air_wave_sum(float v) {
 #pragma unroll

@@ -4,14 +4,15 @@
 // -- inline device code in namespace airg -- and, at the end, the host's dispatch plan.
 #pragma once
 #include "air_common.h"
+#include "air_mfma.h"
 #include "air_philox.h"
 #include "air_lstm_cell.h"
 #include <type_traits>
 
 namespace airg {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+using airm::f32x4; using airm::bf16x8; using airm::s16x4;
+using airm::zero_acc; using airm::read_tr_bf16x8; using airm::aligned16; using airm::aligned8;      // air_mfma.h
 
 constexpr int THREADS = 256;
 // internal epilogue id (never in the ABI): AIR_EPI_LSTM_FWD on 16-column tiles of FOUR units x four gates (column
@@ -385,9 +386,6 @@ __device__ __forceinline__ void xcd_tile(int& tile_m, int& tile_n) {
     tile_n = swz / ny;
 }
 
-__host__ __device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-__host__ __device__ __forceinline__ bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 // ---- the skeleton the tiled kernels share.  What differs between families -- the global -> LDS staging -- stays in
 // the family; a new staging variant is one staging function beside the others, around these parts.
 // (gemm_bf16v2_kernel, air_gemm.hip, does not use them: with them its large tiles measured 1.3 .. 3 % slower, DESIGN.md
@@ -431,14 +429,6 @@ __device__ __forceinline__ Frame frame_of(const Args& a) {
     return f;
 }
 
-template <int TM, int TN>
-__device__ __forceinline__ void zero_acc(f32x4 (&acc)[TM][TN]) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
 // the lean kernels load 16 bytes as two 8-byte halves when an operand is only 8-byte aligned (ldg16x<HALF>):
 // row strides / column-group strides that are even but not multiples of 4 (Z = 50)
 __device__ __forceinline__ bool halves_a(const Args& a) { return !(((a.lda & 3) == 0) && aligned16(a.A) && ((a.K & 3) == 0)); }
@@ -472,17 +462,6 @@ __device__ __forceinline__ void store_slab(const Args& a, const float* Red, int 
             if (m < a.M && n < a.N) Cz[(size_t)m * a.ldc + n] = Red[(t * 4 + q) * 64 + lane];
         }
     }
-}
-
-// gfx950 transpose read ds_read_b64_tr_b16, twice: from a [k][BN] bf16 image, lane i of a 16-lane group hands in the
-// address of row 8g + i/4 (+4), column quad i%4 of the [k][16] block (blk); it receives k = 8g .. 8g+3 (+4) of
-// column i -- the 8 consecutive k v_mfma_f32_16x16x32_bf16 wants
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bf16x8 read_tr_bf16x8(const unsigned short* blk, int BN) {
-    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(blk + 4 * BN));
-    return bf16x8{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 }
 
 // MFMAs of one round of R 64-deep bf16 image pairs, ImgA = [R][BM][64 k] with the 16-byte slots of a row XOR-swizzled by

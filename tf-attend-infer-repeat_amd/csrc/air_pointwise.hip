@@ -238,16 +238,13 @@ __global__ __launch_bounds__(THREADS) void heads_out_wgrad_kernel(
     __shared__ float part[4][64];
     __shared__ float red[4];
     const int o = blockIdx.x;
-    const int head[7] = {0, 1, 2, 2, 3, 3, 4};
-    const int wid[5] = {Hs, Hs, Hh, Hh, Hz};
-    int off = 0;
-    for (int i = 0; i < head[o]; ++i) off += wid[i];
+    const int hd = air_out_head(o), wd = air_head_wid(Hs, Hh, Hz, hd), off = air_head_off(Hs, Hh, hd);
     const int HT = 2 * Hs + 2 * Hh + Hz;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int j0 = 0; j0 < wid[head[o]]; j0 += 64) {
+    for (int j0 = 0; j0 < wd; j0 += 64) {
         const int j = j0 + lane;
         float acc = 0.0f;
-        if (j < wid[head[o]]) {
+        if (j < wd) {
             int r = wave;
             for (; r + 28 < rows; r += 32) {
                 float a[8], h[8];
@@ -264,7 +261,7 @@ __global__ __launch_bounds__(THREADS) void heads_out_wgrad_kernel(
         __syncthreads();
         part[wave][lane] = acc;
         __syncthreads();
-        if (wave == 0 && j < wid[head[o]])
+        if (wave == 0 && j < wd)
             dw[o * ld + j] = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
     }
     float s = 0.0f;
