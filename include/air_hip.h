@@ -988,6 +988,71 @@ int air_scene_source_prepare(const air_scene_source_t* a);
 /* bytes of dynamic LDS per workgroup, or AIR_EINVAL / AIR_ELIMIT for a (C, gd) the entry point refuses -- no GPU is touched */
 int64_t air_scene_source_lds(int C, int gd);
 
+/* ---- glyph bank: scale and rotation jitter (additive to ABI 6) -----------------------------------------------------------
+ * The two jitter options of the reference's generate_multi_image (multi_mnist.py:113-135) as ONE launch that turns the base
+ * glyphs into V jittered variants with their crop boxes: a bank the scene source draws from in place of the glyph set
+ * (bank / bank_crops are its glyphs / crops, with gd = od).  multi_mnist.DeviceGlyphBank is the caller.
+ *
+ * One variant, by one workgroup, its planes in LDS.  The bank generation is *counter (null: 0; air_scene_source_advance
+ * moves it).  Draw j of variant v is word j & 3 of Philox4x32-10(key = (seed low, seed high), counter = (v, j >> 2,
+ * (uint32_t)generation, 0x474A4954)).  Word 0 picks the base glyph g = umulhi(word, G).  A real takes two words:
+ * u = ((a >> 5) * 2^26 + (b >> 6)) / 2^53, value = lo + (hi - lo) * u in fp64.  Only when one of the four scale bounds is
+ * not 1.0: new_width, then new_height.  Then, only when one of the two angle bounds is not 0.0: angle (degrees).
+ *   Scale (:117-126): the base glyph's crop box (h x w) through the transform below with matrix diag(1 / new_height,
+ *   1 / new_width), offset 0, onto a plane of int(gd * new_height) x int(gd * new_width).
+ *   Rotation (:128-135, scipy.ndimage.rotate(reshape=True)): c, s = cos, sin of the angle (fp64, on the device: the angle
+ *   less its nearest multiple of 90 is exact, sincospi of that / 180, the quadrant put back by sign and swap);
+ *   R = (c s; -s c); plane = int(ptp(R (0 0 h h; 0 w 0 w), axis 1) + 0.5); offset = (in - 1) / 2 - R ((plane - 1) / 2).
+ *   Each stage's result is rounded to float32, clipped to [0, 1], values < 0.05 set to 0, cropped to its non-empty box.
+ * status[v]: 0 usable; 1 a stage left nothing (or the base crop box is empty or leaves its gd x gd frame); 2 a plane outside
+ * its limit (scaled side not in 1 .. AIR_JITTER_MAX_PLANE, rotated side not in 1 .. 64) or a final box larger than od.  A
+ * non-zero status writes an all-zero frame and an all-zero crop box: the scene kernel restarts a scene that draws it, which
+ * is what the reference's IndexError path does (:177).
+ *
+ * The transform is scipy's affine_transform(order=5, mode='constant', cval=0, prefilter=True), fp64 throughout:
+ *   prefilter: along axis 0, then axis 1; a line of n = 1 is left alone; poles z1 = sqrt(67.5 - sqrt(4436.25)) + sqrt(26.25)
+ *   - 6.5, z2 = sqrt(67.5 + sqrt(4436.25)) - sqrt(26.25) - 6.5 (computed on the host); the line times
+ *   gain = prod (1 - z)(1 - 1 / z); then per pole: zn = z^(n-1) by repeated multiplication, c0 = c[0] + zn c[n-1], for
+ *   i = 1 .. n-2: c0 += z^i (c[i] + zn c[n-1-i]), c[0] = c0 / (1 - zn zn); c[i] += z c[i-1]; c[n-1] = (z c[n-2] + c[n-1]) z /
+ *   (z z - 1); c[i] = z (c[i+1] - c[i]) from n-2 down to 0.
+ *   evaluation: cc = (oy m00 + ox m01) + offset per axis; a coordinate < 0 or > len - 1 gives 0; taps floor(cc) - 2 .. + 3
+ *   per axis, mirrored with period 2n - 2; weights at x = cc - floor(cc): w2 = t (t (0.25 - x / 12) - 0.5) + 0.55, t = x x;
+ *   w3 the same in 1 - x; w1 = y (y (y (y (y / 24 - 0.375) + 1.25) - 1.75) + 0.625) + 0.425, y = x + 1; w4 the same in 2 - x;
+ *   w0 = y t t / 120, y = 1 - x, t = y y; w5 = 1 - ((((w0 + w1) + w2) + w3) + w4).
+ *   SUMMATION ORDER of the 36 products: t = 0; for tap row 0 .. 5 (top first), for tap column 0 .. 5 (left first):
+ *   t = t + (coefficient * wy[row]) * wx[column].
+ *
+ * Outputs (every element is written): bank [V, od * od] float32, the variant's final crop at the top-left of its od x od
+ * frame, +0 elsewhere; bank_crops [V, 4] = (0, 0, w, h), or zeros; source [V], the base glyph; params [V, 6] fp64: new_width,
+ * new_height, angle, c, s, 0 (1, 1, 0, 1, 0 for what was not drawn); status [V].
+ *
+ * Limits, answered on the host before any HIP call, an invalid size before a limit, a limit before a null pointer.
+ * AIR_EINVAL: a null descriptor; V, G, gd or od < 1; od < gd; a bound that is not finite; min > max; a scale bound <= 0;
+ * int(gd * min_h) or int(gd * min_w) < 1; then a null pointer (counter may be null).  AIR_ELIMIT: gd or od >
+ * AIR_SCENE_MAX_GLYPH; int(gd * max_h) or int(gd * max_w) > AIR_JITTER_MAX_PLANE; |angle bound| > 180.  AIR_EALIGN: crops
+ * or bank_crops not 16-byte aligned, params not 8-byte aligned.  Dynamic LDS: air_glyph_jitter_lds(gd, od) = 8 * 48 * 48
+ * (coefficients) + 4 * 64 * 64 (the image so far) + 32 (boxes) = 34 848 bytes at every accepted (gd, od): below 48 KiB, so
+ * no grant and nothing for air_glyph_jitter_prepare to do but the checks. */
+typedef struct {
+    const float* glyphs;                 /* [G, gd * gd]                                                                */
+    const int32_t* crops;                /* [G, 4] x0, y0, w, h                                                         */
+    const int64_t* counter;              /* nullable: one device int64, the bank generation                             */
+    float* bank;                         /* out [V, od * od]                                                            */
+    int32_t* bank_crops;                 /* out [V, 4]                                                                  */
+    int32_t* source;                     /* out [V]                                                                     */
+    double* params;                      /* out [V, 6]                                                                  */
+    int32_t* status;                     /* out [V]                                                                     */
+    int32_t V, G, gd, od;
+    double min_w, max_w, min_h, max_h, min_ang, max_ang;
+    uint64_t seed;
+} air_glyph_jitter_t;
+#define AIR_JITTER_MAX_PLANE 48
+int air_glyph_jitter(const air_glyph_jitter_t* a, void* stream);
+/* the checks of air_glyph_jitter without its launch */
+int air_glyph_jitter_prepare(const air_glyph_jitter_t* a);
+/* bytes of dynamic LDS per workgroup, or AIR_EINVAL / AIR_ELIMIT for a (gd, od) the entry point refuses -- no GPU is touched */
+int64_t air_glyph_jitter_lds(int gd, int od);
+
 #ifdef __cplusplus
 }
 #endif

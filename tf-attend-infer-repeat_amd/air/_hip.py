@@ -209,6 +209,18 @@ class SceneSource(C.Structure):
                 ("max_attempts", _i), ("max_restarts", _i), ("seed", C.c_uint64)]
 
 
+JITTER_MAX_PLANE = 48
+
+
+class GlyphJitter(C.Structure):
+    """air_glyph_jitter_t: base glyphs and their crop boxes in, a bank of V jittered variants (frames, crop boxes, base glyph,
+    drawn parameters, status) out; counter is a nullable device int64, the bank generation"""
+    _fields_ = [("glyphs", _p), ("crops", _p), ("counter", _p), ("bank", _p), ("bank_crops", _p), ("source", _p),
+                ("params", _p), ("status", _p), ("V", _i), ("G", _i), ("gd", _i), ("od", _i),
+                ("min_w", C.c_double), ("max_w", C.c_double), ("min_h", C.c_double), ("max_h", C.c_double),
+                ("min_ang", C.c_double), ("max_ang", C.c_double), ("seed", C.c_uint64)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -286,6 +298,9 @@ _SIGNATURES = {
     "air_scene_source_advance": (C.c_int, [_p, C.c_int, _p]),
     "air_scene_source_prepare": (C.c_int, [C.POINTER(SceneSource)]),
     "air_scene_source_lds": (C.c_int64, [C.c_int, C.c_int]),
+    "air_glyph_jitter": (C.c_int, [C.POINTER(GlyphJitter), _p]),
+    "air_glyph_jitter_prepare": (C.c_int, [C.POINTER(GlyphJitter)]),
+    "air_glyph_jitter_lds": (C.c_int64, [C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -27,6 +27,35 @@ __device__ __forceinline__ void air_philox4x32_10(uint32_t (&c)[4], uint32_t k0,
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
 }
+// A stream of draws that every thread of a workgroup computes alike (the scene source, the glyph bank): draw j is word j & 3
+// of Philox4x32-10(key = seed, counter = (id, j >> 2, epoch, SALT)) -- id the workgroup's item, epoch the batch or generation.
+template <uint32_t SALT>
+struct AirDraws {
+    uint32_t id, epoch, k0, k1, w[4];
+    int j, quad;
+    __device__ __forceinline__ AirDraws(uint32_t id_, uint32_t epoch_, uint64_t seed)
+        : id(id_), epoch(epoch_), k0((uint32_t)seed), k1((uint32_t)(seed >> 32)), w{0, 0, 0, 0}, j(0), quad(-1) {}
+    __device__ __forceinline__ uint32_t next() {
+        const int q = j >> 2, k = j & 3;
+        if (q != quad) {
+            uint32_t c[4] = {id, (uint32_t)q, epoch, SALT};
+            air_philox4x32_10(c, k0, k1);
+            w[0] = c[0]; w[1] = c[1]; w[2] = c[2]; w[3] = c[3];
+            quad = q;
+        }
+        ++j;
+        return k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3];       // (selects: no indexed register array)
+    }
+    // an integer in [lo, lo + span)
+    __device__ __forceinline__ int range(int lo, int span) { return lo + (int)__umulhi(next(), (uint32_t)span); }
+    // lo + (hi - lo) * u in fp64, u a 53-bit real in [0, 1) of two words
+    __device__ __forceinline__ double real(double lo, double hi) {
+        const uint32_t a = next(), b = next();
+        const double u = ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
+        return lo + (hi - lo) * u;
+    }
+};
+
 __device__ __forceinline__ float air_u01_open_low(uint32_t x) { return ((float)(x >> 8) + 1.0f) * 5.9604644775390625e-8f; }  // (0,1]
 __device__ __forceinline__ float air_u01_half_open(uint32_t x) { return (float)(x >> 8) * 5.9604644775390625e-8f; }          // [0,1)
 

@@ -34,25 +34,6 @@ inline SceneLds scene_lds(int C, int gd) {
     return L;
 }
 
-// the draws of one scene: draw j is word j & 3 of the quad j >> 2
-struct SceneDraws {
-    uint32_t b, batch, k0, k1, w[4];
-    int j, quad;
-    __device__ __forceinline__ uint32_t next() {
-        const int q = j >> 2, k = j & 3;
-        if (q != quad) {
-            uint32_t c[4] = {b, (uint32_t)q, batch, SC_SALT};
-            air_philox4x32_10(c, k0, k1);
-            w[0] = c[0]; w[1] = c[1]; w[2] = c[2]; w[3] = c[3];
-            quad = q;
-        }
-        ++j;
-        return k == 0 ? w[0] : k == 1 ? w[1] : k == 2 ? w[2] : w[3];       // (selects: no indexed register array)
-    }
-    // an integer in [lo, lo + span)
-    __device__ __forceinline__ int range(int lo, int span) { return lo + (int)__umulhi(next(), (uint32_t)span); }
-};
-
 __global__ __launch_bounds__(SC_THREADS) void scene_compose_kernel(air_scene_source_t a, int step_in_replay, size_t off_glyph,
                                                                    size_t off_occ, size_t off_meta) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sc_lds[];
@@ -64,12 +45,7 @@ __global__ __launch_bounds__(SC_THREADS) void scene_compose_kernel(air_scene_sou
     const int C = a.C, CC = C * C, gd = a.gd, gap = a.gap, margin = a.margin;
     const int n16_canvas = (int)(off_glyph / 16), n16_occ = (int)((off_meta - off_occ) / 16);
 
-    SceneDraws d;
-    d.b = (uint32_t)b;
-    d.batch = (uint32_t)(*a.batch_counter + (int64_t)step_in_replay);
-    d.k0 = (uint32_t)a.seed; d.k1 = (uint32_t)(a.seed >> 32);
-    d.j = 0; d.quad = -1;
-    d.w[0] = d.w[1] = d.w[2] = d.w[3] = 0;
+    AirDraws<SC_SALT> d((uint32_t)b, (uint32_t)(*a.batch_counter + (int64_t)step_in_replay), a.seed);    // the draws of one scene
 
     int n;
     if (a.counts) {

@@ -14,10 +14,13 @@ follows the reference.
 
   python multi_mnist.py [--max-digits 2] [--images-per-digit 20000] [--test-set-size 1000]
                         [--digit-gap 0] [--canvas-margin 0] [--bg-path X --bg-max-intensity 1.0]
-  python multi_mnist.py --device 60000 [--seed 0] [...]     the same files, composed on the GPU (DeviceSceneSource)
+  python multi_mnist.py --device 60000 [--seed 0] [...]     the same files, composed on the GPU (DeviceSceneSource; with
+                        --min-width-scale ... --max-rotation-angle from a DeviceGlyphBank remade for every batch)
 
 DeviceSceneSource is that default path as device work: one HIP launch composes a fresh batch of canvases into the train
-model's input buffers (training.py --online-data), eagerly or inside a captured replay.
+model's input buffers (training.py --online-data), eagerly or inside a captured replay.  DeviceGlyphBank is the scale and
+rotation jitter (:113-135) as device work: one launch makes a bank of jittered variants of the glyphs, with scipy's order-5
+spline arithmetic, and a scene source built on the bank draws from those.
 """
 import argparse
 import gzip
@@ -329,6 +332,93 @@ def crop_boxes(glyphs, image_dim):
     return out
 
 
+JITTER_NEUTRAL = dict(min_w=1.0, max_w=1.0, min_h=1.0, max_h=1.0, min_ang=0.0, max_ang=0.0)
+
+
+def _glyph_array(glyphs):
+    """-> ([G, gd * gd] float32 contiguous numpy, gd)"""
+    import torch
+    g = glyphs.detach().cpu().numpy() if torch.is_tensor(glyphs) else np.asarray(glyphs)
+    g = np.ascontiguousarray(g.reshape(len(g), -1), np.float32)
+    gd = int(round(np.sqrt(g.shape[1])))
+    if gd * gd != g.shape[1]:
+        raise ValueError("glyphs must be [G, gd * gd]")
+    if g.min() < 0:
+        raise ValueError("glyph values must be >= 0")
+    return g, gd
+
+
+class DeviceGlyphBank:
+    """The scale and rotation jitter of generate_multi_image (:113-135) on the device, as a bank: ONE launch
+    (air_glyph_jitter, one workgroup per variant) turns the base `glyphs` [G, gd * gd] into `variants` jittered glyphs --
+    base glyph, new_width, new_height and angle drawn per variant -- each cropped into the top-left of an od x od frame, with
+    its crop box.  The arithmetic is scipy's affine_transform / rotate at order 5 in fp64 (include/air_hip.h states it), so a
+    variant is the glyph Generator.multi_image would have placed for the same draws.  DeviceSceneSource takes the bank in
+    place of a glyph array and draws its digits from the variants.
+
+    refresh(): the launch, then the generation counter advanced by one -- on the current stream, nothing synchronises; every
+    generation is another bank (its draws are keyed by (seed; variant, draw, generation)).  The tensors bank [V, od * od],
+    bank_crops [V, 4], source [V] (the base glyph of each variant), params [V, 6] (new_width, new_height, angle, cos, sin, 0)
+    and status [V] hold the last refresh.  status: 0 usable, 1 nothing left after the threshold, 2 larger than a plane limit
+    or than od -- such a variant has an all-zero crop box, and a scene that draws it restarts (the reference's IndexError
+    path, :177).  labels(base_labels): the label of every variant; status_counts(): a device tensor [3]."""
+
+    def __init__(self, glyphs, variants, od=32, seed=0, min_w=1.0, max_w=1.0, min_h=1.0, max_h=1.0, min_ang=0.0, max_ang=0.0,
+                 device=None):
+        import ctypes as C
+        import torch
+        from air import _hip as H
+        self._C, self._torch, self._H = C, torch, H
+        g, gd = _glyph_array(glyphs)
+        self.base_crops = crop_boxes(g, gd)
+        self.variants, self.gd, self.od = int(variants), gd, int(od)
+        self.bounds = dict(min_w=float(min_w), max_w=float(max_w), min_h=float(min_h), max_h=float(max_h),
+                           min_ang=float(min_ang), max_ang=float(max_ang))
+        V = self.variants
+        # the argument checks first, before anything is allocated: they need no device (the pointers are placeholders that
+        # the checks only compare with null and test for alignment)
+        self._a = H.GlyphJitter(16, 16, None, 16, 16, 16, 16, 16, V, len(g), gd, self.od,
+                                *[self.bounds[k] for k in ("min_w", "max_w", "min_h", "max_h", "min_ang", "max_ang")],
+                                int(seed) & 0xFFFFFFFFFFFFFFFF)
+        H.check(H.lib().air_glyph_jitter_prepare(C.byref(self._a)), "air_glyph_jitter_prepare")
+        if device is None and not torch.cuda.is_available():
+            raise H.AirHipError("DeviceGlyphBank: needs a GPU (no CPU fallback)")
+        dev = self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise H.AirHipError("DeviceGlyphBank: device must be a GPU (no CPU fallback)")
+        self.glyphs = torch.tensor(g, device=dev)
+        self.crops = torch.tensor(self.base_crops, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)           # the bank generation (device: replays move it)
+        self.bank = torch.zeros(V, self.od * self.od, device=dev)
+        self.bank_crops = torch.zeros(V, 4, dtype=torch.int32, device=dev)
+        self.source = torch.zeros(V, dtype=torch.int32, device=dev)
+        self.params = torch.zeros(V, 6, dtype=torch.float64, device=dev)
+        self.status = torch.ones(V, dtype=torch.int32, device=dev)             # (nothing is usable before the first refresh)
+        for k in ("glyphs", "crops", "counter", "bank", "bank_crops", "source", "params", "status"):
+            setattr(self._a, k, getattr(self, k).data_ptr())
+        H.check(H.lib().air_glyph_jitter_prepare(C.byref(self._a)), "air_glyph_jitter_prepare")
+
+    def refresh(self):
+        H = self._H
+        s = H.stream(self.device)
+        H.check(H.lib().air_glyph_jitter(self._C.byref(self._a), s), "air_glyph_jitter")
+        H.check(H.lib().air_scene_source_advance(self.counter.data_ptr(), 1, s), "air_scene_source_advance")
+
+    def labels(self, base_labels):
+        """[V]: the label of the base glyph of every variant of the last refresh (a read-back)"""
+        return np.asarray(base_labels)[self.source.cpu().numpy()]
+
+    def status_counts(self):
+        """device tensor [3]: the variants of the last refresh that are usable / empty / too large"""
+        return self._torch.bincount(self.status, minlength=3)[:3]
+
+    def fits(self, canvas_dim, margin):
+        """whether some base glyph, at the smallest scale that may be drawn, fits the canvas"""
+        w = np.floor(self.base_crops[:, 2] * self.bounds["min_w"]) + 2 * margin
+        h = np.floor(self.base_crops[:, 3] * self.bounds["min_h"]) + 2 * margin
+        return bool(np.any((w <= canvas_dim) & (h <= canvas_dim)))
+
+
 class DeviceSceneSource:
     """generate_multi_image (:82-183) on the device, default path only (pixel overlap with the optional gap buffer, margin,
     background): every batch is COMPOSED by one launch (air_scene_source_compose, one workgroup per canvas) straight into
@@ -346,21 +436,28 @@ class DeviceSceneSource:
     sampler, -1 = given up after max_restarts: an empty canvas with 0 digits).  gave_up(): a device scalar, the number of
     such canvases over all batches so far; nothing here synchronises.
 
+    `glyphs` may be a DeviceGlyphBank instead: the source then draws from the bank's jittered variants (its frames and crop
+    boxes, gd = the bank's od; meta()['indices'] are bank indices, bank.source maps them to base glyphs), and
+    graph_hooks(steps) enqueues bank.refresh() in front of the first compose of every replay.  next_batch() does not
+    refresh: the caller decides when the bank turns over.
+
     Against the host generator: glyph indices are drawn uniformly instead of walking a permutation, and the restart loop
-    is bounded.  Scale / rotation jitter and bounding-box overlap exist only there (Generator.multi_image)."""
+    is bounded.  Jitter keywords here are refused (the jitter is the bank's); bounding-box overlap exists only in
+    Generator.multi_image."""
 
     def __init__(self, glyphs, batch_size, out_images, out_digits, canvas_dim=CANVAS_SIZE, max_digits=2, margin=0, gap=0,
                  bg=None, counts=None, seed=0, max_attempts=100, max_restarts=32, use_pixel_overlap=True, **jitter):
         import ctypes as C
         import torch
         from air import _hip as H
-        neutral = dict(min_w=1.0, max_w=1.0, min_h=1.0, max_h=1.0, min_ang=0.0, max_ang=0.0)
+        neutral = JITTER_NEUTRAL
         unknown = sorted(set(jitter) - set(neutral))
         if unknown:
             raise TypeError("unexpected arguments: %s" % ", ".join(unknown))
         if any(float(jitter[k]) != v for k, v in neutral.items() if k in jitter):
-            raise NotImplementedError("scale / rotation jitter is not composed on the device (the reference's order-5 splines): "
-                                      "use the host generator, multi_mnist.Generator.multi_image")
+            raise NotImplementedError("scale / rotation jitter is not an option of the scene source: pass a DeviceGlyphBank built "
+                                      "with these bounds as `glyphs`, or use the host generator, "
+                                      "multi_mnist.Generator.multi_image")
         if not use_pixel_overlap:
             raise NotImplementedError("bounding-box overlap is not composed on the device: use the host generator, "
                                       "multi_mnist.Generator.multi_image(use_pixel_overlap=False)")
@@ -368,25 +465,33 @@ class DeviceSceneSource:
         H.require_device(out_digits, "out_digits", "DeviceSceneSource")
         self._C, self._torch, self._H = C, torch, H
         dev = self.device = out_images.device
-        g = glyphs.detach().cpu().numpy() if torch.is_tensor(glyphs) else np.asarray(glyphs)
-        g = np.ascontiguousarray(g.reshape(len(g), -1), np.float32)
-        gd = int(round(np.sqrt(g.shape[1])))
-        if gd * gd != g.shape[1]:
-            raise ValueError("glyphs must be [G, gd * gd]")
-        if g.min() < 0:
-            raise ValueError("glyph values must be >= 0")
+        self.bank = glyphs if isinstance(glyphs, DeviceGlyphBank) else None
+        if self.bank is not None:
+            if self.bank.device != dev:
+                raise ValueError("the glyph bank lives on %s, out_images on %s" % (self.bank.device, dev))
+            G, gd = self.bank.variants, self.bank.od
+        else:
+            g, gd = _glyph_array(glyphs)
+            G = len(g)
         self.batch, self.canvas_dim, self.max_digits = int(batch_size), int(canvas_dim), int(max_digits)
         B, D, md = self.batch, self.canvas_dim ** 2, self.max_digits
         if tuple(out_images.shape) != (B, D) or out_images.dtype != torch.float32 or not out_images.is_contiguous():
             raise ValueError("out_images must be a contiguous float32 [%d, %d]" % (B, D))
         if tuple(out_digits.shape) != (B,) or out_digits.dtype != torch.int32:
             raise ValueError("out_digits must be an int32 [%d]" % B)
-        crops = crop_boxes(g, gd)
-        if not np.any((crops[:, 2] + 2 * margin <= canvas_dim) & (crops[:, 3] + 2 * margin <= canvas_dim)):
+        if self.bank is not None:
+            fits = self.bank.fits(canvas_dim, margin)
+        else:
+            crops = crop_boxes(g, gd)
+            fits = np.any((crops[:, 2] + 2 * margin <= canvas_dim) & (crops[:, 3] + 2 * margin <= canvas_dim))
+        if not fits:
             raise ValueError("no glyph fits a %d x %d canvas with margin %d" % (canvas_dim, canvas_dim, margin))
         self.out_images, self.out_digits = out_images, out_digits
-        self.glyphs = torch.tensor(g, device=dev)
-        self.crops = torch.tensor(crops, device=dev)
+        if self.bank is not None:
+            self.glyphs, self.crops = self.bank.bank, self.bank.bank_crops
+        else:
+            self.glyphs = torch.tensor(g, device=dev)
+            self.crops = torch.tensor(crops, device=dev)
         self.bg = None if bg is None else torch.tensor(np.ascontiguousarray(bg, np.float32).reshape(-1), device=dev)
         if self.bg is not None and self.bg.numel() != D:
             raise ValueError("bg must be [%d, %d]" % (canvas_dim, canvas_dim))
@@ -407,7 +512,7 @@ class DeviceSceneSource:
             self.counts.data_ptr() if self.counts is not None else None, self.counter.data_ptr(),
             out_images.data_ptr(), out_digits.data_ptr(), self.indices.data_ptr(), self.positions.data_ptr(),
             self.boxes.data_ptr(), self.status.data_ptr(), self._gave_up.data_ptr(),
-            B, len(g), gd, self.canvas_dim, int(margin), int(gap), md, int(max_attempts), int(max_restarts),
+            B, G, gd, self.canvas_dim, int(margin), int(gap), md, int(max_attempts), int(max_restarts),
             int(seed) & 0xFFFFFFFFFFFFFFFF)
         # the argument checks and the LDS grant now: the first compose may be enqueued under stream capture
         with torch.cuda.device(dev):
@@ -440,6 +545,8 @@ class DeviceSceneSource:
             raise ValueError("graph_hooks was set up for %d steps per replay" % self._steps)
 
         def between_steps(i):
+            if i == 0 and self.bank is not None:         # a fresh bank for every replay, made by the replay itself
+                self.bank.refresh()
             self._compose(i)
             if i == steps - 1:                           # behind the last compose of the replay: the next replay goes on
                 self._advance(steps)
@@ -453,28 +560,37 @@ class DeviceSceneSource:
 
 
 def compose_on_device(num_images, max_digits=2, canvas_dim=CANVAS_SIZE, bg=None, gap=0, margin=0, seed=0, batch_size=1000,
-                      **generator_options):
+                      variants=4096, **generator_options):
     """`num_images` canvases from DeviceSceneSource (cuda:0), with the metadata generate_strata keeps: -> (dict of numpy
     arrays images [n, canvas_dim^2], digits, indices, positions, boxes, labels [n, max_digits] (slots behind digits[i] are
-    0) and status [n], glyph source).  generator_options: what the device does not compose is refused by the source."""
+    0) and status [n], glyph source).  generator_options: scale / rotation bounds that are not neutral put a DeviceGlyphBank
+    of `variants` jittered glyphs under the source, refreshed before every batch (`indices` are then indices into that
+    batch's bank; `labels` are mapped through it); what the device does not compose is refused by the source."""
     import torch
     glyphs, labels, source = load_glyphs()
     dev = torch.device("cuda", 0)
     B = min(batch_size, num_images)
     images = torch.zeros(B, canvas_dim * canvas_dim, device=dev)
     digits = torch.zeros(B, dtype=torch.int32, device=dev)
-    src = DeviceSceneSource(glyphs, B, images, digits, canvas_dim=canvas_dim, max_digits=max_digits, margin=margin, gap=gap,
-                            bg=bg, seed=seed, **generator_options)
-    out = {k: [] for k in ("images", "digits", "indices", "positions", "boxes", "status")}
+    jitter = {k: float(generator_options.pop(k)) for k in JITTER_NEUTRAL if k in generator_options}
+    bank = None
+    if any(v != JITTER_NEUTRAL[k] for k, v in jitter.items()):
+        bank = DeviceGlyphBank(glyphs, variants, seed=seed, device=dev, **jitter)
+    src = DeviceSceneSource(glyphs if bank is None else bank, B, images, digits, canvas_dim=canvas_dim, max_digits=max_digits,
+                            margin=margin, gap=gap, bg=bg, seed=seed, **generator_options)
+    out = {k: [] for k in ("images", "digits", "indices", "positions", "boxes", "status", "labels")}
     for _ in range((num_images + B - 1) // B):
+        if bank is not None:
+            bank.refresh()
         src.next_batch()
         out["images"].append(images.cpu().numpy())
         out["digits"].append(digits.cpu().numpy())
         for k, v in src.meta().items():
             out[k].append(v.cpu().numpy())
+        out["labels"].append((labels if bank is None else bank.labels(labels))[out["indices"][-1]])
     out = {k: np.concatenate(v)[:num_images] for k, v in out.items()}
     used = np.arange(max_digits)[None, :] < out["digits"][:, None]
-    out["labels"] = np.where(used, labels[out["indices"]], 0).astype(np.int32)
+    out["labels"] = np.where(used, out["labels"], 0).astype(np.int32)
     return out, source
 
 

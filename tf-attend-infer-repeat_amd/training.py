@@ -19,7 +19,10 @@ test model's forward + one summaries launch whose numbers are fetched without bl
 --online-data replaces the queue and the train set by multi_mnist.DeviceSceneSource: the generator's default path as one
 launch per step that composes a fresh batch into the train model's input buffers (inside the replay when there is one), so
 no canvas is trained on twice; the evaluation set stays the fixed one.  The run ends with a line that says how many
-batches were composed and how many canvases the bounded rejection sampler gave up on.
+batches were composed and how many canvases the bounded rejection sampler gave up on.  With the generator's scale /
+rotation flags (--min-width-scale ... --max-rotation-angle) the digits come from a bank of --jitter-bank jittered glyphs
+(multi_mnist.DeviceGlyphBank), remade on the device every --graph-steps steps -- by the replay itself when there is one, so
+the batches are the same with and without --no-graph; the last line then also counts the banks and the unusable variants.
 """
 import argparse
 import json
@@ -30,7 +33,7 @@ import time
 import numpy as np
 import torch
 
-from multi_mnist import DeviceSceneSource, ShuffleBatchQueue, generate_dataset, load_glyphs, shift_zero_digits_images
+from multi_mnist import JITTER_NEUTRAL, DeviceGlyphBank, DeviceSceneSource, ShuffleBatchQueue, generate_dataset, load_glyphs, shift_zero_digits_images
 from air.air_model import AIRModel
 
 EPOCHS = 300
@@ -248,6 +251,16 @@ def main():
     parser.add_argument("--online-max-digits", type=int, default=2, help="--online-data: scenes hold 0 .. this many digits")
     parser.add_argument("--digit-gap", type=int, default=0, help="--online-data: empty pixels kept between two digits")
     parser.add_argument("--canvas-margin", type=int, default=0, help="--online-data: empty border of the canvas")
+    # --online-data: the generator's six jitter flags (multi_mnist.py:322-327); neutral values leave the run as it is
+    parser.add_argument("--min-width-scale", type=float, default=1.0)
+    parser.add_argument("--max-width-scale", type=float, default=1.0)
+    parser.add_argument("--min-height-scale", type=float, default=1.0)
+    parser.add_argument("--max-height-scale", type=float, default=1.0)
+    parser.add_argument("--min-rotation-angle", type=float, default=0.0)
+    parser.add_argument("--max-rotation-angle", type=float, default=0.0)
+    parser.add_argument("--jitter-bank", type=int, default=4096, metavar="V",
+                        help="--online-data with jitter: digits are drawn from a bank of V jittered glyphs made on the device "
+                             "(multi_mnist.DeviceGlyphBank), a fresh bank every --graph-steps steps")
     args = parser.parse_args()
     if args.cnn and args.tensorboard:
         parser.error("--tensorboard writes histogram summaries, which a --cnn model does not have yet")
@@ -319,8 +332,13 @@ def main():
     # all its batches, one row gather sits in front of every step.
     # --online-data: no queue and no train set -- one launch in front of every step composes the step's batch from the
     # glyphs (same hooks: next_batch() eagerly, graph_hooks() inside the replay).
+    bank = None
     if args.online_data:
-        batches = DeviceSceneSource(load_glyphs()[0], BATCH_SIZE, train_data, train_targets, canvas_dim=CANVAS_SIZE,
+        jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
+                      max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
+        if jitter != JITTER_NEUTRAL:
+            bank = DeviceGlyphBank(load_glyphs()[0], args.jitter_bank, seed=0x4A4954 + args.seed, device=dev, **jitter)
+        batches = DeviceSceneSource(load_glyphs()[0] if bank is None else bank, BATCH_SIZE, train_data, train_targets, canvas_dim=CANVAS_SIZE,
                                     max_digits=args.online_max_digits, margin=args.canvas_margin, gap=args.digit_gap,
                                     bg=load_background(args.bg_path, args.bg_max_intensity), seed=0x5343454E45 + args.seed)
     else:
@@ -366,6 +384,8 @@ def main():
             order = train_model.backward
             print("iteration {}: sampler backward order -> {}".format(step - gsteps, order))
         if gsteps == 1:
+            if bank is not None and step % max(args.graph_steps, 1) == 0:      # (a replay of --graph-steps steps does it itself)
+                bank.refresh()
             batches.next_batch()
         train_model.training()
         if board and step % GRAD_SUMMARIES_EACH_ITERATIONS == 0:
@@ -385,7 +405,9 @@ def main():
         float(test_model.accuracy), float(test_model.loss), step, time.perf_counter() - t0))
     if args.online_data:
         print("online data: {} batches composed on the device, {} canvases given up".format(
-            int(batches.counter), int(batches.gave_up())))
+            int(batches.counter), int(batches.gave_up())) + ("" if bank is None else
+            ", {} glyph banks of {} variants, {} unusable in the last".format(
+                int(bank.counter), bank.variants, int(bank.status_counts()[1:].sum()))))
     torch.save(train_model.state_dict(), models_folder + "air-model-%d.pt" % step)
     if args.tf_checkpoints:
         train_model.save_tf_checkpoint(models_folder + "air-model-%d" % step)
