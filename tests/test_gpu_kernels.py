@@ -660,7 +660,8 @@ def _softplus_tf(x):
     return np.where(x > 13.942384719848633, x, np.where(x < -13.942384719848633, np.exp(x), np.log1p(np.exp(x))))
 
 
-@pytest.mark.parametrize("M,Hd,Z", [(192, 256, 50), (37, 192, 50), (16, 256, 64), (5, 64, 2)])
+# (Hd = 200 = 3 x 64 + 8: a ragged last slice beside full ones; Hd = 8: one slice, 14 of its 16 column quads masked)
+@pytest.mark.parametrize("M,Hd,Z", [(192, 256, 50), (37, 192, 50), (16, 256, 64), (5, 64, 2), (37, 200, 50), (16, 8, 64), (5, 200, 2)])
 def test_vae_bottleneck_forward_matches_the_formulas(H, M, Hd, Z):
     """air_vae_bottleneck_fwd = vae.py:16-30 in one launch: mean | log-variance, the reparameterised
     sample and the first generative layer.  Reference: float64 on bf16-rounded GEMM operands."""
@@ -1566,7 +1567,7 @@ def test_write_bwd_takes_its_items_longest_first_without_changing_results(H, Cc,
     assert lib.air_write_bwd(C.byref(wb), _stream()) == -1
 
 
-@pytest.mark.parametrize("M,Hd,Z", [(192, 256, 50), (37, 192, 50), (16, 256, 52), (5, 64, 2)])
+@pytest.mark.parametrize("M,Hd,Z", [(192, 256, 50), (37, 192, 50), (16, 256, 52), (5, 64, 2), (37, 200, 50), (16, 8, 52), (5, 200, 2)])
 def test_vae_bottleneck_forward_exact_fp32(H, M, Hd, Z):
     """air_bottleneck_fwd_t.exact_fp32: vae.py:16-30 in one launch with exact fp32 products (the fp32 path's arithmetic):
     against float64 on the fp32 operands, and against the two exact-fp32 air_gemm launches it replaces."""

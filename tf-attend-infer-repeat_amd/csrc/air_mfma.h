@@ -1,6 +1,7 @@
-// What the GEMM kernels (air_gemm_common.h, namespace airg) and the weight-gradient tiles (air_wgrad.hip, namespace airw)
-// both need and neither owns: the MFMA operand / accumulator vector types, accumulator zeroing, gfx950's transpose read
-// and the pointer-alignment predicates.  Both namespaces import the names with using-declarations.
+// What the GEMM kernels (air_gemm_common.h, namespace airg), the weight-gradient tiles (air_wgrad.hip, namespace airw) and
+// the bottleneck kernels (air_bottleneck.hip) need and none of them owns: the MFMA operand / accumulator vector types,
+// accumulator zeroing, gfx950's transpose read and the pointer-alignment predicates.  They import the names with
+// using-declarations.
 #pragma once
 #include "air_common.h"
 
