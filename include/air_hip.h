@@ -470,6 +470,24 @@ int air_write_bwd(const air_write_bwd_t* a, void* stream);
 /* the kernel function air_write_bwd dispatches this descriptor to, as rocprofv3 prints it (profiling tools) */
 int air_write_bwd_kernel_name(const air_write_bwd_t* a, char* buf, int n);
 
+/* air_write_fwd(f) followed by air_write_bwd(b) as ONE launch, every output bit for bit that of the two: a workgroup of
+ * the write backward builds d loss / d canvas of its image itself, the workgroup of step 0 stores the image's forward
+ * outputs (d_recon included), and the owner workgroup that finishes last computes the batch means.  The pair must describe
+ * one train step: b->d_recon / vrec / att / fin_loss_item / fin_digits are f's d_recon / vrec / att / loss_item /
+ * run_digits, equal B, N, C, w, f->d_recon and all four b->fin_* given (AIR_EINVAL otherwise, and for b->literal != 2).
+ * The form exists where all four taps' terms of the write backward are resident in LDS, compose's scratch fits over
+ * them, and N * B <= 256 without f->wb_order / b->order: AIR_ELIMIT otherwise -- the caller keeps its two launches.
+ * N * B <= 256 is an ASSUMPTION about placement, not a guarantee: the hand-off of the batch means uses agent-scope
+ * relaxed stores and loads in place of a release / acquire pair, a form measured with one workgroup per CU on a 256-CU
+ * part.  The launch asks for under half a CU's LDS, so on a part with fewer CUs, or beside another stream's work, two of
+ * its workgroups can share a CU -- a setting that form has not been measured in.
+ * `arrive`: one device word, zero before the first call; every call leaves it zero.  Calls that share it must not overlap.
+ * Like air_write_bwd, call it once eagerly before capturing it (the accumulator probe). */
+int air_write_fwd_bwd(const air_write_fwd_t* f, const air_write_bwd_t* b, int32_t* arrive, void* stream);
+/* the kernel function air_write_fwd_bwd dispatches this pair to, as rocprofv3 prints it; the code air_write_fwd_bwd
+ * returns for a pair it refuses (both read one host-side plan: no GPU is touched) */
+int air_write_fwd_bwd_kernel_name(const air_write_fwd_t* f, const air_write_bwd_t* b, char* buf, int n);
+
 /* ---- VAE bottleneck, one launch per direction (vae.py:16-34) ------------------
  * Forward = the last recognition product and the first generative layer:
  *   ml [M,2Z] = X [M,K1].Wml [K1,2Z] + bml  (mean | log-variance, vae.py:16-20)

@@ -407,7 +407,8 @@ class AIRModel:
                  learning_rate=1e-3, gradient_clipping_norm=100.0, cnn=None, cnn_filters=8,
                  num_summary_images=60, train=False, reuse=False, scope="air",
                  annealing_schedules=None, seed=0, gemm_precision=None, backward="reference", noise_seed=None,
-                 bf16_twins=None, dp_exchange=None, xw_tile=None, xwx_twin_staging="lds_dma", step0_fusion=None):
+                 bf16_twins=None, dp_exchange=None, xw_tile=None, xwx_twin_staging="lds_dma", step0_fusion=None,
+                 compose_fold=True):
         if cnn is None:
             # The reference's default is cnn=True (:21) and every caller of the reference passes cnn=False.  A call that leaves
             # `cnn` out has always been refused here, and still is: which LSTM input a model has (and with it the layout of
@@ -568,6 +569,11 @@ class AIRModel:
         if xwx_twin_staging not in ("lds_dma", "registers"):
             raise ValueError("xwx_twin_staging must be 'lds_dma' or 'registers'")
         self._xwx_twin_staging = xwx_twin_staging
+        # captured train steps run compose inside the write-backward launch where the library has that form
+        # (air_write_fwd_bwd; same results); False keeps the two launches: the A/B arm within one build
+        self._compose_fold = bool(compose_fold)
+        self._fold_op = None
+        self._graph_step_ops = []
         self._graph_xwx = []
         self._last_xwx_op = None
         self._graph = None
@@ -681,6 +687,8 @@ class AIRModel:
         self._rec_loss = f(B)
         self._loss_item = f(B)
         self.scalars = self.store.grads[self.store.n:self.store.n + 4] if self.train else f(4)
+        # arrival count of air_write_fwd_bwd (the captured steps' compose + write backward launch): zero between launches
+        self._arrive = torch.zeros(1, dtype=torch.int32, device=self.input_images.device) if self.train else None
 
         self.h16 = h16(N + 1, B, R)                     # [0] stays zero like h[0]
         self.hid16 = h16(N, B, HT)
@@ -974,6 +982,7 @@ class AIRModel:
                         _ptr(self._recon), _ptr(self._rec_loss), _ptr(self.d_recon if self.train else None),
                         _ptr(self.run_loss), _ptr(self.run_digits), _ptr(self._loss_item), B, N, Cc, w, Z, _ptr(self._wb_order))
         keep.append(wf)
+        self._write_fwd_desc = wf
         fwd.append(self._call("air_write_fwd", C.byref(wf),
                               nbytes=NB * (d + 2 * Z) * 4 + B * D * 4 * (3 if self.train else 2), tag="compose_fwd"))
         # batch means: their own launch after a plain forward; inside air_write_bwd in a train step
@@ -1078,6 +1087,18 @@ class AIRModel:
         bwd.append(self._call("air_write_bwd", C.byref(wb), nbytes=NB * ((D + d) * 4 + 16 + 12), tag="write_bwd"))
         self._write_bwd_fin = self._call("air_write_bwd", C.byref(wbf), nbytes=NB * ((D + d) * 4 + 16 + 12), tag="write_bwd")
         bwd[-1].kernel = self._write_bwd_fin.kernel = kbuf.value.decode()
+        # compose + write backward (+ batch means) as one launch, for the captured steps: the library says whether this pair
+        # of descriptors has that form (a refusal keeps the two launches; anything else is an error)
+        self._fold_op = None
+        if self._compose_fold:
+            rc = self.lib.air_write_fwd_bwd_kernel_name(C.byref(self._write_fwd_desc), C.byref(wbf), kbuf, 96)
+            if rc == 0:
+                self._fold_op = self._call("air_write_fwd_bwd", C.byref(self._write_fwd_desc), C.byref(wbf), _ptr(self._arrive),
+                                           nbytes=self._fwd[-1].nbytes + self._write_bwd_fin.nbytes - NB * D * 4,
+                                           tag="compose_write_bwd")
+                self._fold_op.kernel = kbuf.value.decode()
+            elif rc not in (H.EINVAL, H.ELIMIT):
+                H.check(rc, "air_write_fwd_bwd_kernel_name")
 
         def dgrad(l, dy, dy16, out, out16, saved=None, tag="dgrad_win"):
             """dX = dY . W^T of product l; times softplus'(saved activation X) where one is given"""
@@ -1240,11 +1261,12 @@ class AIRModel:
         hi, hop = self._begin_host
         return [(hop if i == hi else op) for i, op in enumerate(self._fwd if fwd is None else fwd)]
 
-    def _run_forward(self, s, finalize=True, twin_x=False):
+    def _run_forward(self, s, finalize=True, twin_x=False, fold=False):
         """twin_x: x.Wx reads the padded bf16 twin of the image batch.  Only capture_graph may ask for it, and only for a
-        step whose predecessor in the SAME replay ran the fp32-operand launch over the same, untouched batch."""
+        step whose predecessor in the SAME replay ran the fp32-operand launch over the same, untouched batch.
+        fold: without the compose launch, the last of the list -- the backward that follows opens with air_write_fwd_bwd."""
         self._fresh_shadow()
-        fwd = self._fwd
+        fwd = self._fwd[:-1] if fold else self._fwd
         if twin_x:
             if self._xwx_twin_op is None:
                 raise RuntimeError("this model has no twin-operand x.Wx launch")
@@ -1261,6 +1283,7 @@ class AIRModel:
             op(s)
         if finalize:
             self._finalize(s)
+        self._last_fwd_run = ([self._cnn_fwd] if self._cnn_fwd is not None else []) + run
 
     def forward(self):
         """Evaluates the model on the current contents of the input buffers."""
@@ -1372,22 +1395,24 @@ class AIRModel:
                 dist.all_reduce(out)
         dist.all_reduce(f["tail"])                               # everything but dWx (+ loss / accuracy)
 
-    def _run_backward(self, s, for_update=False, fused_finalize=False):
+    def _run_backward(self, s, for_update=False, fused_finalize=False, fold=False):
         """for_update: this backward is followed by the optimizer of a single-GPU train step -- the
-        weight-gradient launch then also publishes the global-norm partials and counts the step."""
-        for i, op in enumerate(self._bwd):
-            (self._write_bwd_fin if (i == 0 and fused_finalize) else op)(s)
+        weight-gradient launch then also publishes the global-norm partials and counts the step.
+        fold: the forward before it ran without its compose launch (_run_forward): air_write_fwd_bwd opens the list."""
+        first = self._fold_op if fold else (self._write_bwd_fin if fused_finalize else self._bwd[0])
         # (tried: the VAE weight gradients as their own launch on a side stream beside attend_bwd ->
         # dh_heads -> BPTT.  The big launch takes the CUs the latency-critical chain needs: 217 -> 257 us.)
         if for_update and not self._dp():
-            self._wgrad_fused(s)
-            return
-        if for_update and self._dp_exchange == "factors":
+            tail = [self._wgrad_fused]
+        elif for_update and self._dp_exchange == "factors":
             f = self._dp_factors()
-            f["local"](s)
-            f["bias"](s)
-            return
-        self._wgrad_plain(s)
+            tail = [f["local"], f["bias"]]
+        else:
+            tail = [self._wgrad_plain]
+        run = [first] + self._bwd[1:] + tail
+        for op in run:
+            op(s)
+        self._last_bwd_run = run
 
     def train_step_ops(self):
         """The launches of one single-GPU train step, in order (bench / profiling tools): the EAGER step, whose x.Wx reads
@@ -1405,10 +1430,18 @@ class AIRModel:
     def captured_xwx_ops(self):
         return None if self._graph is None or not self.train else list(self._graph_xwx)
 
-    def _train_phase_a(self, s, twin_x=False):
+    def captured_step_ops(self, step=0):
+        """The launches of train step `step` of the captured replay, in order (None: no train graph): the ops that were
+        enqueued under capture.  Where the library has the form, compose and the write backward are ONE of them
+        (air_write_fwd_bwd: compose_fold), so the list is one shorter than train_step_ops(), the eager step.
+        Data parallel over a backend whose collectives cannot be captured: the ops of the FIRST graph, prologue to weight
+        gradients -- the optimizer is replayed from a graph of its own after the exchange and is not listed."""
+        return None if self._graph is None or not self.train else list(self._graph_step_ops[step])
+
+    def _train_phase_a(self, s, twin_x=False, fold=False):
         """step prologue + forward + loss + backward (+ weight grads) into the flat grad buffer"""
-        self._run_forward(s, finalize=False, twin_x=twin_x)
-        self._run_backward(s, for_update=True, fused_finalize=True)
+        self._run_forward(s, finalize=False, twin_x=twin_x, fold=fold)
+        self._run_backward(s, for_update=True, fused_finalize=True, fold=fold)
 
     def _train_phase_b(self, s):
         """global-norm clip + TF-style Adam + global_step += 1 (after the all-reduce)"""
@@ -1455,6 +1488,8 @@ class AIRModel:
                 self._dp_exchange_gradients()    # also the first collective of the communicator: never under capture
                 if factors:
                     self._dp_factors()["dwx"](s)
+            if self._fold_op is not None:
+                self._fold_op(s)                 # (its LDS grant, like every launch's, is a driver call: never under capture)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         # Step 0 of a replay reads the caller's fp32 image batch (the host may have rewritten it since the last replay) and
@@ -1464,7 +1499,10 @@ class AIRModel:
         # (Nor with the conv front-end, whose model builds no twin-operand launch: Adam moves the conv variables, so the LSTM's
         # input differs from step to step.)
         can_twin = between_steps is None and self._xwx_twin_op is not None and self._begin_host[0] != 0
-        xwx = []
+        # Every captured step runs compose inside the write-backward launch where the library has that form for this model
+        # (air_write_fwd_bwd: one launch fewer, same results) -- with or without hooks: nothing it reads can be stale.
+        fold = self._fold_op is not None
+        xwx, step_ops = [], []
         ga = torch.cuda.CUDAGraph()
         # (thread_local: RCCL's watchdog thread may touch the runtime while this thread captures)
         with torch.cuda.graph(ga, **({"capture_error_mode": "thread_local"} if dp else {})):
@@ -1473,8 +1511,12 @@ class AIRModel:
                     between_steps(i)
                 s = self._stream()
                 twin_x = i >= 1 and can_twin
-                self._train_phase_a(s, twin_x=twin_x)
+                self._train_phase_a(s, twin_x=twin_x, fold=fold)
                 xwx.append(self._last_xwx_op)
+                # (a backend whose collectives cannot be captured: the optimizer is recorded into the second graph, below)
+                step_ops.append(self._last_fwd_run + self._last_bwd_run +
+                                ([] if (dp and not in_graph) else
+                                 ([self._dp_factors()["dwx"]] if factors else []) + list(self._optimizer_ops())))
                 if not dp:
                     self._train_phase_b(s)
                 elif in_graph:
@@ -1491,6 +1533,7 @@ class AIRModel:
                 self._train_phase_b(self._stream())
         self._graph = (ga, gb)
         self._graph_xwx = xwx
+        self._graph_step_ops = step_ops
         self._graph_dp = (dp, in_graph)
         return self
 

@@ -101,11 +101,7 @@ __device__ __forceinline__ HeadSeg head_segments(int Hs, int Hh, int Hz) {
 }
 // (output unit -> head, head -> (offset, width): air_out_head / air_head_wid / air_head_off, air_common.h)
 
-// air_model.py:443-447 for one element
-__device__ __forceinline__ float gauss_kl_term(float plv, float lv, float var, float pv, float mean, float pm) {
-    const float d = mean - pm;
-    return (((plv - lv) - 1.0f) + var / pv) + (d * d) / pv;
-}
+// (gauss_kl_term, air_model.py:443-447 for one element: air_sampler_common.h)
 
 // ---------------------------------------------------------------------------
 // attend forward, TIME-BATCHED: one workgroup per (image, time step).
@@ -609,14 +605,11 @@ __global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
         const float R = compose_pixel(sh_act, sh_z, sh_tx, sh_ty, sh_win, N, C, w, i, j);
         i += di; j += dj;
         if (j >= C) { j -= C; ++i; }
-        const float r = fmaxf(fminf(R, 1.0f), 0.0f);                // clipped_rec :582
-        const float p1 = r + AIR_EPS, p0 = (1.0f - r) + AIR_EPS;
+        float p1, p0;
+        const float r = compose_clip(R, p1, p0);                    // clipped_rec :582
         acc += x * logf(p1) + (1.0f - x) * logf(p0);                // :586-589
         a.recon[base + p] = r;
-        if (a.d_recon) {
-            const bool pass = (R <= 1.0f) && (fminf(R, 1.0f) >= 0.0f);   // Minimum/Maximum grads pass at ties
-            a.d_recon[base + p] = pass ? -gsc * (x / p1 - (1.0f - x) / p0) : 0.0f;
-        }
+        if (a.d_recon) a.d_recon[base + p] = compose_dloss(R, x, p1, p0, gsc);
     }
     acc = air_block_sum_n<NT / 64>(acc, sh_red);
     if (tid == 0) {

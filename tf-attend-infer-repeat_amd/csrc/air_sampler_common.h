@@ -104,8 +104,8 @@ constexpr int CF_THREADS = 1024;
 
 // taps of theta_recon (air_model.py:353-356) for every (step, canvas column / row) and the windows of all N steps of image
 // b into LDS: sh_tx / sh_ty [N][C], sh_win [N][w*w]
-__device__ __forceinline__ void compose_stage(const float* att, const float* vrec, int b, int B, int N,
-                                              int C, int w, int tid, int nthreads, Tap* sh_tx, Tap* sh_ty, float* sh_win) {
+__device__ __forceinline__ void compose_stage_taps(const float* att, int b, int B, int N, int C, int w, int tid, int nthreads,
+                                                   Tap* sh_tx, Tap* sh_ty) {
     for (int it = tid; it < N * C; it += nthreads) {
         const int t = it / C, j = it % C;
         const float* at = att + ((size_t)t * B + b) * AIR_ATT_STRIDE;
@@ -115,10 +115,19 @@ __device__ __forceinline__ void compose_stage(const float* att, const float* vre
         sh_tx[it] = axis_tap(j, C, w, ia, bx);
         sh_ty[it] = axis_tap(j, C, w, ia, by);
     }
-    for (int it = tid; it < N * w * w; it += nthreads) {
-        const int t = it / (w * w);
-        sh_win[it] = vrec[((size_t)t * B + b) * w * w + (it - t * w * w)];
-    }
+}
+// element `it` of the N windows of image b ([N][w*w], as sh_win holds them)
+__device__ __forceinline__ float compose_window_at(const float* vrec, int b, int B, int w, int it) {
+    const int t = it / (w * w);
+    return vrec[((size_t)t * B + b) * w * w + (it - t * w * w)];
+}
+__device__ __forceinline__ void compose_stage_windows(const float* vrec, int b, int B, int N, int w, int first, int nthreads, float* sh_win) {
+    for (int it = first; it < N * w * w; it += nthreads) sh_win[it] = compose_window_at(vrec, b, B, w, it);
+}
+__device__ __forceinline__ void compose_stage(const float* att, const float* vrec, int b, int B, int N,
+                                              int C, int w, int tid, int nthreads, Tap* sh_tx, Tap* sh_ty, float* sh_win) {
+    compose_stage_taps(att, b, B, N, C, w, tid, nthreads, sh_tx, sh_ty);
+    compose_stage_windows(vrec, b, B, N, w, tid, nthreads, sh_win);
 }
 
 // running_recon of canvas pixel (i, j) (:552, :429-439): the z-scaled window -> canvas taps of the active steps, summed in
@@ -135,6 +144,24 @@ __device__ __forceinline__ float compose_pixel(const int* sh_act, const float* s
         R = R + sh_z[t] * wr;
     }
     return R;
+}
+
+// clipped_rec :582 of running_recon R (returned), and the arguments of the two logs of the Bernoulli cross-entropy :586-589
+__device__ __forceinline__ float compose_clip(float R, float& p1, float& p0) {
+    const float r = fmaxf(fminf(R, 1.0f), 0.0f);
+    p1 = r + AIR_EPS; p0 = (1.0f - r) + AIR_EPS;
+    return r;
+}
+// d loss / d running_recon of one pixel (gsc: AIR_DYN_GRAD_SCALE)
+__device__ __forceinline__ float compose_dloss(float R, float x, float p1, float p0, float gsc) {
+    const bool pass = (R <= 1.0f) && (fminf(R, 1.0f) >= 0.0f);      // Minimum/Maximum grads pass at ties
+    return pass ? -gsc * (x / p1 - (1.0f - x) / p0) : 0.0f;
+}
+
+// air_model.py:443-447 for one element
+__device__ __forceinline__ float gauss_kl_term(float plv, float lv, float var, float pv, float mean, float pm) {
+    const float d = mean - pm;
+    return (((plv - lv) - 1.0f) + var / pv) + (d * d) / pv;
 }
 
 template <typename K>
@@ -162,6 +189,10 @@ inline size_t write_bwd_graph_smem(int C, int w, bool allph) {
             (allph ? 5 : 1) * (((size_t)C * C + 3) & ~3)) * sizeof(float);
 }
 inline bool write_bwd_graph_allph(int C, int w) { return write_bwd_graph_smem(C, w, true) <= 80 * 1024; }
+// air_write_fwd_bwd: compose's scratch (write_smem's layout + the two words handed to the signalling lane) lies over the
+// term buffer of the all-taps-resident write backward, which is dead until the term phase
+inline size_t compose_fold_floats(int N, int C, int w) { return write_smem(N, C, w) / sizeof(float) + 4; }
+inline bool compose_fold_fits(int N, int C, int w) { return compose_fold_floats(N, C, w) <= 4 * (((size_t)C * C + 3) & ~3); }
 // air_write_bwd, literal 0
 inline size_t write_bwd_smem(int C, int w) { return (64 + 8 * C + C + 8 * w + (size_t)w * w + (size_t)C * w + (size_t)C * C) * sizeof(float); }
 

@@ -496,9 +496,33 @@ __device__ __forceinline__ void stream_add2(float& c, float& q, const float* T, 
     }
     while (k < end) { const float t = T[k]; c += t; q += t; ++k; }
 }
-template <bool ALLPH, bool CARRIED>
-__device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, int seq_flags)
+// agent-scope relaxed accesses of the words one workgroup hands to another inside a launch (global_ ... sc1: served by the
+// memory side, never by a CU's L1)
+typedef __attribute__((address_space(1))) float air_global_float;
+typedef __attribute__((address_space(1))) int32_t air_global_int;
+__device__ __forceinline__ void store_agent(float* p, float v) {
+    __hip_atomic_store((air_global_float*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void store_agent(int32_t* p, int32_t v) {
+    __hip_atomic_store((air_global_int*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float load_agent(const float* p) {
+    return __hip_atomic_load((const air_global_float*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ int32_t load_agent(const int32_t* p) {
+    return __hip_atomic_load((const air_global_int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// FOLD (air_write_fwd_bwd; ALLPH, not CARRIED): the compose pass runs at the front of this launch.  Every workgroup of
+// image b builds d loss / d canvas of that image itself, straight into sh_g -- compose's tap tables and windows lie over
+// sh_T, which nothing writes before the term phase -- and the workgroup of step 0 owns the image's forward outputs
+// (write_fwd_kernel's, in its summation orders).  The batch means need every image's loss_item / run_digits: the owners
+// count themselves on *arrive and the one that arrives last computes them (fold_signal / fold_means below).
+template <bool ALLPH, bool CARRIED, bool FOLD = false>
+__device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, int seq_flags,
+                                                     const air_write_fwd_t* fp = nullptr, int32_t* arrive = nullptr)
 {
+    static_assert(!FOLD || (ALLPH && !CARRIED), "the compose fold exists in the all-taps-resident graph order only");
     // seq_flags (accumulators(), below): bit 0 the LDS atomic pipe applies lanes in order, bit 1 the lane-ring accumulator
     // is exact on this part (used when the pipe is not)
     const bool lds_ordered = seq_flags & 1, ring_ok = seq_flags & 2;
@@ -529,7 +553,7 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
     float* sh_T = ALLPH ? sh_g + CCp : sh_g;               // [4 or 1][C*C] terms, rectangle-blocked per tap (16-byte aligned)
     const float* gsrc = a.d_recon + (size_t)b * CC;
 
-    if (a.fin_scalars && lin == (a.order ? (int)(gridDim.x * gridDim.y) - 1 : 0)) {     // (ordered: the lightest item's workgroup)
+    if (!FOLD && a.fin_scalars && lin == (a.order ? (int)(gridDim.x * gridDim.y) - 1 : 0)) {     // (ordered: the lightest item's workgroup)
         float r4[4] = {0.f, 0.f, 0.f, 0.f};
         for (int i = tid; i < a.B; i += WB_THREADS) {
             r4[0] += a.fin_loss_item[i];
@@ -548,18 +572,179 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
     // the window and (small canvases) the first pass over d_recon do not depend on the record: their loads go out
     // BEFORE the mask test waits for it -- one memory round trip for the set-up instead of two
     const float* v = a.vrec + row * w * w;
-    const float win_pre = tid < w * w ? v[tid] : 0.0f;      // (w * w <= WB_THREADS: checked by the launcher)
+    float win_pre = 0.0f;
     float g_pre[8];
-    if (ALLPH) {
+    if (!FOLD) {
+        win_pre = tid < w * w ? v[tid] : 0.0f;              // (w * w <= WB_THREADS: checked by the launcher)
+        if (ALLPH) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { const int p = k * WB_THREADS + tid; g_pre[k] = p < CC ? gsrc[p] : 0.0f; }
+            for (int k = 0; k < 8; ++k) { const int p = k * WB_THREADS + tid; g_pre[k] = p < CC ? gsrc[p] : 0.0f; }
+        }
     }
-    if (at[AIR_ATT_MASK] == 0.0f) {                        // Select(active, ., 0): no gradient
+    // FOLD: the lane that counts an owner workgroup on *arrive for all that workgroup's stores (the first lane of the last
+    // wave: that wave runs the pixel loop, not a corner feed), and the LDS word through which it tells the workgroup
+    // whether its add came last (a free word of the last wave's partials row: zeroed with the row, read behind a barrier)
+    constexpr int SIG = WB_THREADS - 64;
+    int* sh_last = reinterpret_cast<int*>(sh_red) + (NW - 1) * 8 + 7;
+    const bool owner = FOLD && t == 0;
+    // hand-off, producer side: the signalling lane stored the workgroup's two words (store_agent, below); once those
+    // stores have completed it counts the workgroup with ONE returning agent-scope add
+    auto fold_signal = [&]() -> int {
+        int ticket = -1;
+        if (tid == SIG) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            ticket = __hip_atomic_fetch_add((air_global_int*)arrive, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return ticket;
+    };
+    // hand-off, consumer side.  `last` is workgroup-uniform and was read from sh_last behind a barrier the adding wave
+    // joined after its add had returned B - 1: every owner's words are complete.  loss = mean(loss_item) :593,610;
+    // accuracy = mean(target == digits) :597-611 (air_finalize) -- the loop and the reduction of the two-launch form
+    auto fold_means = [&](bool last) {
+        if (!last) return;
+        float r4[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int i = tid; i < a.B; i += WB_THREADS) {
+            r4[0] += load_agent(a.fin_loss_item + i);
+            r4[1] += (a.fin_targets[i] == load_agent(a.fin_digits + i)) ? 1.0f : 0.0f;
+        }
+        air_block_sum4<NW>(r4, sh_red);
+        if (tid == 0) {
+            a.fin_scalars[0] = r4[0] / (float)a.B; a.fin_scalars[1] = r4[1] / (float)a.B;
+            store_agent(arrive, 0);                          // every owner has arrived: the next launch counts from 0
+        }
+    };
+    float fs = 0.0f, fx = 0.0f, fy = 0.0f, fz = 0.0f;        // FOLD: this item's s, x, y, z, loaded with the set-up
+    if constexpr (FOLD) {
+        const air_write_fwd_t& f = *fp;
+        const int N = a.N, B = a.B, Z = f.Z;
+        // compose's scratch in write_fwd_kernel's layout (write_smem), over the term buffer
+        float* c_red = sh_T;                                                    // [16]
+        float* c_z = sh_T + 16;                                                 // [MAX_STEPS] z_pres
+        int* c_act = reinterpret_cast<int*>(sh_T + 16 + MAX_STEPS);             // [MAX_STEPS]
+        float* c_kl = sh_T + 16 + 2 * MAX_STEPS;                                // [MAX_STEPS] VAE KL per step
+        float* c_rec = sh_T + 16 + 3 * MAX_STEPS;                               // [MAX_STEPS][4]: mask_prev, KL z, KL scale, KL shift
+        Tap* c_tx = reinterpret_cast<Tap*>(sh_T + 16 + 7 * MAX_STEPS);          // [N][C]
+        Tap* c_ty = c_tx + (size_t)N * C;                                       // [N][C]
+        float* c_win = reinterpret_cast<float*>(c_ty + (size_t)N * C);          // [N][w*w]
+        float* c_sig = c_win + (size_t)N * w * w;                               // [2] run_loss, run_digits for the signalling lane
+        const float* dyn = f.dyn;
+        const size_t base = (size_t)b * CC;
+        // ONE memory round trip for the set-up: this item's record, the image row and the first WPRE * WB_THREADS window
+        // elements go out before anything waits (the tap tables wait for the records of all steps; what is behind the
+        // prefetched window elements is loaded after them)
+        const float mask_own = at[AIR_ATT_MASK];
+        fs = at[AIR_ATT_S]; fx = at[AIR_ATT_X]; fy = at[AIR_ATT_Y]; fz = at[AIR_ATT_Z];
+        constexpr int XPRE = 4, WPRE = 4;
+        const bool xpre = CC <= XPRE * WB_THREADS;
+        float xs[XPRE], wpre[WPRE];
+#pragma unroll
+        for (int k = 0; k < XPRE; ++k) { const int p = tid + k * WB_THREADS; xs[k] = f.images[base + ((xpre && p < CC) ? p : 0)]; }
+#pragma unroll
+        for (int k = 0; k < WPRE; ++k) {
+            const int it = tid + k * WB_THREADS;
+            wpre[k] = compose_window_at(a.vrec, b, B, w, it < N * w * w ? it : 0);
+        }
+        if (owner) {
+            for (int tt = wave; tt < N; tt += NW) {
+                // VAE KL :479-493 (a public output whether or not the item is still active): one wave per step
+                const float* ml = f.ml + ((size_t)tt * B + b) * 2 * Z;
+                const float pv = dyn[AIR_DYN_VAE_PV], pm = dyn[AIR_DYN_VAE_PM], plv = dyn[AIR_DYN_VAE_PLV];
+                float klt = 0.0f;
+                for (int j = lane; j < Z; j += 64) {
+                    const float lv = ml[Z + j];
+                    klt += gauss_kl_term(plv, lv, expf(lv), pv, ml[j], pm);
+                }
+                klt = air_wave_sum(klt);
+                if (lane == 0) c_kl[tt] = 0.5f * klt;
+            }
+        }
+        compose_stage_taps(a.att, b, B, N, C, w, tid, WB_THREADS, c_tx, c_ty);
+#pragma unroll
+        for (int k = 0; k < WPRE; ++k) { const int it = tid + k * WB_THREADS; if (it < N * w * w) c_win[it] = wpre[k]; }
+        compose_stage_windows(a.vrec, b, B, N, w, tid + WPRE * WB_THREADS, WB_THREADS, c_win);
+        if (tid < N) {
+            const float* ar = a.att + ((size_t)tid * B + b) * AIR_ATT_STRIDE;
+            const float zv = ar[AIR_ATT_Z], mk = ar[AIR_ATT_MASK], mp = ar[AIR_ATT_MASK_PREV];
+            const float kz = ar[AIR_ATT_KL_Z], ks = ar[AIR_ATT_KL_SCALE], kh = ar[AIR_ATT_KL_SHIFT];
+            c_z[tid] = zv;
+            c_act[tid] = mk != 0.0f ? 1 : 0;
+            c_rec[4 * tid] = mp; c_rec[4 * tid + 1] = kz; c_rec[4 * tid + 2] = ks; c_rec[4 * tid + 3] = kh;
+        }
+        __syncthreads();
+        if (!owner && mask_own == 0.0f) {                    // Select(active, ., 0): no gradient, and not this image's owner
+            for (int p = tid; p < w * w; p += WB_THREADS) { dgen[p] = 0.0f; if (dgen16) dgen16[p] = 0; }
+            if (tid < 4) dsx[tid] = 0.0f;
+            return;
+        }
+        if (owner && tid == 0) {
+            // running loss in the reference order: z KL (old mask), scale, shift, VAE KL (new mask) :411-493
+            float L = 0.0f;
+            int digits = 0;
+            for (int tt = 0; tt < N; ++tt) {
+                const bool mask = c_act[tt] != 0;
+                L = L + (c_rec[4 * tt] != 0.0f ? c_rec[4 * tt + 1] : 0.0f);
+                L = L + (mask ? c_rec[4 * tt + 2] : 0.0f);
+                L = L + (mask ? c_rec[4 * tt + 3] : 0.0f);
+                L = L + (mask ? c_kl[tt] : 0.0f);
+                digits += mask ? 1 : 0;
+                f.att[((size_t)tt * B + b) * AIR_ATT_STRIDE + AIR_ATT_KL_VAE] = c_kl[tt];
+            }
+            f.run_loss[b] = L;
+            c_sig[0] = L;
+            c_sig[1] = __builtin_bit_cast(float, digits);
+        }
+        // canvas + Bernoulli cross-entropy, pixel by pixel: d loss / d canvas into sh_g; the owner also stores it and the
+        // clipped reconstruction and sums the cross-entropy
+        const float gsc = dyn[AIR_DYN_GRAD_SCALE];
+        float acc = 0.0f;
+        const int cdi = WB_THREADS / C, cdj = WB_THREADS % C;
+        int i = tid / C, j = tid % C, k = 0;
+        for (int p = tid; p < CC; p += WB_THREADS, ++k) {
+            float xv;
+            if (xpre) {                                                 // (k < XPRE whenever xpre: a compile-time-indexed pick)
+                xv = xs[0];
+#pragma unroll
+                for (int q = 1; q < XPRE; ++q) xv = (k == q) ? xs[q] : xv;
+            } else xv = f.images[base + p];
+            const float R = compose_pixel(c_act, c_z, c_tx, c_ty, c_win, N, C, w, i, j);
+            i += cdi; j += cdj;
+            if (j >= C) { j -= C; ++i; }
+            float p1, p0;
+            const float r = compose_clip(R, p1, p0);                    // clipped_rec :582
+            const float dr = compose_dloss(R, xv, p1, p0, gsc);
+            sh_g[p] = dr;
+            if (owner) {
+                acc += xv * logf(p1) + (1.0f - xv) * logf(p0);          // :586-589
+                f.recon[base + p] = r;
+                f.d_recon[base + p] = dr;
+            }
+        }
+        if (owner) {
+            acc = air_block_sum_n<NW>(acc, c_red);
+            const float rl = -acc;
+            if (tid == 0) f.rec_loss[b] = rl;
+            if (tid == SIG) {
+                store_agent(f.loss_item + b, c_sig[0] + rl);            // loss += reconstruction_loss :593
+                store_agent(f.run_digits + b, __builtin_bit_cast(int, c_sig[1]));
+            }
+        }
+        AIR_STAMP_WG(7);
+        if (mask_own == 0.0f) {                              // (an owner only) no gradient: count the workgroup and finish here
+            for (int p = tid; p < w * w; p += WB_THREADS) { dgen[p] = 0.0f; if (dgen16) dgen16[p] = 0; }
+            if (tid < 4) dsx[tid] = 0.0f;
+            const int ticket = fold_signal();
+            if (tid == SIG) *sh_last = ticket == a.B - 1 ? 1 : 0;
+            __syncthreads();
+            fold_means(*sh_last != 0);
+            return;
+        }
+        win_pre = tid < w * w ? c_win[(size_t)t * w * w + tid] : 0.0f;
+    } else if (at[AIR_ATT_MASK] == 0.0f) {                 // Select(active, ., 0): no gradient
         for (int p = tid; p < w * w; p += WB_THREADS) { dgen[p] = 0.0f; if (dgen16) dgen16[p] = 0; }
         if (tid < 4) dsx[tid] = 0.0f;
         return;
     }
-    const float s = at[AIR_ATT_S], x = at[AIR_ATT_X], y = at[AIR_ATT_Y], z = at[AIR_ATT_Z];
+    const float s = FOLD ? fs : at[AIR_ATT_S], x = FOLD ? fx : at[AIR_ATT_X], y = FOLD ? fy : at[AIR_ATT_Y], z = FOLD ? fz : at[AIR_ATT_Z];
     const float ia = 1.0f / s, bx = (-x) / s, by = (-y) / s;
     for (int j = tid; j < C; j += WB_THREADS) {
         float tv;
@@ -571,7 +756,7 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
     if (tid < 8) sh_acc[tid] = 0.0f;
     if (tid >= 64 && tid < 64 + NW * 8) sh_red[tid - 64] = 0.0f;          // the feeding waves publish no pixel-loop partials
     if (tid < w * w) sh_win[tid] = win_pre;
-    if (ALLPH) {
+    if (ALLPH && !FOLD) {                                  // (FOLD: the compose front has filled sh_g)
 #pragma unroll
         for (int k = 0; k < 8; ++k) { const int p = k * WB_THREADS + tid; if (p < CC) sh_g[p] = g_pre[k]; }
         for (int p0 = 8 * WB_THREADS; p0 < CC; p0 += 8 * WB_THREADS) {
@@ -848,16 +1033,26 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
     // atomic pipe (whose traffic starves every other LDS request of the CU), so the taps are recomputed per pixel
     // (axis_tap: the same function of the same inputs as the tables) and d_recon / the window come from memory (L1 / L2:
     // 10 KB + 3 KB per workgroup at 50 x 50).
-    auto theta_loop = [&](int tid0, int NT) {
-        const int tt = tid - tid0;
-        if (tt < 0 || tt >= NT) return;
-        for (int p0 = tt; p0 < CC; p0 += 3 * NT) {
+    // FOLD: d_recon of this image exists in sh_g only (its owner's stores are for the launches behind this one), so the
+    // values of this thread's pixels -- pixel m of the loop below is tt + m * NT -- are taken into registers while the LDS
+    // still answers at full speed (theta_take, before the corner feeds start): THETA_G per thread cover the canvas
+    constexpr int THETA_G = 6;
+    float theta_g[THETA_G];
+    auto theta_take = [&](int tid0, int NT) {
+#pragma unroll
+        for (int m = 0; m < THETA_G; ++m) { const int p = tid - tid0 + m * NT; theta_g[m] = (p >= 0 && p < CC) ? sh_g[p] : 0.0f; }
+    };
+    // one round of the loop: pixels p0, p0 + NT, p0 + 2 NT (FOLD: round `it`, a compile-time constant, of theta_g)
+    auto theta_round = [&](int p0, int NT, auto itc) __attribute__((always_inline)) {
+        constexpr int it = decltype(itc)::value;
+        {
             Tap tx[3], ty[3];
             float Iv[3][4], gv[3], tj[3], ti[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const int p = min(p0 + k * NT, CC - 1), i = p / C, j = p - i * C;
-                gv[k] = (p0 + k * NT < CC) ? gsrc[p] : 0.0f;     // a pixel past the end contributes exact zeros
+                if constexpr (FOLD) gv[k] = theta_g[it * 3 + k];
+                else gv[k] = (p0 + k * NT < CC) ? gsrc[p] : 0.0f;     // a pixel past the end contributes exact zeros
                 tx[k] = axis_tap(j, C, w, ia, bx, &tj[k]); ty[k] = axis_tap(i, C, w, ia, by, &ti[k]);
             }
 #pragma unroll
@@ -873,6 +1068,17 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
                 d00 += gX * tj[k]; d02 += gX;                    // MatMul_grad: rows of theta x (x_t, y_t, 1)
                 d11 += gY * ti[k]; d12 += gY;
             }
+        }
+    };
+    auto theta_loop = [&](int tid0, int NT) {
+        const int tt = tid - tid0;
+        if (tt < 0 || tt >= NT) return;
+        if constexpr (FOLD) {
+            static_assert(THETA_G == 6, "two rounds of three pixels");
+            if (tt < CC) theta_round(tt, NT, std::integral_constant<int, 0>{});
+            if (tt + 3 * NT < CC) theta_round(tt + 3 * NT, NT, std::integral_constant<int, 1>{});
+        } else {
+            for (int p0 = tt; p0 < CC; p0 += 3 * NT) theta_round(p0, NT, std::integral_constant<int, 0>{});
         }
         // this wave's coordinate / z gradient partials (combined over the waves in a fixed order at the end)
         d00 = air_wave_sum(d00); d02 = air_wave_sum(d02); d11 = air_wave_sum(d11); d12 = air_wave_sum(d12); dz = air_wave_sum(dz);
@@ -1093,6 +1299,7 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
         chains(0, 4);
         AIR_STAMP(49);
         publish();
+        if (FOLD) theta_take(TH0, THN);
         AIR_STAMP(39);
         __syncthreads();
         AIR_STAMP(44);
@@ -1100,7 +1307,13 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
         if (wave < 4) {
             if ((pipe_mask >> wave) & 1) feed_corner(wave, 0, 4);
             else if (ring_ok) ring_corner(wave, 0, 4);
-        } else theta_loop(TH0, THN);
+        } else {
+            // an owner is counted here, beside the corner feeds and long after its two words were stored: neither the wait
+            // for those stores nor the add's round trip stands in front of a barrier
+            const int ticket = owner ? fold_signal() : -1;
+            theta_loop(TH0, THN);
+            if (owner && tid == SIG) *sh_last = ticket == a.B - 1 ? 1 : 0;
+        }
         AIR_STAMP(48);
         AIR_STAMP_WG(4);                       // wave 0's own feed is over
         __syncthreads();
@@ -1160,6 +1373,7 @@ __device__ __forceinline__ void write_bwd_graph_body(const air_write_bwd_t& a, i
         if (dgen16) dgen16[tid] = air_bf16_of(dgv);
     }
     if (tid < 64) finish_theta();
+    if (owner) fold_means(*sh_last != 0);                  // (behind this workgroup's own outputs: nothing waits for the means)
     AIR_STAMP(47);
     AIR_STAMP_WG(6);
 }
@@ -1173,6 +1387,11 @@ template <bool ALLPH>
 __global__ __launch_bounds__(WB_THREADS) void write_bwd_carried_kernel(air_write_bwd_t a)
 {
     write_bwd_graph_body<ALLPH, true>(a, 0);
+}
+// compose + the graph-order write backward in one launch (air_write_fwd_bwd)
+__global__ __launch_bounds__(WB_THREADS) void compose_write_bwd_graph_kernel(air_write_fwd_t f, air_write_bwd_t a, int32_t* arrive, int seq_flags)
+{
+    write_bwd_graph_body<true, false, true>(a, seq_flags, &f, arrive);
 }
 
 // ---------------------------------------------------------------------------
@@ -1352,6 +1571,57 @@ extern "C" int air_write_bwd(const air_write_bwd_t* a, void* stream) {
     int rc = ensure_lds(write_bwd_kernel, lds);
     if (rc) return rc;
     hipLaunchKernelGGL(write_bwd_kernel, dim3(a->B, a->N), dim3(WB_THREADS), lds, air_stream(stream), *a);
+    AIR_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// air_write_fwd_bwd: air_write_fwd and air_write_bwd (literal 2, with the batch means) as ONE launch.  ONE host predicate
+// says whether a descriptor pair has that form; the launcher and the name function both read it.
+// ---------------------------------------------------------------------------
+namespace {
+int compose_fold_plan(const air_write_fwd_t* f, const air_write_bwd_t* b) {
+    if (!f || !b) return AIR_EINVAL;
+    if (!f->vrec || !f->ml || !f->images || !f->dyn || !f->att || !f->recon || !f->rec_loss || !f->d_recon ||
+        !f->run_loss || !f->run_digits || !f->loss_item)
+        return AIR_EINVAL;                                          // (d_recon: a train step)
+    if (!b->d_gen_pre || !b->d_sxy_write || !b->fin_targets || !b->fin_scalars) return AIR_EINVAL;
+    // the two descriptors describe one step: the backward reads what the forward leaves
+    if (b->d_recon != f->d_recon || b->vrec != f->vrec || b->att != f->att || b->fin_loss_item != f->loss_item ||
+        b->fin_digits != f->run_digits)
+        return AIR_EINVAL;
+    if (f->B <= 0 || f->N <= 0 || f->C < 2 || f->w < 2 || f->Z <= 0) return AIR_EINVAL;
+    if (b->B != f->B || b->N != f->N || b->C != f->C || b->w != f->w) return AIR_EINVAL;
+    if (b->literal != 2) return AIR_EINVAL;
+    if (f->N > MAX_STEPS || 2 * f->w > THREADS || f->w * f->w > WB_THREADS) return AIR_ELIMIT;
+    // the hand-off of the batch means was measured with one workgroup per CU: no more items than the 256 CUs of the part
+    // this is built for, hence no longest-first order either.  An assumption about placement, not a guarantee (two of
+    // these workgroups fit a CU's LDS): include/air_hip.h says so
+    if (f->wb_order || b->order || (long)f->N * f->B > 256) return AIR_ELIMIT;
+    if (!write_bwd_graph_allph(f->C, f->w)) return AIR_ELIMIT;
+    if (!compose_fold_fits(f->N, f->C, f->w)) return AIR_ELIMIT;
+    if ((size_t)f->C * f->C > 6 * (size_t)(WB_THREADS - 4 * 64)) return AIR_ELIMIT;    // (THETA_G pixels per pixel-loop thread)
+    return 0;
+}
+}  // namespace
+
+extern "C" int air_write_fwd_bwd_kernel_name(const air_write_fwd_t* f, const air_write_bwd_t* b, char* buf, int n) {
+    if (!buf || n <= 0) return AIR_EINVAL;
+    const int rc = compose_fold_plan(f, b);
+    if (rc) return rc;
+    snprintf(buf, n, "compose_write_bwd_graph_kernel");
+    return 0;
+}
+
+extern "C" int air_write_fwd_bwd(const air_write_fwd_t* f, const air_write_bwd_t* b, int32_t* arrive, void* stream) {
+    int rc = compose_fold_plan(f, b);
+    if (rc) return rc;
+    if (!arrive) return AIR_EINVAL;
+    const size_t lds = write_bwd_graph_smem(b->C, b->w, true);
+    rc = ensure_lds(compose_write_bwd_graph_kernel, lds);
+    if (rc) return rc;
+    const int flags = accumulators(air_stream(stream));
+    hipLaunchKernelGGL(compose_write_bwd_graph_kernel, dim3(b->B, b->N), dim3(WB_THREADS), lds, air_stream(stream), *f, *b, arrive, flags);
     AIR_CHECK_LAUNCH();
     return 0;
 }

@@ -1,20 +1,29 @@
 """Per-workgroup phase timeline of the graph-order write backward at the bench configuration (debug build with
--DAIR_STAMPS made on the GPU box): which workgroup is the long pole of the launch, and in which phase.
-  python tools/wb_wg_stamps.py"""
+-DAIR_STAMPS made on the GPU box, or given with --lib PATH): which workgroup is the long pole of the launch, and in which
+phase.  `compose_write_bwd` looks at the launch of the captured steps, compose inside the write backward.
+  python tools/wb_wg_stamps.py [--lib PATH] [write_bwd | compose_write_bwd | <op name>] [--stress | --carried]"""
 import ctypes as C, glob, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "tf-attend-infer-repeat_amd")
 sys.path.insert(0, ROOT); sys.path.insert(0, PKG)
 out = "/tmp/libair_hip_stamps.so"
+PREBUILT = None
+if "--lib" in sys.argv:
+    i = sys.argv.index("--lib")
+    PREBUILT = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 src = sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip")))
 from concurrent.futures import ThreadPoolExecutor
 flags = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DAIR_STAMPS",
          "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc")]
 objs = ["/tmp/stamps_%s.o" % os.path.basename(f) for f in src]
-with ThreadPoolExecutor(8) as ex:
-    list(ex.map(lambda fo: subprocess.check_call(flags + ["-c", fo[0], "-o", fo[1]]), zip(src, objs)))
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out])
+if PREBUILT:
+    out = PREBUILT
+else:
+    with ThreadPoolExecutor(8) as ex:
+        list(ex.map(lambda fo: subprocess.check_call(flags + ["-c", fo[0], "-o", fo[1]]), zip(src, objs)))
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out])
 import torch
 from air import _hip as H
 H._LIB = H.load(out)
@@ -37,7 +46,8 @@ for _ in range(5):
 torch.cuda.synchronize()
 s = m._stream()
 which = sys.argv[1] if len(sys.argv) > 1 else "write_bwd"
-op = [o for o in m._fwd + m._bwd if which in o.name][0]
+FOLD = which == "compose_write_bwd"
+op = m._fold_op if FOLD else [o for o in m._fwd + m._bwd if which in o.name][0]
 names = ["setup", "stage_T", "chains+outputs", "feed(wave 0)", "wait for the others", "final"]
 if STRESS:
     # per-CU occupancy of the LDS atomic pipe and of the lane rings at the 128x128 configuration: every workgroup stamps its
@@ -101,13 +111,29 @@ for rep in range(3):
     n = 192
     buf = (C.c_ulonglong * (n * 8))()
     H._LIB.air_debug_stamps_wg(buf, n * 8)
-    v = np.array(list(buf), dtype=np.int64).reshape(n, 8)[:, :7] / 100.0
-    if which != "write_bwd":
+    v8 = np.array(list(buf), dtype=np.int64).reshape(n, 8) / 100.0
+    v = v8[:, :7]
+    if FOLD:
+        # every workgroup stamps its start [0] and the end of its compose front [7]; the ones that go on, the phases of the
+        # write backward ([1] is then newer than [0]: an older one is left from a launch in which the item was active)
+        ran = v8[:, 7] > v8[:, 0]                     # (an inactive item that owns no image returns before the pixel loop)
+        front = (v8[:, 7] - v8[:, 0])[ran]
+        own = (np.arange(n) < 64)[ran]
+        print("launch %d: compose front of %d workgroups: mean %.2f max %.2f us (owners %.2f / %.2f, the others %.2f / %.2f)" % (
+            rep, int(ran.sum()), front.mean(), front.max(), front[own].mean(), front[own].max(), front[~own].mean(), front[~own].max()))
+        live = v[:, 1] > v[:, 0]
+        v8, v = v8[live], v[live]
+        tot = v[:, 6] - v[:, 0]
+        w = int(np.argmax(v[:, 6]))
+        print("  of the last workgroup to end (item %d of the live ones): front %.2f, set-up after it %.2f, total %.2f us" % (
+            w, v8[w, 7] - v8[w, 0], v8[w, 1] - v8[w, 7], tot[w]))
+    elif which != "write_bwd":
         print("launch %d (%s): start skew %.2f us, first start -> last end %.2f us, workgroup total mean %.2f max %.2f" % (
             rep, which, v[:, 0].max() - v[:, 0].min(), v[:, 6].max() - v[:, 0].min(), (v[:, 6] - v[:, 0]).mean(), (v[:, 6] - v[:, 0]).max()))
         continue
-    live = v[:, 1] > 0
-    v = v[live]
+    if not FOLD:
+        live = v[:, 1] > v[:, 0]                      # (an older [1] is left from a launch in which the item was active)
+        v = v[live]
     t0 = v[:, 0].min()
     d = np.diff(v, axis=1)
     tot = v[:, 6] - v[:, 0]
