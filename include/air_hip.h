@@ -461,7 +461,7 @@ typedef struct {
     const float* fin_loss_item; const int32_t* fin_targets; const int32_t* fin_digits;
     float* fin_scalars;
     uint16_t* d_gen_pre16;               /* bf16 twin of d_gen_pre (nullable) */
-    /* nullable (literal 2 only): workgroup i of the launch computes item order[i] = t * B + b instead of item i -- the
+    /* nullable (literals 2 and 4; AIR_EINVAL with literal 0): workgroup i of the launch computes item order[i] = t * B + b instead of item i -- the
      * longest-first permutation of air_write_fwd_t.wb_order (the hardware hands workgroups out in launch order).  Results
      * do not depend on it.  With `order` the batch-mean finisher is the LAST workgroup of the launch. */
     const int32_t* order;

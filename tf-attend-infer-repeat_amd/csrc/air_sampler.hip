@@ -519,99 +519,30 @@ __global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
         return;
     }
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int vt = tid;
-    const int C = a.C, w = a.w, Z = a.Z, N = a.N, B = a.B;
-    float* sh_red = smem;                                    // [16]
-    float* sh_z = smem + 16;                                 // [MAX_STEPS] z_pres
-    int* sh_act = reinterpret_cast<int*>(smem + 16 + MAX_STEPS);         // [MAX_STEPS]
-    float* sh_kl = smem + 16 + 2 * MAX_STEPS;                            // [MAX_STEPS] VAE KL per step
-    float* sh_rec = smem + 16 + 3 * MAX_STEPS;                           // [MAX_STEPS][4]: mask_prev, KL z, KL scale, KL shift
-    Tap* sh_tx = reinterpret_cast<Tap*>(smem + 16 + 7 * MAX_STEPS);      // [N][C]
-    Tap* sh_ty = sh_tx + (size_t)N * C;                                    // [N][C]
-    float* sh_win = reinterpret_cast<float*>(sh_ty + (size_t)N * C);      // [N][w*w]
-    const float* dyn = a.dyn;
+    const int C = a.C, w = a.w, N = a.N, B = a.B;
+    const ComposeLds L = compose_lds(smem, N, C, w);
     const size_t base = (size_t)b * C * C;
-    const int CC = C * C;
-
-    // the image pixels of this thread do not depend on anything computed here: on small canvases (<= 4 per thread) their
-    // loads go out with phase A's -- one memory round trip instead of two
-    constexpr int XPRE = 4;
-    const bool xpre = CC <= XPRE * CF_THREADS;
-    float xs[XPRE];
-#pragma unroll
-    for (int k = 0; k < XPRE; ++k) { const int p = vt + k * CF_THREADS; xs[k] = a.images[base + ((xpre && p < CC) ? p : 0)]; }
+    float xs[COMPOSE_XPRE];
+    const bool xpre = compose_prefetch_image(a.images, base, C * C, tid, xs);
 
     // phase A -- everything that only needs the per-step records, for all steps at once
     // (independent loads: one memory round trip instead of one per step)
-    {
-        for (int t = wave; t < N; t += NT / 64) {
-            // VAE KL :479-493 (a public output whether or not the item is still active): one wave per step
-            const float* ml = a.ml + ((size_t)t * B + b) * 2 * Z;
-            const float pv = dyn[AIR_DYN_VAE_PV], pm = dyn[AIR_DYN_VAE_PM], plv = dyn[AIR_DYN_VAE_PLV];
-            float klt = 0.0f;
-            for (int j = lane; j < Z; j += 64) {
-                const float lv = ml[Z + j];
-                klt += gauss_kl_term(plv, lv, expf(lv), pv, ml[j], pm);
-            }
-            klt = air_wave_sum(klt);
-            if (lane == 0) sh_kl[t] = 0.5f * klt;
-        }
-    }
-    compose_stage(a.att, a.vrec, b, B, N, C, w, tid, NT, sh_tx, sh_ty, sh_win);
-    if (tid < N) {
-        // one thread per step fetches its record (six independent loads); thread 0 below then sums from LDS -- as a loop
-        // of conditional loads on one thread it was a dozen memory round trips in a row
-        const float* at = a.att + ((size_t)tid * B + b) * AIR_ATT_STRIDE;
-        const float zv = at[AIR_ATT_Z], mk = at[AIR_ATT_MASK], mp = at[AIR_ATT_MASK_PREV];
-        const float kz = at[AIR_ATT_KL_Z], ks = at[AIR_ATT_KL_SCALE], kh = at[AIR_ATT_KL_SHIFT];
-        sh_z[tid] = zv;
-        sh_act[tid] = mk != 0.0f ? 1 : 0;
-        sh_rec[4 * tid] = mp; sh_rec[4 * tid + 1] = kz; sh_rec[4 * tid + 2] = ks; sh_rec[4 * tid + 3] = kh;
-    }
+    compose_vae_kl<NT / 64>(a.ml, a.dyn, b, B, N, a.Z, lane, wave, L.kl);
+    compose_stage(a.att, a.vrec, b, B, N, C, w, tid, NT, L.tx, L.ty, L.win);
+    compose_fetch_records(a.att, b, B, N, tid, L);
     __syncthreads();
     float Lkeep = 0.0f;
     if (tid == 0) {
-        // running loss in the reference order: z KL (old mask), scale, shift, VAE KL (new mask) :411-493
-        float L = 0.0f;
-        int digits = 0;
-        for (int t = 0; t < N; ++t) {
-            float* at = a.att + ((size_t)t * B + b) * AIR_ATT_STRIDE;
-            const bool mask = sh_act[t] != 0;
-            L = L + (sh_rec[4 * t] != 0.0f ? sh_rec[4 * t + 1] : 0.0f);
-            L = L + (mask ? sh_rec[4 * t + 2] : 0.0f);
-            L = L + (mask ? sh_rec[4 * t + 3] : 0.0f);
-            L = L + (mask ? sh_kl[t] : 0.0f);
-            digits += mask ? 1 : 0;
-            at[AIR_ATT_KL_VAE] = sh_kl[t];
-        }
-        a.run_loss[b] = L;
+        int digits;
+        compose_running_loss(L, a.att, b, B, N, Lkeep, digits);
+        a.run_loss[b] = Lkeep;
         a.run_digits[b] = digits;
-        Lkeep = L;
     }
 
     // phase B -- canvas + Bernoulli cross-entropy, pixel by pixel
-    const float gsc = dyn[AIR_DYN_GRAD_SCALE];
-    float acc = 0.0f;
-    const int di = CF_THREADS / C, dj = CF_THREADS % C;
-    int i = vt / C, j = vt % C;
-    int k = 0;
-    for (int p = vt; p < CC; p += CF_THREADS, ++k) {
-        float x;
-        if (xpre) {                                                 // (k < XPRE whenever xpre: a compile-time-indexed pick)
-            x = xs[0];
-#pragma unroll
-            for (int q = 1; q < XPRE; ++q) x = (k == q) ? xs[q] : x;
-        } else x = a.images[base + p];
-        const float R = compose_pixel(sh_act, sh_z, sh_tx, sh_ty, sh_win, N, C, w, i, j);
-        i += di; j += dj;
-        if (j >= C) { j -= C; ++i; }
-        float p1, p0;
-        const float r = compose_clip(R, p1, p0);                    // clipped_rec :582
-        acc += x * logf(p1) + (1.0f - x) * logf(p0);                // :586-589
-        a.recon[base + p] = r;
-        if (a.d_recon) a.d_recon[base + p] = compose_dloss(R, x, p1, p0, gsc);
-    }
-    acc = air_block_sum_n<NT / 64>(acc, sh_red);
+    float acc = compose_pixels<1, false>(L, a.images, base, xs, xpre, N, C, w, a.dyn[AIR_DYN_GRAD_SCALE], tid, true,
+                                         a.recon, a.d_recon, nullptr);
+    acc = air_block_sum_n<NT / 64>(acc, L.red);
     if (tid == 0) {
         const float rl = -acc;
         a.rec_loss[b] = rl;

@@ -65,6 +65,23 @@ __device__ __forceinline__ GenTap generic_tap(const float* th, int i, int j, int
     return t;
 }
 
+// generic transformer backward, d theta: one output pixel's share.  ga..gd = g * Ia..Id (summed over the channels where
+// there are several); graph_dxy's order (AddN over wa, wb, wc, wd) -- the two axes have their own (W - 1.001) here -- then the
+// MatMul_grad contraction with (x_t, y_t, 1) into s6
+__device__ __forceinline__ void generic_dtheta_pixel(const GenTap& t, float ga, float gb, float gc, float gd, int Hi, int Wi, float (&s6)[6]) {
+    const float dX = ((-(ga * t.wy0) + -(gb * t.wy1)) + gc * t.wy0) + gd * t.wy1;
+    const float dY = ((-(t.wx0 * ga) + t.wx0 * gb) + -(t.wx1 * gc)) + t.wx1 * gd;
+    const float gX = (dX / 2.0f) * ((float)Wi - 1.001f);
+    const float gY = (dY / 2.0f) * ((float)Hi - 1.001f);
+    s6[0] += gX * t.xt; s6[1] += gX * t.yt; s6[2] += gX;
+    s6[3] += gY * t.xt; s6[4] += gY * t.yt; s6[5] += gY;
+}
+// generic transformer backward, d U: weight (wa, wb, wc, wd) and input pixel of tap ph of one output pixel
+__device__ __forceinline__ void generic_tap_term(const GenTap& t, int ph, int Wi, float& wgt, int& idx) {
+    wgt = ((ph & 2) ? t.wx1 : t.wx0) * ((ph & 1) ? t.wy1 : t.wy0);
+    idx = ((ph & 1) ? t.y1 : t.y0) * Wi + ((ph & 2) ? t.x1 : t.x0);
+}
+
 // Gradient of one output pixel wrt its source coordinates (X, Y) in the op order of the reference's SAVED graph
 // (model/air-model.meta, executed by the graph executor of tests/test_graph_exec.py).  For an out-of-range pixel (both
 // taps clipped to one index) the four legs cancel exactly in real arithmetic but NOT in fp32: the rounding residue,
@@ -164,6 +181,110 @@ __device__ __forceinline__ float gauss_kl_term(float plv, float lv, float var, f
     return (((plv - lv) - 1.0f) + var / pv) + (d * d) / pv;
 }
 
+// ---- the compose front: what air_write_fwd computes per image, as parts.  write_fwd_kernel runs them on one workgroup
+// per image; the compose fold of the write backward (compose_write_bwd_graph_kernel) runs them at the front of every
+// workgroup of the image, the workgroup of step 0 (the owner) storing the image's outputs ----------------------------------
+// compose's LDS in write_smem's layout, from `base`
+struct ComposeLds {
+    float* red; float* z; int* act;      // [16]; [MAX_STEPS] z_pres; [MAX_STEPS]
+    float* kl; float* rec;               // [MAX_STEPS] VAE KL per step; [MAX_STEPS][4]: mask_prev, KL z, KL scale, KL shift
+    Tap* tx; Tap* ty; float* win;        // [N][C] each; [N][w*w]
+};
+__device__ __forceinline__ ComposeLds compose_lds(float* base, int N, int C, int w) {
+    ComposeLds L;
+    L.red = base; L.z = base + 16; L.act = reinterpret_cast<int*>(base + 16 + MAX_STEPS);
+    L.kl = base + 16 + 2 * MAX_STEPS; L.rec = base + 16 + 3 * MAX_STEPS;
+    L.tx = reinterpret_cast<Tap*>(base + 16 + 7 * MAX_STEPS); L.ty = L.tx + (size_t)N * C;
+    L.win = reinterpret_cast<float*>(L.ty + (size_t)N * C);
+    return L;
+}
+// VAE KL :479-493 of every step of image b (a public output whether or not the item is still active): one wave per step
+template <int NWAVES>
+__device__ __forceinline__ void compose_vae_kl(const float* ml_all, const float* dyn, int b, int B, int N, int Z, int lane, int wave,
+                                               float* sh_kl) {
+    for (int t = wave; t < N; t += NWAVES) {
+        const float* ml = ml_all + ((size_t)t * B + b) * 2 * Z;
+        const float pv = dyn[AIR_DYN_VAE_PV], pm = dyn[AIR_DYN_VAE_PM], plv = dyn[AIR_DYN_VAE_PLV];
+        float klt = 0.0f;
+        for (int j = lane; j < Z; j += 64) {
+            const float lv = ml[Z + j];
+            klt += gauss_kl_term(plv, lv, expf(lv), pv, ml[j], pm);
+        }
+        klt = air_wave_sum(klt);
+        if (lane == 0) sh_kl[t] = 0.5f * klt;
+    }
+}
+// one thread per step fetches its record (six independent loads); one thread then sums from LDS (compose_running_loss) -- as
+// a loop of conditional loads on one thread it was a dozen memory round trips in a row
+__device__ __forceinline__ void compose_fetch_records(const float* att, int b, int B, int N, int tid, const ComposeLds& L) {
+    if (tid < N) {
+        const float* at = att + ((size_t)tid * B + b) * AIR_ATT_STRIDE;
+        const float zv = at[AIR_ATT_Z], mk = at[AIR_ATT_MASK], mp = at[AIR_ATT_MASK_PREV];
+        const float kz = at[AIR_ATT_KL_Z], ks = at[AIR_ATT_KL_SCALE], kh = at[AIR_ATT_KL_SHIFT];
+        L.z[tid] = zv;
+        L.act[tid] = mk != 0.0f ? 1 : 0;
+        L.rec[4 * tid] = mp; L.rec[4 * tid + 1] = kz; L.rec[4 * tid + 2] = ks; L.rec[4 * tid + 3] = kh;
+    }
+}
+// (one thread) the running loss in the reference order: z KL (old mask), scale, shift, VAE KL (new mask) :411-493; the digit
+// count; the steps' VAE KL into their records
+__device__ __forceinline__ void compose_running_loss(const ComposeLds& L, float* att, int b, int B, int N, float& loss, int& digits) {
+    loss = 0.0f;
+    digits = 0;
+    for (int t = 0; t < N; ++t) {
+        const bool mask = L.act[t] != 0;
+        loss = loss + (L.rec[4 * t] != 0.0f ? L.rec[4 * t + 1] : 0.0f);
+        loss = loss + (mask ? L.rec[4 * t + 2] : 0.0f);
+        loss = loss + (mask ? L.rec[4 * t + 3] : 0.0f);
+        loss = loss + (mask ? L.kl[t] : 0.0f);
+        digits += mask ? 1 : 0;
+        att[((size_t)t * B + b) * AIR_ATT_STRIDE + AIR_ATT_KL_VAE] = L.kl[t];
+    }
+}
+// the image pixels of a thread do not depend on anything computed in the launch: on small canvases (<= COMPOSE_XPRE per
+// thread) their loads go out with the set-up's -- one memory round trip instead of two
+constexpr int COMPOSE_XPRE = 4;
+__device__ __forceinline__ bool compose_prefetch_image(const float* images, size_t base, int CC, int tid, float (&xs)[COMPOSE_XPRE]) {
+    const bool xpre = CC <= COMPOSE_XPRE * CF_THREADS;
+#pragma unroll
+    for (int k = 0; k < COMPOSE_XPRE; ++k) { const int p = tid + k * CF_THREADS; xs[k] = images[base + ((xpre && p < CC) ? p : 0)]; }
+    return xpre;
+}
+// canvas + Bernoulli cross-entropy, pixel by pixel, CF_THREADS threads; returns the thread's part of the cross-entropy sum.
+// Compile-time: OUT, who stores the image's outputs (the clipped reconstruction, d loss / d canvas to memory where g_mem is
+// given, and the sum) -- 0 nobody, 1 every caller, 2 the callers with `owner`; G_LDS, d loss / d canvas into g_lds as well.
+// (Both callers prefetch the image values -- xs / xpre of compose_prefetch_image -- so that is no switch.)
+template <int OUT, bool G_LDS>
+__device__ __forceinline__ float compose_pixels(const ComposeLds& L, const float* images, size_t base, const float (&xs)[COMPOSE_XPRE],
+                                                bool xpre, int N, int C, int w, float gsc, int tid, bool owner,
+                                                float* recon, float* g_mem, float* g_lds) {
+    const int CC = C * C;
+    const bool store = OUT == 1 || (OUT == 2 && owner);
+    float acc = 0.0f;
+    const int di = CF_THREADS / C, dj = CF_THREADS % C;
+    int i = tid / C, j = tid % C, k = 0;
+    for (int p = tid; p < CC; p += CF_THREADS, ++k) {
+        float x;
+        // (k < COMPOSE_XPRE whenever xpre: a compile-time-indexed pick, written out -- as a loop over a referenced array it
+        // was left in scratch memory)
+        static_assert(COMPOSE_XPRE == 4, "the pick below");
+        if (xpre) x = k == 3 ? xs[3] : k == 2 ? xs[2] : k == 1 ? xs[1] : xs[0];
+        else x = images[base + p];
+        const float R = compose_pixel(L.act, L.z, L.tx, L.ty, L.win, N, C, w, i, j);
+        i += di; j += dj;
+        if (j >= C) { j -= C; ++i; }
+        float p1, p0;
+        const float r = compose_clip(R, p1, p0);                    // clipped_rec :582
+        if (G_LDS) g_lds[p] = compose_dloss(R, x, p1, p0, gsc);
+        if (store) {
+            acc += x * logf(p1) + (1.0f - x) * logf(p0);            // :586-589
+            recon[base + p] = r;
+            if (g_mem) g_mem[base + p] = compose_dloss(R, x, p1, p0, gsc);
+        }
+    }
+    return acc;
+}
+
 template <typename K>
 int ensure_lds(K kernel, size_t bytes) { return air_grant_lds(reinterpret_cast<const void*>(kernel), bytes); }
 
@@ -183,16 +304,37 @@ inline size_t attend_bwd_smem(int C, int w) {
 inline size_t write_smem(int N, int C, int w) { return (16 + 7 * MAX_STEPS + (size_t)N * (8 * C + (size_t)w * w)) * sizeof(float); }
 // air_render
 inline size_t render_smem(int N, int C, int w) { return (2 * MAX_STEPS + (size_t)N * (8 * (size_t)C + (size_t)w * w)) * sizeof(float); }
-// air_write_bwd, literals 2 and 4: all four taps' terms resident (allph) when they fit next to a second workgroup's share of the LDS
-inline size_t write_bwd_graph_smem(int C, int w, bool allph) {
-    return (136 + 8 * C + ((C + 3) & ~3) + 8 * C + ((8 * w + 3) & ~3) + (((size_t)w * w + 3) & ~3) +
-            (allph ? 5 : 1) * (((size_t)C * C + 3) & ~3)) * sizeof(float);
+// air_write_bwd, literals 2 and 4: the ONE carve-up of the dynamic LDS, as offsets in floats -- the kernels build their views
+// from it and the host sizes the launch with it.  All four taps' terms are resident (allph) when they fit next to a second
+// workgroup's share of the LDS; d loss / d canvas is staged (g) only then
+struct WbLayout {
+    size_t red, acc;     // [128] fin sums / per-wave partials [16][8]; [4] corner accumulators + [4] corner term counts
+    size_t tx, ty, t;    // [C] Tap each; [C] linspace
+    size_t ci, ri;       // [C] int4 each: per canvas column / row {first, count} of the runs of its two keys
+    size_t run, win;     // [4][w][2]: run [lo, hi] of every key of x0 / x1 / y0 / y1; [w*w]
+    size_t g, T;         // [C*C] (allph only); [4 or 1][C*C] terms, rectangle-blocked per tap (16-byte aligned)
+    size_t floats;       // the whole of it
+};
+__host__ __device__ inline WbLayout write_bwd_graph_layout(int C, int w, bool allph) {
+    const size_t c = (size_t)C, ww = (size_t)w * w, CCp = (c * c + 3) & ~(size_t)3;
+    WbLayout L;
+    L.red = 0; L.acc = 128; L.tx = 136; L.ty = L.tx + 4 * c; L.t = L.ty + 4 * c;
+    L.ci = L.t + ((c + 3) & ~(size_t)3); L.ri = L.ci + 4 * c; L.run = L.ri + 4 * c;
+    L.win = L.run + ((8 * (size_t)w + 3) & ~(size_t)3);
+    L.g = L.win + ((ww + 3) & ~(size_t)3);
+    L.T = L.g + (allph ? CCp : 0);
+    L.floats = L.T + (allph ? 4 : 1) * CCp;
+    return L;
 }
+inline size_t write_bwd_graph_smem(int C, int w, bool allph) { return write_bwd_graph_layout(C, w, allph).floats * sizeof(float); }
 inline bool write_bwd_graph_allph(int C, int w) { return write_bwd_graph_smem(C, w, true) <= 80 * 1024; }
 // air_write_fwd_bwd: compose's scratch (write_smem's layout + the two words handed to the signalling lane) lies over the
 // term buffer of the all-taps-resident write backward, which is dead until the term phase
 inline size_t compose_fold_floats(int N, int C, int w) { return write_smem(N, C, w) / sizeof(float) + 4; }
-inline bool compose_fold_fits(int N, int C, int w) { return compose_fold_floats(N, C, w) <= 4 * (((size_t)C * C + 3) & ~3); }
+inline bool compose_fold_fits(int N, int C, int w) {
+    const WbLayout L = write_bwd_graph_layout(C, w, true);
+    return compose_fold_floats(N, C, w) <= L.floats - L.T;
+}
 // air_write_bwd, literal 0
 inline size_t write_bwd_smem(int C, int w) { return (64 + 8 * C + C + 8 * w + (size_t)w * w + (size_t)C * w + (size_t)C * C) * sizeof(float); }
 
