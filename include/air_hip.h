@@ -275,8 +275,8 @@ int air_wgrad_num_blocks(const air_wgrad_t* probs, int count);
  * STRIPS -- at precision 1 a twin problem of >= 512 tiles (K = 64, 128, 192 or 256; 16-byte dY rows; M % 4 == 0) gives each
  * workgroup 2 (from 2048 tiles: 4) consecutive column tiles of a block-row, its A block fetched once and its MFMA fragments
  * kept in registers.  Values, db and the partials (still one per tile, at the same index) are bit-identical either way.
- * For a problem of >= 512 tiles (any precision) the tile that sums db of column tile nt is the one in block-row nt % 16,
- * not block-row 0.  Diagnostic; AIR_WGRAD_STRIP=<tiles per workgroup, 0 = off> overrides. */
+ * For a problem of >= 512 tiles (any precision) the tile that sums db of column tile nt is the one in block-row
+ * nt % min(16, block-rows), not block-row 0.  Diagnostic. */
 int air_wgrad_num_workgroups(const air_wgrad_t* probs, int count, int precision);
 #define AIR_MAX_WGRAD_PROBLEMS 16
 int air_wgrad_grouped(const air_wgrad_t* probs /*HOST array, <= AIR_MAX_WGRAD_PROBLEMS*/, int count, int precision,

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import abi_check as abi
+import wgrad_edge_cases as wec
 
 pytestmark = pytest.mark.gpu
 
@@ -539,6 +540,16 @@ def test_heads_out_wgrad_matches_grouped_launch(H):
         h = head[o]
         np.testing.assert_allclose(got[o, :offs[h + 1] - offs[h]], full[o, offs[h]:offs[h + 1]], rtol=1e-4, atol=2e-4)
     np.testing.assert_allclose(db.cpu().numpy(), d7.astype(np.float64).sum(0)[:7], rtol=1e-5, atol=1e-4)
+    # ... and the head_pack problem of the grouped launch (exact fp32 products, another order of summation)
+    gw, gb = torch.full((7, Hmax), float("nan"), device="cuda"), torch.full((7,), float("nan"), device="cuda")
+    arr = (H.Wgrad * 1)(H.Wgrad(_p(dt), _p(ht), _p(gw), _p(gb), 8, HT, K, 8, HT, Hmax, 1, Hs, Hh, Hz))
+    H.check(H.lib().air_wgrad_grouped(arr, 1, 0, None, None, _stream()), "air_wgrad_grouped")
+    torch.cuda.synchronize()
+    for o in range(7):
+        wd = offs[head[o] + 1] - offs[head[o]]
+        np.testing.assert_allclose(gw.cpu().numpy()[o, :wd], got[o, :wd], rtol=1e-4, atol=2e-4)
+        assert bool(torch.isnan(gw[o, wd:]).all())                              # beyond the unit's segment: not written
+    np.testing.assert_allclose(gb.cpu().numpy(), db.cpu().numpy(), rtol=1e-5, atol=1e-4)
 
 
 @pytest.mark.parametrize("Hi,Wi,Ho,Wo", [(28, 28, 50, 50), (50, 50, 28, 28), (9, 11, 7, 8), (128, 128, 28, 28)])
@@ -1161,12 +1172,13 @@ def test_wgrad_grouped_bf16_twins_bit_identical(H, shapes):
                                  _p(A16) if twins else None, _p(Y16) if twins else None))
         arr = (H.Wgrad * len(probs))(*probs)
         nblk = H.lib().air_wgrad_num_blocks(arr, len(probs))
-        # strips: only with twins, only for the big problems (>= 512 tiles: 2 column tiles per workgroup, >= 2048: 4)
+        # strips: only with twins, only for the big problems (>= 512 tiles: 2 column tiles per workgroup, >= 2048: 4; fewer
+        # or none where N is not made of whole strips -- strip_of, restated in tests/wgrad_edge_cases.py)
         saved = 0
         for (M, N, K) in shapes:
-            tiles = -(-M // 64) * -(-N // 64)
-            if tiles >= 512 and K in (64, 128, 192, 256) and M % 4 == 0 and N % 256 == 0:
-                saved += tiles - tiles // (4 if tiles >= 2048 else 2)
+            case = wec.dense_case(M, N, K)
+            if wec.strip_of(case):
+                saved += wec.tiles(case) - wec.tiles(case) // wec.strip_of(case)
         assert H.lib().air_wgrad_num_workgroups(arr, len(probs), 1) == (nblk - saved if twins else nblk)
         assert H.lib().air_wgrad_num_workgroups(arr, len(probs), 0) == nblk
         part = torch.full((nblk,), float("nan"), device=dev)

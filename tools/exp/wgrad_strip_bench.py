@@ -1,6 +1,6 @@
 """Stand-alone timing of the input-weight gradient problem of configs[3] (dWx = X^T . sum_t dgates: M = 16384, N = 1024,
-K = 256, bf16 twins) through air_wgrad_grouped: python tools/exp/wgrad_strip_bench.py  (AIR_WGRAD_STRIP=<g> selects the
-strip width, 0 = one tile per workgroup)."""
+K = 256, bf16 twins) through air_wgrad_grouped: python tools/exp/wgrad_strip_bench.py [M N K]  (the strip width is the
+library's own choice, strip_of in csrc/air_wgrad.hip; the workgroup count printed tells which)."""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tf-attend-infer-repeat_amd"))
@@ -28,5 +28,4 @@ e0.record()
 for _ in range(R):
     lib.air_wgrad_grouped(arr, 1, 1, p(part), p(ist), s)
 e1.record(); torch.cuda.synchronize()
-print("strip=%s workgroups=%d tiles=%d: %.2f us per launch" % (os.environ.get("AIR_WGRAD_STRIP", "default"),
-      lib.air_wgrad_num_workgroups(arr, 1, 1), nb, e0.elapsed_time(e1) * 1000 / R))
+print("workgroups=%d tiles=%d: %.2f us per launch" % (lib.air_wgrad_num_workgroups(arr, 1, 1), nb, e0.elapsed_time(e1) * 1000 / R))

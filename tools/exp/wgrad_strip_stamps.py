@@ -27,7 +27,7 @@ buf = (C.c_ulonglong * 64)()
 lib.air_debug_stamps_wgrad(buf, 64)
 v = list(buf)
 names = {0: "enter", 1: "A + dY0 staged"}
-G = int(os.environ.get("AIR_WGRAD_STRIP", 4))
+G = 4                                         # strip_of: 4 column tiles per workgroup from 2048 tiles (this problem has 4096)
 for j in range(G):
     for k, nm in enumerate(("barrier", "mfma", "Ct in LDS", "stored", "published", "next staged")):
         names[2 + 6 * j + k] = "t%d %s" % (j, nm)
