@@ -163,6 +163,19 @@ __device__ __forceinline__ void publish_sq(float sq, float* sq_partials, int32_t
         if (part == 0 && istate) istate[AIR_IST_GLOBAL_STEP] += 1;
     }
 }
+// The same partial off the workgroup's chain (bf16 launch), in two halves with air_block_sum_256's order of additions:
+// park_sq leaves each wave's sum in its own word of `red` -- words nothing else has used, so no barrier stands in front;
+// publish_parked, behind ONE barrier of the caller, adds the four in wave order and stores.  A one-tile workgroup parks
+// in sq_red (behind the images: the output tile does not alias it), a strip parks every tile in words of its own while
+// the next tile is staged and publishes them all behind its last tile's stores.
+__device__ __forceinline__ void park_sq(float sq, float* red) {
+    sq = air_wave_sum(sq);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+}
+__device__ __forceinline__ void publish_parked(const float* red, float* sq_partials, int32_t* istate, int part) {
+    sq_partials[part] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (part == 0 && istate) istate[AIR_IST_GLOBAL_STEP] += 1;
+}
 
 // Epilogue of the weight-gradient kernels: the tile in Ct goes to pr.dW (whole rows per store
 // instruction) and its sum of squares to the caller.  pr.dW == NULL: nothing is stored, only the
@@ -552,6 +565,33 @@ __device__ __forceinline__ float bias_tw(const Prob& pr, int n0)
     return (bias_thread && bg == 0) ? store_db(pr.db, csum, n0 + 4 * bq, N) : 0.0f;
 }
 
+// The same sums with their loads taken off the end of a one-tile workgroup's chain (tile_bf16_tw; one round of images,
+// 16-byte rows of dY: bias_early): bias_issue sends image c's eight loads, bias_add adds them in bias_tw's order.  The tile
+// issues image 0 behind its operand loads at entry, images 1 and 2 once image 0 is summed, in front of the barrier and the
+// MFMAs -- only in the workgroups that own a bias column (block-uniform branches; the registers are never merged with
+// other values behind them).  14.1 -> 12.0 us for the launch of the 50 x 50 step: its last workgroups were the owners,
+// which fetched their three images one round trip after the other behind the MFMAs.
+__device__ __forceinline__ bool bias_early(const Prob& pr) {
+    return pr.K <= NIMG_W * KB && (pr.K % KB) == 0 && ((pr.ldb & 3) == 0) && aligned16(pr.dY);
+}
+// (whole images: every row exists; a column quad at or past N reads quad 0 instead and is masked when added -- one
+// per-thread address, the rows at uniform steps)
+__device__ __forceinline__ void bias_issue(float4 (&v)[8], const Prob& pr, int n0, int c) {
+    const int bg = threadIdx.x & 7, col = n0 + ((threadIdx.x & 127) >> 3) * 4;
+    const float* p = pr.dY + ((size_t)(unsigned)(c * KB + bg * 8) * (unsigned)pr.ldb + (unsigned)(col < pr.N ? col : 0));
+    const size_t step = (size_t)(unsigned)pr.ldb;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = *reinterpret_cast<const float4*>(p + r * step);
+}
+__device__ __forceinline__ void bias_add(float (&csum)[4], const float4 (&v)[8], const Prob& pr, int n0, int c) {
+    const int bg = threadIdx.x & 7, bq = (threadIdx.x & 127) >> 3;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const float4 t = mask4(v[r], c * KB + bg * 8 + r, n0 + 4 * bq, pr.K, pr.N);
+        csum[0] += t.x; csum[1] += t.y; csum[2] += t.z; csum[3] += t.w;
+    }
+}
+
 // Twin staging of one operand, one round of NIMG_W images: T8 8-byte pieces per thread in registers (two of them = one
 // 16-byte piece).  w16 (wave-uniform): 16-byte pieces, piece t = tid + 256 i is row t >> 3, 8 columns from (t & 7) * 8;
 // else 8-byte pieces, row t >> 4, 4 columns from (t & 15) * 4.  A piece outside [K x cols] reads element 0 and is
@@ -608,26 +648,16 @@ __device__ __forceinline__ float tile_bf16_tw(const Prob& pr, int m0, int n0, un
     f32x4 acc[2][2];
     zero_acc(acc);
 
-    uint2 ra[T8], rb[T8];
-    // all operand loads of one round, one wave-uniform branch per operand.  Rounds are software-pipelined: the loads of
-    // round r+1 are issued as soon as round r's registers are in LDS, i.e. under its barrier and MFMAs (K > 192: the
-    // 128x128 configuration contracts over 256 rows)
-    auto issue_round = [&](int kr) __attribute__((always_inline)) {
+    // all operand loads of one round, one wave-uniform branch per operand.  (An interior form of the 16-byte pieces -- one
+    // per-thread offset, rows at uniform steps, no compare or select -- was built and measured: 13.96 -> 13.78 us for the
+    // launch on its own, 12.01 -> 12.08 beside the early bias sums, i.e. nothing: the launch ends with its slowest
+    // workgroup, not with the sum of their instructions.  Removed)
+    auto issue_round = [&](uint2 (&ra)[T8], uint2 (&rb)[T8], int kr) __attribute__((always_inline)) {
         issue_pieces(ra, Ab, a16, kr, m0, K, M, lda);
         issue_pieces(rb, Yb, b16, kr, n0, K, N, ldb);
     };
-    AIR_STAMP(1);
-    issue_round(0);
-    AIR_STAMP(2);
-    for (int kr = 0; kr < K; kr += NIMG * KB) {
-        if (kr > 0) __syncthreads();
-        store_pieces(ra, ImgA, a16);
-        store_pieces(rb, ImgB, b16);
-        AIR_STAMP(3);
-        if (kr + NIMG * KB < K) issue_round(kr + NIMG * KB);
-        __syncthreads();
-        AIR_STAMP(4);
-        // ---- MFMAs: fragments through the transpose read
+    // ---- MFMAs of one round: fragments through the transpose read
+    auto multiply = [&](int kr) __attribute__((always_inline)) {
         const int il = lane & 15;
 #pragma unroll
         for (int c = 0; c < NIMG; ++c)
@@ -645,9 +675,60 @@ __device__ __forceinline__ float tile_bf16_tw(const Prob& pr, int m0, int n0, un
                     mfma_2x2(acc, av, bv);
                 }
             }
+    };
+    float sq = 0.0f;
+    const bool early = bias_block && bias_early(pr);          // (bias_early: one round)
+    AIR_STAMP(1);
+    if (K <= NIMG * KB) {
+        // ONE round (every problem of the 50 x 50 step): a path of its own, with no loop around it.  The owner of a bias
+        // column (whole images, 16-byte rows: bias_early) sends image 0 of the fp32 dY right behind the operand loads,
+        // which are waited for first; sums it as soon as the operands are staged and sends images 1 and 2 into the barrier
+        // and the MFMAs (threads 128..255: bias_tw's roles).  One image beside the operand registers, two beside the
+        // accumulators: with two at entry the kernel no longer fits its 168 registers (20 bytes of scratch).  The images'
+        // registers are live in this path alone.
+        const bool bias_wave = early && tid >= 128;
+        uint2 ra[T8], rb[T8];
+        float4 b0[8], b1[8];
+        float csum[4] = {0.f, 0.f, 0.f, 0.f};
+        issue_round(ra, rb, 0);
+        if (bias_wave) bias_issue(b0, pr, n0, 0);
+        AIR_STAMP(2);
+        store_pieces(ra, ImgA, a16);
+        store_pieces(rb, ImgB, b16);
+        if (bias_wave) {
+            bias_add(csum, b0, pr, n0, 0);
+            if (K > KB) bias_issue(b1, pr, n0, 1);
+            if (K > 2 * KB) bias_issue(b0, pr, n0, 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);                    // (the scheduler would sink the loads below the MFMAs)
+        AIR_STAMP(3);
+        __syncthreads();
+        AIR_STAMP(4);
+        multiply(0);
+        AIR_STAMP(5);
+        if (early) {
+            if (bias_wave) {
+                if (K > KB) bias_add(csum, b1, pr, n0, 1);
+                if (K > 2 * KB) bias_add(csum, b0, pr, n0, 2);
+            }
+            sum_kruns(csum);
+            if (bias_wave && (tid & 7) == 0) sq = store_db(pr.db, csum, n0 + ((tid & 127) >> 3) * 4, N);
+        }
+    } else {
+        // Rounds are software-pipelined: the loads of round r+1 are issued as soon as round r's registers are in LDS, i.e.
+        // under its barrier and MFMAs (K > 192: the 128x128 configuration contracts over 256 rows)
+        uint2 ra[T8], rb[T8];
+        issue_round(ra, rb, 0);
+        for (int kr = 0; kr < K; kr += NIMG * KB) {
+            if (kr > 0) __syncthreads();
+            store_pieces(ra, ImgA, a16);
+            store_pieces(rb, ImgB, b16);
+            if (kr + NIMG * KB < K) issue_round(ra, rb, kr + NIMG * KB);
+            __syncthreads();
+            multiply(kr);
+        }
     }
-    AIR_STAMP(5);
-    const float sq = bias_block ? bias_tw(pr, n0) : 0.0f;
+    if (bias_block && !early) sq = bias_tw(pr, n0);              // (the one call for every other owner: after the MFMAs)
     __syncthreads();
     acc_to_lds(acc, reinterpret_cast<float*>(Img), wm, wn, lane);
     __syncthreads();
@@ -678,7 +759,8 @@ constexpr int STRIP_KMAX = 256;
 #endif
 constexpr int STRIP_LDS = STRIP_KMAX * BT * 2;              // bytes: one [K][64] image (32 KB <= the 48 KB of the one-tile workgroups)
 constexpr int STRIP_MAXG = 16;                               // column tiles per strip workgroup, at most
-constexpr int STRIP_TAIL = (4 + STRIP_MAXG * 16) * 4;       // bytes behind the images: reduction scratch + parked bias squares
+constexpr int STRIP_TAIL = (4 + STRIP_MAXG * 16 + STRIP_MAXG * 4) * 4;   // bytes behind the images: reduction scratch + parked bias
+                                                                         // squares + the tiles' squares per wave
 template <int NPER,     // 16-byte pieces per thread per operand = K / 32 (a template argument: the operand registers must be
                         // statically indexed -- with a run-time count the compiler kept them in scratch memory and waited for
                         // every load on the spot: 12 us to stage the first images)
@@ -699,6 +781,7 @@ __device__ __forceinline__ void run_strip_bf16(const Prob& pr, int m0, int n0, u
     // Bias gradient of the column tiles this block-row owns (owns_bias: at most one of the strip for the big problems),
     // BEFORE the tile loop: the 16 threads that hold a share of its square park it in LDS.
     float* bias_park = sq_red + 4;                            // [strip][16] floats behind the reduction scratch
+    float* tile_park = bias_park + STRIP_MAXG * 16;           // [strip][4 waves]: the tiles' squares (park_sq)
     if (has_bias) {
         for (int j = 0; j < G; ++j) {
             if (!owns_bias(pr, m0, n0 + j * BT)) continue;    // block-uniform
@@ -805,13 +888,19 @@ __device__ __forceinline__ void run_strip_bf16(const Prob& pr, int m0, int n0, u
         STRIP_STAMP(4 + 6 * j);
         const float sq = store_tile(pr, m0, nj, Ct, bias_sq);
         STRIP_STAMP(5 + 6 * j);
-        if (sq_partials) publish_sq(sq, sq_partials, istate, part0 + tj, sq_red);
+        if (sq_partials) park_sq(sq, tile_park + 4 * tj);   // (no barrier: published behind the loop)
         STRIP_STAMP(6 + 6 * j);
         if (j + 1 < G) {
             __syncthreads();                                  // the output tile has left LDS
             stage_b(rb);
         }
         STRIP_STAMP(7 + 6 * j);
+    }
+    // the tiles' global-norm partials, one thread per tile: the waves' parked sums in air_block_sum_256's order, at the
+    // tile's own index
+    if (sq_partials) {
+        __syncthreads();
+        if (tid < G) publish_parked(tile_park + 4 * tid, sq_partials, istate, part0 + tid);
     }
 }
 // K = 64 / 128 / 192 / 256 (strip_of) -> NPER, once
@@ -946,7 +1035,11 @@ __device__ __forceinline__ void run_tile_bf16(const Table& tab, int block, unsig
     AIR_STAMP(6);
     const float sq = store_tile(pr, m0, n0, reinterpret_cast<const float*>(Img), bias_sq);
     AIR_STAMP(7);
-    if (sq_partials) publish_sq(sq, sq_partials, istate, pr.first_part + (block - pr.first_block), sq_red);
+    if (sq_partials) {
+        park_sq(sq, sq_red);                                  // (nothing has touched sq_red yet: no barrier in front)
+        __syncthreads();
+        if (threadIdx.x == 0) publish_parked(sq_red, sq_partials, istate, pr.first_part + (block - pr.first_block));
+    }
     AIR_STAMP(8);
 }
 

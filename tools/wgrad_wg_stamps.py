@@ -1,20 +1,24 @@
 """Per-workgroup timeline of the grouped weight-gradient launch at the bench configuration (debug build with -DAIR_STAMPS
 made on the GPU box): when every workgroup starts and ends, on which CU, and how long the launch's tail is.
-  python tools/wgrad_wg_stamps.py [--stress]"""
+  python tools/wgrad_wg_stamps.py [--stress] [--lib STAMPS_LIBRARY]
+--lib: a library built elsewhere with -DAIR_STAMPS on csrc/air_wgrad.hip at least (nothing is compiled here then)."""
 import ctypes as C, glob, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "tf-attend-infer-repeat_amd")
 sys.path.insert(0, ROOT); sys.path.insert(0, PKG)
-out = "/tmp/libair_hip_stamps.so"
-src = sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip")))
-from concurrent.futures import ThreadPoolExecutor
-flags = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DAIR_STAMPS",
-         "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc")]
-objs = ["/tmp/stamps_%s.o" % os.path.basename(f) for f in src]
-with ThreadPoolExecutor(8) as ex:
-    list(ex.map(lambda fo: subprocess.check_call(flags + ["-c", fo[0], "-o", fo[1]]), zip(src, objs)))
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out])
+if "--lib" in sys.argv:
+    out = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
+else:
+    out = "/tmp/libair_hip_stamps.so"
+    src = sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip")))
+    from concurrent.futures import ThreadPoolExecutor
+    flags = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-DAIR_STAMPS",
+             "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc")]
+    objs = ["/tmp/stamps_%s.o" % os.path.basename(f) for f in src]
+    with ThreadPoolExecutor(8) as ex:
+        list(ex.map(lambda fo: subprocess.check_call(flags + ["-c", fo[0], "-o", fo[1]]), zip(src, objs)))
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out])
 import torch
 from air import _hip as H
 H._LIB = H.load(out)
