@@ -315,6 +315,11 @@ class _Op:
         self.fn(stream)
 
 
+def _enqueue(plan, stream):
+    for op in plan:
+        op(stream)
+
+
 class GeneratedScenes:
     """What AIRModel.generate() / decode() return: device tensors, image-major like the rec_* attributes, all max_steps
     steps (a step is an object of scene b while masks[b, t] == 1: the first num_digits[b] of them).  They are VIEWS of the
@@ -573,9 +578,6 @@ class AIRModel:
         # (air_write_fwd_bwd; same results); False keeps the two launches: the A/B arm within one build
         self._compose_fold = bool(compose_fold)
         self._fold_op = None
-        self._graph_step_ops = []
-        self._graph_xwx = []
-        self._last_xwx_op = None
         self._graph = None
         self._dirty = True
         self._steps_executed = None
@@ -865,6 +867,9 @@ class AIRModel:
 
         def gemm(*args, **kw):
             fwd.append(self._gemm(*args, **kw))
+
+        def xwx(tag, lda=Din, **kw):                # one form of the x.Wx launch (lda: the row stride of the A16 twin given)
+            return self._gemm(xin, Wx, self.xw, B, 4 * R, Din, lda, 4 * R, 4 * R, tag=tag, **kw)
         # hoisted x.W_x (the reference recomputes it every step, :286); split-K slabs
         job = H.StepJob(_ptr(self.sched), self._nsched, _ptr(self.dyn), _ptr(st.istate),
                         _ptr(self.normals), self.normals.numel(), _ptr(self.uniforms), self.uniforms.numel(),
@@ -890,28 +895,25 @@ class AIRModel:
             # Only the bf16-twin kernel of this launch writes the twin, and only it has the twin-operand form (R % 8 == 0, a
             # 16-byte aligned batch, ...: twin_rounds in csrc/air_gemm_bf16.hip).  The library is asked, not second-guessed:
             # the plain descriptor is built first, and the twin is offered only where THAT dispatches to the twin kernel.
-            op0 = self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, tag="xWx+lstm0", **step0)
+            op0 = xwx("xWx+lstm0", **step0)
             # (not with the conv front-end: its output changes with every step of a replay, so no step may read a twin an
             # earlier step left behind -- every x.Wx launch is the fp32-operand one)
             if wx_pan is not None and self.train and not self.cnn and op0.kernel.startswith("gemm_bf16tw_kernel<1, 1, false, %d, true," % H.EPI_LSTM_FWD0):
                 x16p = self.images16p
-                op0 = self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, tag="xWx+lstm0", C16=x16p, **step0)
-                self._xwx_twin_op = self._gemm(xin, Wx, self.xw, B, 4 * R, Din, x16p.shape[1], 4 * R, 4 * R, tag="xWx16+lstm0",
-                                               A16=x16p, i0=(3 if self._xwx_twin_staging == "registers" else 2), **step0)
+                op0 = xwx("xWx+lstm0", C16=x16p, **step0)
+                self._xwx_twin_op = xwx("xWx16+lstm0", lda=x16p.shape[1], A16=x16p,
+                                        i0=(3 if self._xwx_twin_staging == "registers" else 2), **step0)
             fwd.append(op0)
             step0["extra_bytes"] += noise_bytes
-            self._begin_host = (0, self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R,
-                                              tag="xWx+lstm0+step_begin", step_job=job, **step0))
+            self._begin_host = (0, xwx("xWx+lstm0+step_begin", step_job=job, **step0))
         else:
             if st.wx_exclusive:
                 Wx16 = None         # (the row-major shadow of Wx is not maintained on this scope: fp32 operand)
-            fwd.append(self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, ksplit=self._xw_ksplit,
-                                  tile=self._xw_tile, tag="xWx", B16=Wx16))
+            plain = dict(ksplit=self._xw_ksplit, tile=self._xw_tile, B16=Wx16)
+            fwd.append(xwx("xWx", **plain))
             # the same launch carrying the step prologue (schedules + Philox noise) as an extra plane of
             # workgroups: x.Wx reads neither, so the train step needs no prologue launch of its own
-            self._begin_host = (0, self._gemm(xin, Wx, self.xw, B, 4 * R, Din, Din, 4 * R, 4 * R, ksplit=self._xw_ksplit,
-                                              tile=self._xw_tile, tag="xWx+step_begin", step_job=job,
-                                              extra_bytes=noise_bytes, B16=Wx16))
+            self._begin_host = (0, xwx("xWx+step_begin", step_job=job, extra_bytes=noise_bytes, **plain))
             # step 0 starts from zero_state (:540): h_0 . Wh = 0, the gates are x.Wx + b -- a pointwise launch
             fwd.append(self._call("air_lstm_first_step", _ptr(self.xw), self._xw_slabs, _ptr(P["lstm_bias"]),
                                   _ptr(self.acts[0]), _ptr(self.c[1]), _ptr(self.h[1]), _ptr(_row16(self.h16, 1)), B, R,
@@ -1255,35 +1257,65 @@ class AIRModel:
         if self._twins and self.store.shadow_stale:
             self.store.refresh_shadow(self._stream())
 
-    def _fwd_with_prologue(self, fwd=None):
-        """the forward list (self._fwd, or the variant of it given) with the launch that carries the step prologue
-        (schedules + Philox noise, as extra workgroups) in the place of its plain form"""
-        hi, hop = self._begin_host
-        return [(hop if i == hi else op) for i, op in enumerate(self._fwd if fwd is None else fwd)]
-
-    def _run_forward(self, s, finalize=True, twin_x=False, fold=False):
-        """twin_x: x.Wx reads the padded bf16 twin of the image batch.  Only capture_graph may ask for it, and only for a
-        step whose predecessor in the SAME replay ran the fp32-operand launch over the same, untouched batch.
-        fold: without the compose launch, the last of the list -- the backward that follows opens with air_write_fwd_bwd."""
-        self._fresh_shadow()
-        fwd = self._fwd[:-1] if fold else self._fwd
+    # The launch plans decide which built ops make up a forward, a backward, an update -- here and nowhere else.  They hand
+    # out the built _Op objects, enqueue nothing and set nothing: the runners, the public lists and capture_graph read them.
+    def _forward_plan(self, finalize=True, twin_x=False, fold=False, injected=None):
+        """twin_x: x.Wx reads the padded bf16 twin of the image batch (capture_graph knows where an earlier step left it).
+        fold: without the compose launch, the last of the list -- the backward that follows opens with air_write_fwd_bwd.
+        injected (default: set_noise was called): the prologue is a launch of its own, the schedules only (parity tests)."""
+        fwd = list(self._fwd[:-1] if fold else self._fwd)
         if twin_x:
             if self._xwx_twin_op is None:
                 raise RuntimeError("this model has no twin-operand x.Wx launch")
-            fwd = [self._xwx_twin_op] + fwd[1:]
-        if self._cnn_fwd is not None:
-            self._cnn_fwd(s)                         # (first: x.Wx and the prologue's bf16 twin read its output)
-        if self._injected_noise:
-            self._begin_sched_only(s)                # (parity tests: the schedules only, the noise buffers hold what was injected)
-            run = list(fwd)
+            fwd[0] = self._xwx_twin_op
+        head = [self._cnn_fwd] if self._cnn_fwd is not None else []   # (first: x.Wx and the prologue's bf16 twin read its output)
+        if self._injected_noise if injected is None else injected:
+            head.append(self._begin_sched_only)
         else:
-            run = self._fwd_with_prologue(fwd)
-        self._last_xwx_op = run[0]                   # (what capture_graph records: the op that WAS enqueued)
-        for op in run:
-            op(s)
-        if finalize:
-            self._finalize(s)
-        self._last_fwd_run = ([self._cnn_fwd] if self._cnn_fwd is not None else []) + run
+            hi, hop = self._begin_host               # the launch that carries the prologue (schedules + Philox noise, as extra
+            fwd[hi] = hop                            # workgroups) in the place of its plain form
+        return head + fwd + ([self._finalize] if finalize else [])
+
+    def _xwx_of(self, plan):
+        """the x.Wx launch of a forward plan: the first behind the conv front-end and the schedules-only prologue"""
+        i = int(self._cnn_fwd is not None)
+        return plan[i + (plan[i] is self._begin_sched_only)]
+
+    def _backward_plan(self, for_update=False, fused_finalize=False, fold=False, dp=None):
+        """for_update: this backward is followed by the optimizer of a train step -- on a single GPU the weight-gradient
+        launch then also publishes the global-norm partials and counts the step.  dp: self._dp() unless given.
+        fold: the forward before it ran without its compose launch (_forward_plan): air_write_fwd_bwd opens the list."""
+        first = self._fold_op if fold else (self._write_bwd_fin if fused_finalize else self._bwd[0])
+        # (tried: the VAE weight gradients as their own launch on a side stream beside attend_bwd ->
+        # dh_heads -> BPTT.  The big launch takes the CUs the latency-critical chain needs: 217 -> 257 us.)
+        if for_update and not (self._dp() if dp is None else dp):
+            tail = [self._wgrad_fused]
+        elif for_update and self._dp_exchange == "factors":
+            tail = [self._dp_factors()[k] for k in ("local", "bias")]
+        else:
+            tail = [self._wgrad_plain]
+        return [first] + self._bwd[1:] + tail
+
+    def _update_plan(self, dp=None):
+        """global-norm clip + TF-style Adam + global_step += 1 (after the all-reduce); with the factor exchange
+        dWx from the gathered factors first, identically on every rank"""
+        factors = (self._dp() if dp is None else dp) and self._dp_exchange == "factors"
+        return ([self._dp_factors()["dwx"]] if factors else []) + list(self._optimizer_ops())
+
+    def forward_ops(self):
+        """The launches of one uncaptured forward(), in order (profiling tools): the forward side of train_step_ops()."""
+        return self._forward_plan()
+
+    def train_step_ops(self):
+        """The launches of one single-GPU train step on device noise, in order (bench / profiling tools): the EAGER step, whose
+        x.Wx reads the caller's fp32 image batch.  Steps 1 .. G-1 of a captured G-step replay without a between_steps hook run
+        the same list with the twin-operand x.Wx launch (gemm_xwx_glds_kernel, captured_xwx_kernels()) in its first place."""
+        return self._forward_plan(finalize=False, twin_x=False, fold=False, injected=False) + \
+            self._backward_plan(for_update=True, fused_finalize=True, fold=False, dp=False) + self._update_plan(dp=False)
+
+    def _run_forward(self, s, finalize=True, twin_x=False, fold=False):
+        self._fresh_shadow()
+        _enqueue(self._forward_plan(finalize, twin_x, fold), s)
 
     def forward(self):
         """Evaluates the model on the current contents of the input buffers."""
@@ -1396,30 +1428,7 @@ class AIRModel:
         dist.all_reduce(f["tail"])                               # everything but dWx (+ loss / accuracy)
 
     def _run_backward(self, s, for_update=False, fused_finalize=False, fold=False):
-        """for_update: this backward is followed by the optimizer of a single-GPU train step -- the
-        weight-gradient launch then also publishes the global-norm partials and counts the step.
-        fold: the forward before it ran without its compose launch (_run_forward): air_write_fwd_bwd opens the list."""
-        first = self._fold_op if fold else (self._write_bwd_fin if fused_finalize else self._bwd[0])
-        # (tried: the VAE weight gradients as their own launch on a side stream beside attend_bwd ->
-        # dh_heads -> BPTT.  The big launch takes the CUs the latency-critical chain needs: 217 -> 257 us.)
-        if for_update and not self._dp():
-            tail = [self._wgrad_fused]
-        elif for_update and self._dp_exchange == "factors":
-            f = self._dp_factors()
-            tail = [f["local"], f["bias"]]
-        else:
-            tail = [self._wgrad_plain]
-        run = [first] + self._bwd[1:] + tail
-        for op in run:
-            op(s)
-        self._last_bwd_run = run
-
-    def train_step_ops(self):
-        """The launches of one single-GPU train step, in order (bench / profiling tools): the EAGER step, whose x.Wx reads
-        the caller's fp32 image batch.  Steps 1 .. G-1 of a captured G-step replay without a between_steps hook run the same
-        list with the twin-operand x.Wx launch (gemm_xwx_glds_kernel, captured_xwx_kernels()) in its first place."""
-        return ([self._cnn_fwd] if self._cnn_fwd is not None else []) + self._fwd_with_prologue() + [self._write_bwd_fin] + \
-            self._bwd[1:] + [self._wgrad_fused] + self._optimizer_ops()
+        _enqueue(self._backward_plan(for_update, fused_finalize, fold), s)
 
     def captured_xwx_kernels(self):
         """Kernel name of the x.Wx launch of every step of the captured replay, in order (None: no train graph): the names
@@ -1428,15 +1437,16 @@ class AIRModel:
         return None if ops is None else [op.kernel for op in ops]
 
     def captured_xwx_ops(self):
-        return None if self._graph is None or not self.train else list(self._graph_xwx)
+        return None if self._graph is None or not self.train else [xwx for xwx, _ in self._graph_record]
 
     def captured_step_ops(self, step=0):
-        """The launches of train step `step` of the captured replay, in order (None: no train graph): the ops that were
+        """The launches of train step `step` of the captured replay, in order (None: no train graph): the plan that was
         enqueued under capture.  Where the library has the form, compose and the write backward are ONE of them
         (air_write_fwd_bwd: compose_fold), so the list is one shorter than train_step_ops(), the eager step.
+        After set_noise that includes the schedules-only prologue launch (air_step_begin): always captured then, not listed before.
         Data parallel over a backend whose collectives cannot be captured: the ops of the FIRST graph, prologue to weight
         gradients -- the optimizer is replayed from a graph of its own after the exchange and is not listed."""
-        return None if self._graph is None or not self.train else list(self._graph_step_ops[step])
+        return None if self._graph is None or not self.train else list(self._graph_record[step][1])
 
     def _train_phase_a(self, s, twin_x=False, fold=False):
         """step prologue + forward + loss + backward (+ weight grads) into the flat grad buffer"""
@@ -1444,11 +1454,17 @@ class AIRModel:
         self._run_backward(s, for_update=True, fused_finalize=True, fold=fold)
 
     def _train_phase_b(self, s):
-        """global-norm clip + TF-style Adam + global_step += 1 (after the all-reduce)"""
-        if self._dp() and self._dp_exchange == "factors":
-            self._dp_factors()["dwx"](s)                         # dWx from the gathered factors, identically on every rank
-        for op in self._optimizer_ops():
-            op(s)
+        _enqueue(self._update_plan(), s)
+
+    def _warm_up(self, run):
+        """run() on a side stream before a capture: lazy module loads, LDS attributes, communicators -- never under capture"""
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            run()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
 
     def capture_graph(self, steps=1, between_steps=None, after_steps=None):
         """Captures the train step into hipGraphs (fixed N, no host sync, no allocation inside).
@@ -1464,7 +1480,6 @@ class AIRModel:
             return self._capture_forward_graph()
         self._capture_args = dict(steps=steps, between_steps=between_steps, after_steps=after_steps)
         self._follow_schedule(recapture=False)        # (this call is the capture)
-        self._optimizer_ops()
         world = self._world()
         if self.store.synced_world != world:
             self.sync_parameters()
@@ -1475,23 +1490,18 @@ class AIRModel:
             raise ValueError("multi-step graphs need world_size 1 or a backend whose collectives can be captured (nccl)")
         self._graph_steps = steps
         factors = dp and self._dp_exchange == "factors"
-        if factors:
-            self._dp_factors()                   # buffers + launch lists exist before anything is captured
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):            # warm-up outside capture (lazy module loads, LDS attributes, communicators)
+        self._update_plan()                      # (the lazily built ops and buffers exist before anything is captured)
+
+        def warm():
             s = self._stream()
-            self._run_forward(s)
-            self._run_backward(s, for_update=factors)
+            _enqueue(self._forward_plan() + self._backward_plan(for_update=factors), s)
             if dp:
                 self._dp_exchange_gradients()    # also the first collective of the communicator: never under capture
                 if factors:
                     self._dp_factors()["dwx"](s)
             if self._fold_op is not None:
                 self._fold_op(s)                 # (its LDS grant, like every launch's, is a driver call: never under capture)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        self._warm_up(warm)
         # Step 0 of a replay reads the caller's fp32 image batch (the host may have rewritten it since the last replay) and
         # leaves its padded bf16 twin behind; nothing inside the graph writes the batch unless a between_steps hook does, so
         # the steps behind it read the twin: half the A bytes of x.Wx, both operands by LDS-DMA.  (Not where the x.Wx launch
@@ -1502,7 +1512,7 @@ class AIRModel:
         # Every captured step runs compose inside the write-backward launch where the library has that form for this model
         # (air_write_fwd_bwd: one launch fewer, same results) -- with or without hooks: nothing it reads can be stale.
         fold = self._fold_op is not None
-        xwx, step_ops = [], []
+        record = []                              # per step: (its x.Wx op, the plan that was enqueued)
         ga = torch.cuda.CUDAGraph()
         # (thread_local: RCCL's watchdog thread may touch the runtime while this thread captures)
         with torch.cuda.graph(ga, **({"capture_error_mode": "thread_local"} if dp else {})):
@@ -1510,18 +1520,16 @@ class AIRModel:
                 if between_steps is not None:
                     between_steps(i)
                 s = self._stream()
-                twin_x = i >= 1 and can_twin
-                self._train_phase_a(s, twin_x=twin_x, fold=fold)
-                xwx.append(self._last_xwx_op)
+                fwd = self._forward_plan(finalize=False, twin_x=i >= 1 and can_twin, fold=fold)
+                bwd = self._backward_plan(for_update=True, fused_finalize=True, fold=fold)
                 # (a backend whose collectives cannot be captured: the optimizer is recorded into the second graph, below)
-                step_ops.append(self._last_fwd_run + self._last_bwd_run +
-                                ([] if (dp and not in_graph) else
-                                 ([self._dp_factors()["dwx"]] if factors else []) + list(self._optimizer_ops())))
-                if not dp:
-                    self._train_phase_b(s)
-                elif in_graph:
+                update = [] if (dp and not in_graph) else self._update_plan()
+                _enqueue(fwd + bwd, s)
+                if dp and in_graph:
                     self._dp_exchange_gradients()
-                    self._train_phase_b(self._stream())
+                    s = self._stream()
+                _enqueue(update, s)
+                record.append((self._xwx_of(fwd), fwd + bwd + update))
             if after_steps is not None:
                 after_steps()
             if dp and in_graph and world > 1:
@@ -1532,8 +1540,7 @@ class AIRModel:
             with torch.cuda.graph(gb):
                 self._train_phase_b(self._stream())
         self._graph = (ga, gb)
-        self._graph_xwx = xwx
-        self._graph_step_ops = step_ops
+        self._graph_record = record
         self._graph_dp = (dp, in_graph)
         return self
 
@@ -1542,13 +1549,7 @@ class AIRModel:
         forward -- schedules + noise, hoisted x.Wx, N x (LSTM, heads, read, VAE), compose, batch means --
         as ONE hipGraph; forward() then is a single replay."""
         self._fresh_shadow()
-        torch.cuda.synchronize()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):            # warm-up outside capture (lazy module loads, LDS attributes)
-            self._run_forward(self._stream())
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
+        self._warm_up(lambda: self._run_forward(self._stream()))
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self._run_forward(self._stream())
@@ -1565,7 +1566,6 @@ class AIRModel:
         runs exactly one step through plain launches even then."""
         if not self.train:
             raise RuntimeError("model was built with train=False")
-        st = self.store
         world = self._world()
         if self.store.synced_world != world:
             self.sync_parameters()
@@ -1595,7 +1595,7 @@ class AIRModel:
         if not self._twins:
             # this model's Adam launch does not maintain the bf16 shadow of the (shared) variables: whoever reads it
             # next -- e.g. a reuse=True model with bf16 twins on the same scope -- has to re-derive it first
-            st.shadow_stale = True
+            self.store.shadow_stale = True
         self._dirty = False
         self._steps_executed = None
 
@@ -1669,8 +1669,7 @@ class AIRModel:
         self._fresh_shadow()
         s = self._stream()
         fill = needs_noise and not self._gen_injected
-        for op in self.generate_ops(likelihood_noise, given, fill):
-            op(s)
+        _enqueue(self.generate_ops(likelihood_noise, given, fill), s)
         if fill:
             self._gen_calls += 1
         self._gen_injected = False

@@ -35,9 +35,7 @@ def timed(fn, n=50):
 print("precision %s, %d test canvases" % (prec, B))
 print("eager forward: %.1f us" % timed(te.forward))
 s = te._stream()
-hi, hop = te._begin_host
-ops = [(hop if i == hi else op) for i, op in enumerate(te._fwd)] + [te._finalize]
-for op in ops:
+for op in te.forward_ops():
     print("   %8.1f us  %-40s %s" % (timed(lambda: op(s), 30), op.name, op.kernel))
 te.capture_graph()
 print("replayed forward: %.1f us" % timed(te.forward))

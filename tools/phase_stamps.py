@@ -35,7 +35,7 @@ for _ in range(3):
 torch.cuda.synchronize()
 s = m._stream()
 names = sys.argv[1:] or ["write_bwd", "compose", "attend_fwd", "attend_bwd"]
-ops = [m._begin] + m._fwd + m._bwd + [m._wgrad_fused]
+ops = m.train_step_ops()
 for want in names:
     for op in ops:
         if want in op.name and not getattr(op, "_seen_%s" % want, False):
