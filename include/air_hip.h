@@ -414,6 +414,15 @@ int air_reparam_bwd(const float* d_zs, const float* ml, const float* eps_z, cons
  * reconstruction loss and its gradient.  air_model.py:351-366 (theta_recon,
  * transformer), :409-439 (masks, running_recon), :479-496 (VAE KL), :580-593 (loss).
  * One workgroup per image. */
+/* the pixel likelihood of the reconstruction loss (air_write_fwd_t.likelihood; additive to ABI 6).  With R the running
+ * reconstruction of a pixel, r = min(max(R, 0), 1) the reported reconstruction, x the image pixel, gsc = dyn[AIR_DYN_GRAD_SCALE]
+ * and pass = (R <= 1 && min(R, 1) >= 0) (Minimum / Maximum pass their gradient at ties):
+ *   AIR_LIK_BERNOULLI  the reference's cross-entropy :586-589:  rec_loss = -sum_p x log(r + 1e-9) + (1 - x) log(1 - r + 1e-9),
+ *                      d_recon = pass ? -gsc * (x / (r + 1e-9) - (1 - x) / (1 - r + 1e-9)) : 0
+ *   AIR_LIK_GAUSSIAN   the AIR paper's Gaussian with mean r and fixed sigma = dyn[AIR_DYN_LIK_STD] (> 0; read on the device):
+ *                      rec_loss = (0.5 / sigma^2) * sum_p (x - r)^2 + C * C * (log sigma + 0.5 log 2 pi)   -- a density: may be < 0;
+ *                      d_recon = pass ? gsc * (r - x) / sigma^2 : 0, so |d_recon| <= gsc / sigma^2 on every canvas */
+enum { AIR_LIK_BERNOULLI = 0, AIR_LIK_GAUSSIAN = 1 };
 typedef struct {
     const float* vrec;                   /* vae reconstructions [N,B,w*w]   */
     const float* ml;                     /* [N,B,2Z] mean | log_var         */
@@ -431,6 +440,8 @@ typedef struct {
      * graph-order write backward will have with them (its corner terms; inactive items last) and leaves the permutation
      * here -- air_write_bwd_t.order.  Worth it when there are more items than CUs (128 x 128, b = 256: 1280 items). */
     int32_t* wb_order;
+    int32_t likelihood;                  /* AIR_LIK_*; 0 (a zero-filled field) is the Bernoulli path, AIR_LIK_GAUSSIAN launches
+                                            write_fwd_gauss_kernel; any other value: AIR_EINVAL */
 } air_write_fwd_t;
 int air_write_fwd(const air_write_fwd_t* a, void* stream);
 
@@ -476,7 +487,8 @@ int air_write_bwd_kernel_name(const air_write_bwd_t* a, char* buf, int n);
  * one train step: b->d_recon / vrec / att / fin_loss_item / fin_digits are f's d_recon / vrec / att / loss_item /
  * run_digits, equal B, N, C, w, f->d_recon and all four b->fin_* given (AIR_EINVAL otherwise, and for b->literal != 2).
  * The form exists where all four taps' terms of the write backward are resident in LDS, compose's scratch fits over
- * them, and N * B <= 256 without f->wb_order / b->order: AIR_ELIMIT otherwise -- the caller keeps its two launches.
+ * them, N * B <= 256 without f->wb_order / b->order, and f->likelihood == AIR_LIK_BERNOULLI (the fold has not been taught
+ * another likelihood): AIR_ELIMIT otherwise -- the caller keeps its two launches.
  * N * B <= 256 is an ASSUMPTION about placement, not a guarantee: the hand-off of the batch means uses agent-scope
  * relaxed stores and loads in place of a release / acquire pair, a form measured with one workgroup per CU on a 256-CU
  * part.  The launch asks for under half a CU's LDS, so on a part with fewer CUs, or beside another stream's work, two of
@@ -533,6 +545,10 @@ int air_vae_bottleneck_bwd(const air_bottleneck_bwd_t* a, void* stream);
 int air_bce_fwd_bwd(const float* images, const float* run_recon, const float* dyn,
                     float* recon /*clipped [B,D]*/, float* rec_loss /*[B]*/,
                     float* d_recon /*[B,D] nullable*/, int B, int D, void* stream);
+/* its twin under AIR_LIK_GAUSSIAN (the formulas above air_write_fwd_t; sigma = dyn[AIR_DYN_LIK_STD]); additive to ABI 6 */
+int air_gauss_nll_fwd_bwd(const float* images, const float* run_recon, const float* dyn,
+                          float* recon /*clipped [B,D]*/, float* rec_loss /*[B]*/,
+                          float* d_recon /*[B,D] nullable*/, int B, int D, void* stream);
 /* loss = mean(run_loss + rec_loss), accuracy = mean(target == digits)  (:597-611)
  * scalars[0] = loss, scalars[1] = accuracy */
 int air_finalize(const float* run_loss, const float* rec_loss, const int32_t* targets,

@@ -31,6 +31,7 @@ ACT_NONE, ACT_RELU, ACT_SOFTPLUS, ACT_SIGMOID_NOISE = 0, 1, 2, 3
 GRAD_NONE, GRAD_RELU, GRAD_SOFTPLUS = 0, 1, 2
 EPI_GENERIC, EPI_LSTM_FWD, EPI_REPARAM_FWD, EPI_LSTM_BWD, EPI_REPARAM_BWD, EPI_LSTM_BWD_TAIL, EPI_LSTM_FWD0 = 0, 1, 2, 3, 4, 5, 6
 SCHED_STAIRCASE, SCHED_HAS_MIN, SCHED_HAS_MAX, SCHED_LOG = 1, 2, 4, 8
+LIK_BERNOULLI, LIK_GAUSSIAN = 0, 1
 
 _p = C.c_void_p
 _i = C.c_int32
@@ -98,7 +99,7 @@ class AttendBwd(C.Structure):
 class WriteFwd(C.Structure):
     _fields_ = [("vrec", _p), ("ml", _p), ("images", _p), ("dyn", _p), ("att", _p), ("recon", _p),
                 ("rec_loss", _p), ("d_recon", _p), ("run_loss", _p), ("run_digits", _p), ("loss_item", _p),
-                ("B", _i), ("N", _i), ("C", _i), ("w", _i), ("Z", _i), ("wb_order", _p)]
+                ("B", _i), ("N", _i), ("C", _i), ("w", _i), ("Z", _i), ("wb_order", _p), ("likelihood", _i)]
 
 
 class WriteBwd(C.Structure):
@@ -250,6 +251,7 @@ _SIGNATURES = {
     "air_write_fwd": (C.c_int, [C.POINTER(WriteFwd), _p]),
     "air_write_bwd": (C.c_int, [C.POINTER(WriteBwd), _p]),
     "air_bce_fwd_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, _p]),
+    "air_gauss_nll_fwd_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, C.c_int, _p]),
     "air_finalize": (C.c_int, [_p, _p, _p, _p, _p, _p, C.c_int, _p]),
     "air_step_begin": (C.c_int, [_p, C.c_int, _p, _p, _p, C.c_int64, _p, C.c_int64, C.c_uint64, _p, _p, C.c_int64, _p]),
     "air_optim_num_partials": (C.c_int, [C.c_int64]),

@@ -413,7 +413,7 @@ class AIRModel:
                  num_summary_images=60, train=False, reuse=False, scope="air",
                  annealing_schedules=None, seed=0, gemm_precision=None, backward="reference", noise_seed=None,
                  bf16_twins=None, dp_exchange=None, xw_tile=None, xwx_twin_staging="lds_dma", step0_fusion=None,
-                 compose_fold=True):
+                 compose_fold=True, likelihood="bernoulli"):
         if cnn is None:
             # The reference's default is cnn=True (:21) and every caller of the reference passes cnn=False.  A call that leaves
             # `cnn` out has always been refused here, and still is: which LSTM input a model has (and with it the layout of
@@ -438,6 +438,15 @@ class AIRModel:
         for name, val, cap, why in limits:
             if val > cap:
                 raise NotImplementedError("%s = %d exceeds the HIP path's limit of %d (%s)" % (name, val, cap, why))
+        # the pixel likelihood of the reconstruction loss (air_write_fwd_t.likelihood, include/air_hip.h): "bernoulli", the
+        # reference's cross-entropy on the clipped canvas (:586-589), or "gaussian", the AIR paper's Gaussian around the
+        # clipped canvas with the fixed standard deviation vae_likelihood_std.  A per-model argument, not part of the
+        # variable scope's shapes: it owns no variable, so a checkpoint of either kind loads into either.
+        if likelihood not in self._LIKELIHOODS:
+            raise ValueError("likelihood must be one of %s" % sorted(self._LIKELIHOODS))
+        if likelihood == "gaussian" and not float(vae_likelihood_std) > 0.0:
+            raise ValueError("likelihood='gaussian' needs vae_likelihood_std > 0, got %r" % (vae_likelihood_std,))
+        self.likelihood = likelihood
         cnn = bool(cnn)
         if cnn:
             # the conv front-end (reference :510-533): the limits of its kernels, as the library answers them
@@ -789,6 +798,8 @@ class AIRModel:
             kernel = "wgrad_grouped_bf16_kernel" if self._prec else "wgrad_grouped_kernel"
         if name in ("air_cnn_fwd", "air_cnn_bwd_sq"):        # (the backward's second launch is cnn_reduce_sq_kernel)
             kernel = "cnn_%s_kernel<%d>" % (name[8:11], self.cnn_filters)
+        if name == "air_write_fwd" and self.likelihood == "gaussian":      # a __global__ of its own over write_fwd_kernel's body
+            kernel = "write_fwd_gauss_kernel<1024>"
         return _Op(tag or name, lambda s, fn=fn, args=args, name=name: H.check(fn(*args, s), name),
                    nbytes=nbytes, flops=flops, kernel=kernel)
 
@@ -982,7 +993,8 @@ class AIRModel:
                           if (self.train and self._literal >= 2 and 256 < NB <= 4096) else None)
         wf = H.WriteFwd(_ptr(self.vrec), _ptr(self.ml), _ptr(imgs), _ptr(self.dyn), _ptr(self.att),
                         _ptr(self._recon), _ptr(self._rec_loss), _ptr(self.d_recon if self.train else None),
-                        _ptr(self.run_loss), _ptr(self.run_digits), _ptr(self._loss_item), B, N, Cc, w, Z, _ptr(self._wb_order))
+                        _ptr(self.run_loss), _ptr(self.run_digits), _ptr(self._loss_item), B, N, Cc, w, Z, _ptr(self._wb_order),
+                        self._LIKELIHOODS[self.likelihood])
         keep.append(wf)
         self._write_fwd_desc = wf
         fwd.append(self._call("air_write_fwd", C.byref(wf),
@@ -1189,6 +1201,7 @@ class AIRModel:
         self._dirty = True
 
     _ORDERS = {"reference_carried": 4, "reference": 2, "exact": 0}      # air_write_bwd_t.literal
+    _LIKELIHOODS = {"bernoulli": H.LIK_BERNOULLI, "gaussian": H.LIK_GAUSSIAN}      # air_write_fwd_t.likelihood
 
     def set_backward(self, backward):
         """Switches the sampler-backward order of a built train model (AIRModel(backward=...)): the launch lists are rebuilt,

@@ -63,6 +63,24 @@ __device__ __forceinline__ float air_softplus(float x) {
     return logf(expf(x) + 1.0f);
 }
 
+// Gaussian pixel likelihood with mean r = clip(R, 0, 1) and fixed sigma = dyn[AIR_DYN_LIK_STD] (AIR_LIK_GAUSSIAN,
+// include/air_hip.h above air_write_fwd_t): ONE definition for compose (air_sampler_common.h) and the un-fused op
+// (air_gauss_nll_fwd_bwd).  A thread sums air_gauss_term over its pixels; air_gauss_image_loss finishes the image's sum.
+struct AirGaussLik { float sigma, var; };
+__device__ __forceinline__ AirGaussLik air_gauss_lik(const float* __restrict__ dyn) {
+    const float s = dyn[AIR_DYN_LIK_STD];
+    return AirGaussLik{s, s * s};
+}
+__device__ __forceinline__ float air_gauss_term(float x, float r) { const float d = x - r; return d * d; }
+// d loss / d running_recon of one pixel: the clip's gate is the Bernoulli path's (ties pass)
+__device__ __forceinline__ float air_gauss_dloss(float R, float r, float x, float gsc, const AirGaussLik& g) {
+    const bool pass = (R <= 1.0f) && (fminf(R, 1.0f) >= 0.0f);
+    return pass ? (gsc * (r - x)) / g.var : 0.0f;
+}
+__device__ __forceinline__ float air_gauss_image_loss(float sum_sq, int D, const AirGaussLik& g) {
+    return (0.5f / g.var) * sum_sq + (float)D * (logf(g.sigma) + 0.91893853320467274f);   // + D * (log sigma + 0.5 log 2 pi)
+}
+
 // two fp32 -> packed bf16 pair / one value, round to nearest even (v_cvt_pk_bf16_f32): the rounding every
 // bf16-operand kernel applies, so a twin written by a producer is what its consumer would have made itself
 typedef __bf16 air_bf16x2_t __attribute__((ext_vector_type(2)));

@@ -180,6 +180,28 @@ __global__ __launch_bounds__(THREADS) void bce_kernel(
     if (threadIdx.x == 0) rec_loss[b] = -acc;
 }
 
+// bce_kernel's twin under the Gaussian pixel likelihood (AIR_LIK_GAUSSIAN; the per-pixel code: air_common.h)
+__global__ __launch_bounds__(THREADS) void gauss_nll_kernel(
+    const float* __restrict__ images, const float* __restrict__ R, const float* __restrict__ dyn,
+    float* __restrict__ recon, float* __restrict__ rec_loss, float* __restrict__ dR, int B, int D)
+{
+    __shared__ float red[4];
+    const int b = blockIdx.x;
+    const float gsc = dyn[AIR_DYN_GRAD_SCALE];
+    const AirGaussLik g = air_gauss_lik(dyn);
+    const size_t base = (size_t)b * D;
+    float acc = 0.0f;
+    for (int k = threadIdx.x; k < D; k += THREADS) {
+        const float x = images[base + k], rr = R[base + k];
+        const float r = fmaxf(fminf(rr, 1.0f), 0.0f);                   // clipped_rec :582
+        acc += air_gauss_term(x, r);
+        recon[base + k] = r;
+        if (dR) dR[base + k] = air_gauss_dloss(rr, r, x, gsc, g);
+    }
+    acc = air_block_sum_256(acc, red);
+    if (threadIdx.x == 0) rec_loss[b] = air_gauss_image_loss(acc, D, g);
+}
+
 // loss = mean(L + rec_loss) :593,610; accuracy = mean(target == digits) :597-611
 __global__ __launch_bounds__(THREADS) void finalize_kernel(
     const float* __restrict__ L, const float* __restrict__ rec_loss, const int32_t* __restrict__ targets,
@@ -344,6 +366,15 @@ extern "C" int air_bce_fwd_bwd(const float* images, const float* run_recon, cons
                                float* recon, float* rec_loss, float* d_recon, int B, int D, void* stream) {
     if (!images || !run_recon || !dyn || !recon || !rec_loss || B <= 0 || D <= 0) return AIR_EINVAL;
     hipLaunchKernelGGL(bce_kernel, dim3(B), dim3(THREADS), 0, air_stream(stream),
+                       images, run_recon, dyn, recon, rec_loss, d_recon, B, D);
+    AIR_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int air_gauss_nll_fwd_bwd(const float* images, const float* run_recon, const float* dyn,
+                                     float* recon, float* rec_loss, float* d_recon, int B, int D, void* stream) {
+    if (!images || !run_recon || !dyn || !recon || !rec_loss || B <= 0 || D <= 0) return AIR_EINVAL;
+    hipLaunchKernelGGL(gauss_nll_kernel, dim3(B), dim3(THREADS), 0, air_stream(stream),
                        images, run_recon, dyn, recon, rec_loss, d_recon, B, D);
     AIR_CHECK_LAUNCH();
     return 0;

@@ -510,14 +510,10 @@ __device__ __forceinline__ void wb_order_block(const air_write_fwd_t& a, unsigne
         if (cls[r] >= 0) a.wb_order[basep[cls[r]] + pos[r]] = tid + r * nthreads;
 }
 
-template <int NT>
-__global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
+// the body of the compose launch; LIK: the pixel likelihood (AIR_LIK_*), one __global__ per value below
+template <int NT, int LIK>
+__device__ __forceinline__ void write_fwd_body(const air_write_fwd_t& a, float* smem)
 {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (a.wb_order && (int)blockIdx.x == a.B) {                  // the one extra workgroup of the launch (block-uniform)
-        wb_order_block(a, reinterpret_cast<unsigned*>(smem));
-        return;
-    }
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = a.C, w = a.w, N = a.N, B = a.B;
     const ComposeLds L = compose_lds(smem, N, C, w);
@@ -539,15 +535,39 @@ __global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
         a.run_digits[b] = digits;
     }
 
-    // phase B -- canvas + Bernoulli cross-entropy, pixel by pixel
-    float acc = compose_pixels<1, false>(L, a.images, base, xs, xpre, N, C, w, a.dyn[AIR_DYN_GRAD_SCALE], tid, true,
-                                         a.recon, a.d_recon, nullptr);
+    // phase B -- canvas + pixel likelihood (the Bernoulli cross-entropy, or the Gaussian's squared errors), pixel by pixel
+    AirGaussLik glik = {};
+    if (LIK == AIR_LIK_GAUSSIAN) glik = air_gauss_lik(a.dyn);
+    float acc = compose_pixels<1, false, LIK>(L, a.images, base, xs, xpre, N, C, w, a.dyn[AIR_DYN_GRAD_SCALE], tid, true,
+                                              a.recon, a.d_recon, nullptr, glik);
     acc = air_block_sum_n<NT / 64>(acc, L.red);
     if (tid == 0) {
-        const float rl = -acc;
+        const float rl = PixelLik<LIK>::image_loss(acc, C * C, glik);
         a.rec_loss[b] = rl;
         a.loss_item[b] = Lkeep + rl;                                // loss += reconstruction_loss :593
     }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void write_fwd_kernel(air_write_fwd_t a)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (a.wb_order && (int)blockIdx.x == a.B) {                  // the one extra workgroup of the launch (block-uniform)
+        wb_order_block(a, reinterpret_cast<unsigned*>(smem));
+        return;
+    }
+    write_fwd_body<NT, AIR_LIK_BERNOULLI>(a, smem);
+}
+// the same launch under AIR_LIK_GAUSSIAN (air_write_fwd_t.likelihood)
+template <int NT>
+__global__ __launch_bounds__(NT) void write_fwd_gauss_kernel(air_write_fwd_t a)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (a.wb_order && (int)blockIdx.x == a.B) {                  // the one extra workgroup of the launch (block-uniform)
+        wb_order_block(a, reinterpret_cast<unsigned*>(smem));
+        return;
+    }
+    write_fwd_body<NT, AIR_LIK_GAUSSIAN>(a, smem);
 }
 
 // a row of wout holds the hidden segment of its unit's head: the stride must cover the widest head
@@ -615,6 +635,7 @@ extern "C" int air_write_fwd(const air_write_fwd_t* a, void* stream) {
         !a->run_loss || !a->run_digits || !a->loss_item)
         return AIR_EINVAL;
     if (a->B <= 0 || a->N <= 0 || a->C < 2 || a->w < 2 || a->Z <= 0) return AIR_EINVAL;
+    if (a->likelihood != AIR_LIK_BERNOULLI && a->likelihood != AIR_LIK_GAUSSIAN) return AIR_EINVAL;
     if (a->N > MAX_STEPS) return AIR_ELIMIT;
     size_t lds = write_smem(a->N, a->C, a->w);
     const unsigned extra = a->wb_order ? 1u : 0u;                 // + the workgroup that sorts the backward's items
@@ -622,7 +643,11 @@ extern "C" int air_write_fwd(const air_write_fwd_t* a, void* stream) {
         if ((long)a->N * a->B > WB_ORDER_MAX) return AIR_ELIMIT;
         if (lds < WB_ORDER_MAX * sizeof(unsigned)) lds = WB_ORDER_MAX * sizeof(unsigned);
     }
-    {
+    if (a->likelihood == AIR_LIK_GAUSSIAN) {
+        int rc = ensure_lds(write_fwd_gauss_kernel<CF_THREADS>, lds);
+        if (rc) return rc;
+        hipLaunchKernelGGL((write_fwd_gauss_kernel<CF_THREADS>), dim3(a->B + extra), dim3(CF_THREADS), lds, air_stream(stream), *a);
+    } else {
         int rc = ensure_lds(write_fwd_kernel<CF_THREADS>, lds);
         if (rc) return rc;
         hipLaunchKernelGGL((write_fwd_kernel<CF_THREADS>), dim3(a->B + extra), dim3(CF_THREADS), lds, air_stream(stream), *a);

@@ -174,6 +174,24 @@ __device__ __forceinline__ float compose_dloss(float R, float x, float p1, float
     const bool pass = (R <= 1.0f) && (fminf(R, 1.0f) >= 0.0f);      // Minimum/Maximum grads pass at ties
     return pass ? -gsc * (x / p1 - (1.0f - x) / p0) : 0.0f;
 }
+// The pixel likelihood of compose, a COMPILE-TIME choice (AIR_LIK_*: the Bernoulli instantiations are the code they were
+// before there was a choice): the thread's term of one pixel, d loss / d running_recon of it, and the image's
+// reconstruction loss from the block sum of the terms over its D pixels.  g: air_gauss_lik(dyn), unused by Bernoulli.
+template <int LIK> struct PixelLik;
+template <> struct PixelLik<AIR_LIK_BERNOULLI> {
+    static __device__ __forceinline__ float term(float x, float, float p1, float p0) { return x * logf(p1) + (1.0f - x) * logf(p0); }   // :586-589
+    static __device__ __forceinline__ float dloss(float R, float, float x, float p1, float p0, float gsc, const AirGaussLik&) {
+        return compose_dloss(R, x, p1, p0, gsc);
+    }
+    static __device__ __forceinline__ float image_loss(float acc, int, const AirGaussLik&) { return -acc; }
+};
+template <> struct PixelLik<AIR_LIK_GAUSSIAN> {
+    static __device__ __forceinline__ float term(float x, float r, float, float) { return air_gauss_term(x, r); }
+    static __device__ __forceinline__ float dloss(float R, float r, float x, float, float, float gsc, const AirGaussLik& g) {
+        return air_gauss_dloss(R, r, x, gsc, g);
+    }
+    static __device__ __forceinline__ float image_loss(float acc, int D, const AirGaussLik& g) { return air_gauss_image_loss(acc, D, g); }
+};
 
 // air_model.py:443-447 for one element
 __device__ __forceinline__ float gauss_kl_term(float plv, float lv, float var, float pv, float mean, float pm) {
@@ -250,14 +268,16 @@ __device__ __forceinline__ bool compose_prefetch_image(const float* images, size
     for (int k = 0; k < COMPOSE_XPRE; ++k) { const int p = tid + k * CF_THREADS; xs[k] = images[base + ((xpre && p < CC) ? p : 0)]; }
     return xpre;
 }
-// canvas + Bernoulli cross-entropy, pixel by pixel, CF_THREADS threads; returns the thread's part of the cross-entropy sum.
+// canvas + pixel likelihood, pixel by pixel, CF_THREADS threads; returns the thread's part of the likelihood's sum
+// (PixelLik<LIK>: the Bernoulli cross-entropy terms, or the squared errors of the Gaussian).
 // Compile-time: OUT, who stores the image's outputs (the clipped reconstruction, d loss / d canvas to memory where g_mem is
-// given, and the sum) -- 0 nobody, 1 every caller, 2 the callers with `owner`; G_LDS, d loss / d canvas into g_lds as well.
+// given, and the sum) -- 0 nobody, 1 every caller, 2 the callers with `owner`; G_LDS, d loss / d canvas into g_lds as well;
+// LIK, the likelihood (glik: its sigma, read by the Gaussian only).
 // (Both callers prefetch the image values -- xs / xpre of compose_prefetch_image -- so that is no switch.)
-template <int OUT, bool G_LDS>
+template <int OUT, bool G_LDS, int LIK = AIR_LIK_BERNOULLI>
 __device__ __forceinline__ float compose_pixels(const ComposeLds& L, const float* images, size_t base, const float (&xs)[COMPOSE_XPRE],
                                                 bool xpre, int N, int C, int w, float gsc, int tid, bool owner,
-                                                float* recon, float* g_mem, float* g_lds) {
+                                                float* recon, float* g_mem, float* g_lds, const AirGaussLik& glik = AirGaussLik{}) {
     const int CC = C * C;
     const bool store = OUT == 1 || (OUT == 2 && owner);
     float acc = 0.0f;
@@ -275,11 +295,11 @@ __device__ __forceinline__ float compose_pixels(const ComposeLds& L, const float
         if (j >= C) { j -= C; ++i; }
         float p1, p0;
         const float r = compose_clip(R, p1, p0);                    // clipped_rec :582
-        if (G_LDS) g_lds[p] = compose_dloss(R, x, p1, p0, gsc);
+        if (G_LDS) g_lds[p] = PixelLik<LIK>::dloss(R, r, x, p1, p0, gsc, glik);
         if (store) {
-            acc += x * logf(p1) + (1.0f - x) * logf(p0);            // :586-589
+            acc += PixelLik<LIK>::term(x, r, p1, p0);
             recon[base + p] = r;
-            if (g_mem) g_mem[base + p] = compose_dloss(R, x, p1, p0, gsc);
+            if (g_mem) g_mem[base + p] = PixelLik<LIK>::dloss(R, r, x, p1, p0, gsc, glik);
         }
     }
     return acc;

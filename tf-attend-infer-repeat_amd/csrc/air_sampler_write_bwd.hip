@@ -1660,6 +1660,9 @@ int compose_fold_plan(const air_write_fwd_t* f, const air_write_bwd_t* b) {
     if (f->B <= 0 || f->N <= 0 || f->C < 2 || f->w < 2 || f->Z <= 0) return AIR_EINVAL;
     if (b->B != f->B || b->N != f->N || b->C != f->C || b->w != f->w) return AIR_EINVAL;
     if (b->literal != 2) return AIR_EINVAL;
+    if (f->likelihood != AIR_LIK_BERNOULLI && f->likelihood != AIR_LIK_GAUSSIAN) return AIR_EINVAL;
+    // the fold computes the Bernoulli likelihood only: any other keeps the two launches
+    if (f->likelihood != AIR_LIK_BERNOULLI) return AIR_ELIMIT;
     if (f->N > MAX_STEPS || 2 * f->w > THREADS || f->w * f->w > WB_THREADS) return AIR_ELIMIT;
     // the hand-off of the batch means was measured with one workgroup per CU: no more items than the 256 CUs of the part
     // this is built for, hence no longest-first order either.  An assumption about placement, not a guarantee (two of

@@ -240,6 +240,10 @@ def main():
     parser.add_argument("--late-backward-from", type=int, default=5000,
                         help="(opt-in: over 48 seeds per precision no switch point keeps the reference order's success rate within 60 000 "
                              "iterations; over the full 276 300 the two end alike and this saves ~3 s -- DESIGN.md section 11.1)")
+    parser.add_argument("--likelihood", default="bernoulli", choices=["bernoulli", "gaussian"],
+                        help="pixel likelihood of the reconstruction loss: the reference's Bernoulli cross-entropy, or the AIR "
+                             "paper's Gaussian around the clipped canvas with the fixed standard deviation vae_likelihood_std "
+                             "(AIRModel(likelihood=...); the reported loss is then a density and may be negative)")
     parser.add_argument("--cnn", action="store_true",
                         help="the reference's conv front-end in front of the LSTM (AIRModel(cnn=True); the reference's own "
                              "training.py passes cnn=False)")
@@ -319,7 +323,7 @@ def main():
                         "staircase": False, "log": True
                     },
                 },
-                seed=args.seed, gemm_precision=args.precision, backward=backward,
+                seed=args.seed, gemm_precision=args.precision, backward=backward, likelihood=args.likelihood,
             )
         )
     train_model, test_model = models
