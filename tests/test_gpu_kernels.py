@@ -581,9 +581,11 @@ def test_transformer_bwd_generic_matches_oracle(H, Hi, Wi, Ho, Wo):
 # ---- exported un-fused kernels vs the oracle directly (not only HIP-vs-HIP) ------------------------------
 
 def test_unfused_lstm_and_reparam_kernels_match_oracle(H):
-    """air_lstm_gates_fwd/bwd, air_lstm_first_step, air_reparam_fwd/bwd against oracle.lstm_cell / oracle.vae
-    arithmetic (BasicLSTMCell: i, j, f, o, forget bias 1.0 -- air_model.py:286; vae.py:22-24) and their
-    torch-autograd gradients."""
+    """air_lstm_gates_fwd, air_lstm_first_step (5 slabs, with bias, no bf16 twin) and air_reparam_fwd against
+    oracle.lstm_cell / the vae.py:22-24 formula (BasicLSTMCell: i, j, f, o, forget bias 1.0 -- air_model.py:286), and
+    air_lstm_gates_bwd (dc_in given, no dgsum) against torch autograd of the same formulas, at one shape each.
+    air_reparam_bwd is NOT called here; it, the other optional arguments and the shape edges of all of these:
+    tests/test_gpu_pointwise_edges.py."""
     from oracle import air_oracle_torch as at  # noqa: F401
     dev, lib = "cuda", H.lib()
     rng = np.random.RandomState(21)
