@@ -334,3 +334,44 @@ def test_wrapper_generate_and_demo(am, tmp_path):
         assert im.size[0] > 8 * 204 and im.size[1] > 2 * 100
     rows = json.load(open(os.path.join(out, "generated.json")))
     assert len(rows) == 16 and all(len(r["positions_s_x_y"]) == r["objects"] for r in rows)
+
+
+def test_generation_survives_a_rebuild_of_the_programs(am):
+    """Host-side state only: a rebuild of the model's programs (set_backward, use_device_rng(seed)) drops the generation
+    launch lists and keeps the generation buffers -- no stale launch list, no reallocated buffer.  Independent of shape, so
+    the smallest model the kernels take; everything is compared bit for bit."""
+    B, N, Z, w = 3, 2, 6, 8
+    am.reset_default_graph()
+    model = am.AIRModel(torch.zeros(B, 16 * 16, device="cuda"), torch.zeros(B, dtype=torch.int32, device="cuda"), cnn=False,
+                        train=True, scope="rebuild", gemm_precision="bf16", max_steps=N, canvas_size=16, windows_size=w,
+                        rnn_units=32, vae_latent_dimensions=Z, vae_recognition_units=(16,), vae_generative_units=(16,),
+                        scale_hidden_units=8, shift_hidden_units=8, z_pres_hidden_units=8)
+    model.set_dynamic(z_pres_prior_log_odds=4.0)
+    rng = np.random.RandomState(3)
+    noise = {"eps_scale": rng.randn(N, B, 1), "eps_shift": rng.randn(N, B, 2), "eps_z": rng.randn(N, B, Z),
+             "eps_x": rng.randn(N, B, w * w),
+             # z_pres = 1 where log-odds + logit(u) > 0: every step but the last scene's second one
+             "u": np.array([[0.5, 0.6, 0.7], [0.4, 0.3, 0.01]])}
+    fields = am.GeneratedScenes.__slots__
+    assert len(fields) == 9
+
+    model.set_generate_noise(noise)
+    sc = model.generate()
+    first = {k: getattr(sc, k).clone() for k in fields}
+    ptrs = {k: getattr(sc, k).data_ptr() for k in fields}
+    assert first["num_digits"].tolist() == [2, 2, 1] and float(first["canvas"].abs().sum()) > 0
+
+    def decoded_canvas():
+        return model.decode(first["latents"], first["scales"], first["shifts"], first["z_pres"]).canvas
+
+    assert torch.equal(decoded_canvas(), first["canvas"])
+    model.set_backward("exact")                              # rebuilds the programs
+    model.set_generate_noise(noise)
+    sc = model.generate()
+    for k in fields:
+        assert torch.equal(getattr(sc, k), first[k]), k
+        assert getattr(sc, k).data_ptr() == ptrs[k], k
+    assert torch.equal(decoded_canvas(), first["canvas"])
+    model.use_device_rng(seed=7)                             # ... and again
+    assert torch.equal(decoded_canvas(), first["canvas"])
+    torch.cuda.synchronize()

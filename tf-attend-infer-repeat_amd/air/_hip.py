@@ -14,6 +14,8 @@ import torch  # noqa: F401  -- FIRST: torch brings its own libamdhip64; loading 
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AIR_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libair_hip.so")   # override: A/B builds in tools/
+# the package default of air_gemm_t.precision -- "fp32": exact-fp32 MFMA (parity path); "bf16": bf16 operands, fp32 accumulate
+GEMM_PRECISION = os.environ.get("AIR_GEMM_PRECISION", "fp32")
 
 # Every upper-case integer constant X below is AIR_X of include/air_hip.h, and every Structure the CamelCase of its
 # air_*_t: tests/test_abi.py compares all of them, and _SIGNATURES, with the header.

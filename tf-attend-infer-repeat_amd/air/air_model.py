@@ -21,22 +21,19 @@ Differences forced by the runtime (TF1 graph/session -> eager device buffers):
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
-from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _hip as H
-from ._hip import ptr as _ptr
-from ._layers import VaeLayers
+from . import summaries as _summaries
+from ._generate import GeneratedScenes, Generator, st_matrices
+from ._hip import GEMM_PRECISION, ptr as _ptr
+from ._store import (VariableStore, _SCOPES, _align8, reset_default_graph,  # noqa: F401  -- (re-exported: every name
+                     saved_cnn_arguments, xavier_uniform_)                  # callers read from this module stays here)
 
-# "fp32": exact-fp32 MFMA (parity path); "bf16": bf16 operands, fp32 accumulate
-GEMM_PRECISION = os.environ.get("AIR_GEMM_PRECISION", "fp32")
-
-_SCOPES = {}
-
+_st_matrices = st_matrices      # (the name this module had for it)
 
 # The sampler-backward order the training driver and the benchmark run (training.py, bench.py).  Round 6 gated the schedule
 # ("reference", "reference_carried", N) -- the reference graph's own accumulation order up to iteration N, the faster carried
@@ -45,253 +42,6 @@ _SCOPES = {}
 # it later; over the full 276 300 iterations the two end alike), so the reference's order stays the default for every iteration
 # and schedules stay opt-in.
 TRAINING_BACKWARD = "reference"
-
-
-def reset_default_graph():
-    """Drops all variable scopes (the tf.reset_default_graph() of this runtime)."""
-    _SCOPES.clear()
-
-
-def saved_cnn_arguments(path):
-    """dict(cnn=, cnn_filters=) of the model saved at `path` -- a torch.save'd state dict, or the prefix of a TensorFlow
-    bundle --, read off its conv variables (cnn/conv1/bias holds one element per filter).  cnn=False for a model saved
-    without the front-end, which is every checkpoint written before it existed."""
-    if os.path.exists(path + ".index"):
-        import tf_checkpoint as tfc
-        entry = tfc.read_index(path + ".index")[1].get(tfc.CNN_SCOPE + "conv1/bias")
-        filters = int(np.prod(entry["shape"])) if entry is not None else 0
-    else:
-        bias = torch.load(path, map_location="cpu").get("cnn/conv1/bias")
-        filters = int(np.prod(np.shape(bias))) if bias is not None else 0
-    return dict(cnn=filters > 0, cnn_filters=filters if filters > 0 else 8)
-
-
-def _align8(n):
-    return (n + 7) & ~7
-
-
-def xavier_uniform_(variables, seed=0, rng=None):
-    """Fills every 2-D tensor of the name -> tensor mapping with Glorot-uniform values, limit sqrt(6 / (fan_in + fan_out)), from
-    ONE numpy stream seeded by `seed` (or the stream `rng`, continued), in the mapping's order (layers.xavier_initializer, the
-    TF 1.3 default of fully_connected and BasicLSTMCell); 1-D tensors (biases: zeros) are left alone, and so are the 4-D
-    conv kernels (VariableStore.initialize draws them)."""
-    if rng is None:
-        rng = np.random.RandomState(seed)
-    with torch.no_grad():
-        for v in variables.values():
-            if v.dim() == 2:
-                limit = math.sqrt(6.0 / (v.shape[0] + v.shape[1]))
-                v.copy_(torch.from_numpy(rng.uniform(-limit, limit, size=tuple(v.shape)).astype(np.float32)))
-
-
-class VariableStore:
-    """All trainable variables of one scope in ONE flat fp32 buffer (+ grads,
-    Adam m/v) so that the optimizer and the data-parallel all-reduce are a
-    single pass / a single collective.  TF variable names (model/air-model.index,
-    SURVEY appendix B) are exposed as views."""
-
-    def __init__(self, hp, device, seed=0):
-        self.hp = hp
-        self.device = device
-        D, d = hp["canvas_size"] ** 2, hp["windows_size"] ** 2
-        R, Z = hp["rnn_units"], hp["vae_latent_dimensions"]
-        Hs, Hh, Hz = hp["scale_hidden_units"], hp["shift_hidden_units"], hp["z_pres_hidden_units"]
-        HT, Hmax = 2 * Hs + 2 * Hh + Hz, max(Hs, Hh, Hz)
-        # the LSTM's input: the canvas, or the [S // 4, S // 4, F] output of the conv front-end (reference :510-535)
-        cnn, F = bool(hp.get("cnn", False)), int(hp.get("cnn_filters", 0))
-        Din = (hp["canvas_size"] // 4) ** 2 * F if cnn else D
-        self.dims = dict(D=D, d=d, R=R, Z=Z, Hs=Hs, Hh=Hh, Hz=Hz, HT=HT, Hmax=Hmax, Din=Din)
-        self.vae_layers = VaeLayers(d, hp["vae_recognition_units"], Z, hp["vae_generative_units"])
-
-        fused = OrderedDict()           # fused device tensors: name -> shape
-        fused["lstm_kernel"] = (Din + R, 4 * R)
-        fused["lstm_bias"] = (4 * R,)
-        fused["whid"] = (R, HT)
-        fused["bhid"] = (HT,)
-        fused["wout"] = (7, Hmax)
-        fused["bout"] = (8,)
-        fused.update(self.vae_layers.shapes())
-        # the conv variables BEHIND every other entry: the offsets of a cnn=False store are those of every earlier build
-        self.cnn_names = []
-        if cnn:
-            from .cnn import CNN
-            self.cnn_names = CNN.variable_names()
-            for i, name in enumerate(self.cnn_names):
-                fused[name] = (5, 5, (1 if i < 2 else F), F) if i % 2 == 0 else (F,)
-
-        self.offsets = OrderedDict()
-        off = 0
-        for k, shp in fused.items():
-            self.offsets[k] = off
-            off += _align8(int(np.prod(shp)))               # every tensor 32-byte aligned in fp32, 16-byte in the bf16 shadow
-        self.n = off                                        # multiple of 8
-        # +4 tail floats: loss / accuracy ride along in the gradient all-reduce
-        self.params = torch.zeros(self.n, dtype=torch.float32, device=device)
-        self.grads = torch.zeros(self.n + 4, dtype=torch.float32, device=device)
-        self.m = torch.zeros(self.n, dtype=torch.float32, device=device)
-        self.v = torch.zeros(self.n, dtype=torch.float32, device=device)
-        self.istate = torch.zeros(H.IST_COUNT, dtype=torch.int32, device=device)
-        # global-norm partial sums: air_grad_sqnorm's fixed count, or one per weight-gradient workgroup
-        self.partials = torch.zeros(max(H.lib().air_optim_num_partials(self.n), 16384), dtype=torch.float32, device=device)
-        self.gnorm = torch.zeros(1, dtype=torch.float32, device=device)
-        self.synced_world = 1            # world size the replicas were last made identical for (AIRModel.sync_parameters)
-        # bf16 shadow of the whole flat variable buffer (same offsets): the weight operand of every bf16 GEMM.
-        # Adam rewrites it with the variables (air_adam_clip_step's bf16_shadow); any host-side change of the
-        # variables (initialize / load_state_dict / sync / checkpoint load) marks it stale and the next
-        # forward() / training() re-derives it with one air_bf16_twin launch.  Code that writes into
-        # `variables[...]` views directly must call touch().
-        self.params16 = torch.zeros(self.n, dtype=torch.int16, device=device)
-        self.shadow_stale = True
-        # PANEL-BLOCKED bf16 twins (air_panel_t) of the weights the forward (untransposed) products read: 16-column
-        # panels of [K][16], so that a 16-column GEMM tile fetches whole cache lines; the LSTM kernel in gate-interleaved
-        # panels (the four gates of four units in 32 contiguous bytes per row), in two pieces (Wx rows, Wh rows).
-        # Maintained by Adam next to the row-major shadow (which the transposed data-gradient products keep reading);
-        # Wx has no other reader than the hoisted x.Wx, so its row-major shadow is dropped ("exclusive") unless the
-        # canvas is large (the throughput tiling of D > 4096 reads row-major lines) or the shape cannot fuse the first step --
-        # or the conv front-end is on: the data gradient d rnn_input = dgsum . Wx^T reads the row-major shadow of Wx.
-        pan, poff = [], 0
-        self.panel_off = {}
-
-        def add_panel(key, src_off, K, N, gates, exclusive=False):
-            nonlocal poff
-            if N % 8 or src_off % 4 or (gates and (N // 4) % 4):
-                return
-            self.panel_off[key] = poff
-            pan.append(H.Panel(src_off, poff, K, N, 4 if gates else 0, 1 if exclusive else 0))
-            poff += _align8(K * N if gates else ((N + 15) // 16) * 16 * K)
-        o = self.offsets["lstm_kernel"]
-        # (its one reader is the x.Wx launch that also runs the first step -- which needs D % 4 == 0 and R % 4 == 0: a shape that
-        # cannot fuse keeps the row-major shadow of Wx; the throughput tiling of a large canvas reads row-major lines: no panel)
-        if Din <= 4096 and Din % 4 == 0 and R % 4 == 0:
-            add_panel("Wx", o, Din, 4 * R, True, exclusive=not cnn)
-        add_panel("Wh", o + Din * 4 * R, R, 4 * R, True)
-        for k, shp in fused.items():
-            if k.endswith("_w") and k not in ("ml_w", "gen0_w") or k == "whid":
-                add_panel(k, self.offsets[k], shp[0], shp[1], False)
-        pan = pan[:H.MAX_PANELS]
-        self.panels = (H.Panel * len(pan))(*pan)
-        self.panel_off = {k: v for k, v in self.panel_off.items() if any(q.dst_off == v for q in pan)}
-        # True: params16 is NOT maintained over the Wx rows of the LSTM kernel (only its panel twin is)
-        self.wx_exclusive = "Wx" in self.panel_off and bool(pan[0].exclusive)
-        self.params16p = torch.zeros(max(poff, 8), dtype=torch.int16, device=device)
-
-        def views(buf):
-            return OrderedDict((k, buf[self.offsets[k]:self.offsets[k] + int(np.prod(s))].view(*s))
-                               for k, s in fused.items())
-        self.P, self.G = views(self.params), views(self.grads)
-        self.P16 = views(self.params16)
-
-        # TF-named views (air-model.index names, relative to scope "<scope>/rnn/")
-        def named(V):
-            o = OrderedDict()
-            o["rnn/kernel"], o["rnn/bias"] = V["lstm_kernel"], V["lstm_bias"]
-            seg = 0
-            rows = (0, 1, (2, 4), (4, 6), 6)
-            for hi, (head, wid, k) in enumerate((("scale/mean", Hs, 1), ("scale/log_variance", Hs, 1),
-                                                 ("shift/mean", Hh, 2), ("shift/log_variance", Hh, 2),
-                                                 ("z_pres/log_odds", Hz, 1))):
-                o[head + "/hidden/weights"] = V["whid"][:, seg:seg + wid]
-                o[head + "/hidden/biases"] = V["bhid"][seg:seg + wid]
-                r = rows[hi]
-                r0, r1 = (r, r + 1) if isinstance(r, int) else r
-                o[head + "/output/weights"] = V["wout"][r0:r1, :wid].t()
-                o[head + "/output/biases"] = V["bout"][r0:r1]
-                seg += wid
-            o.update(self.vae_layers.tf_views(V))
-            for name in self.cnn_names:                  # scope cnn/ sits beside rnn/ (reference :511 against :537)
-                o[name] = V[name]
-            return o
-        self.variables = named(self.P)
-        self.gradients = named(self.G)
-        self.adam_m, self.adam_v = named(views(self.m)), named(views(self.v))   # TF slots <var>/Adam, <var>/Adam_1
-        self.num_trainable = sum(v.numel() for v in self.variables.values())
-        self.initialize(seed)
-
-    def initialize(self, seed=0):
-        """Xavier/Glorot-uniform weights, zero biases -- TF1.3 defaults of
-        BasicLSTMCell / layers.fully_connected (limits sqrt(6/(in+out)) as in
-        air-model.meta's initializer constants); zero Adam slots, step 0."""
-        self.params.zero_()
-        rng = np.random.RandomState(seed)
-        # the reference creates the conv layers first (:511-533): their kernels come first from the store's one stream,
-        # Glorot-uniform over fan_in = 25 Cin, fan_out = 25 F (tf.layers.conv2d's default), zero biases
-        for name in self.cnn_names[::2]:
-            k = self.variables[name]
-            limit = math.sqrt(6.0 / (25 * k.shape[2] + 25 * k.shape[3]))
-            k.copy_(torch.from_numpy(rng.uniform(-limit, limit, size=tuple(k.shape)).astype(np.float32)))
-        xavier_uniform_(self.variables, rng=rng)
-        self.m.zero_(); self.v.zero_(); self.grads.zero_(); self.istate.zero_()
-        self.shadow_stale = True
-
-    def touch(self):
-        """The variables were changed from the host side: the bf16 shadow has to be re-derived."""
-        self.shadow_stale = True
-
-    def refresh_shadow(self, stream=None):
-        if stream is None:
-            stream = H.stream(self.device)
-        H.check(H.lib().air_bf16_twin(_ptr(self.params), _ptr(self.params16), self.n, stream), "air_bf16_twin")
-        if len(self.panels):
-            H.check(H.lib().air_panel_shadow(_ptr(self.params), _ptr(self.params16p), self.panels, len(self.panels), stream),
-                    "air_panel_shadow")
-        self.shadow_stale = False
-
-    def panel(self, key):
-        """device pointer (as int16 tensor view) of the panel-blocked twin of matrix `key`, or None"""
-        if key not in self.panel_off:
-            return None
-        return self.params16p[self.panel_off[key]:]
-
-    def state_dict(self):
-        sd = OrderedDict((k, v.detach().cpu().contiguous().clone()) for k, v in self.variables.items())
-        sd["global_step"] = self.istate[H.IST_GLOBAL_STEP].cpu().clone()
-        # Adam slots per variable under TensorFlow's slot names (<var>/Adam, <var>/Adam_1): independent of the
-        # alignment / order of the flat buffers, which is an implementation detail that has changed between rounds
-        for k in self.variables:
-            sd[k + "/Adam"] = self.adam_m[k].detach().cpu().contiguous().clone()
-            sd[k + "/Adam_1"] = self.adam_v[k].detach().cpu().contiguous().clone()
-        return sd
-
-    def load_state_dict(self, sd, strict=True, load_optimizer=True):
-        """Variables (+ global_step, + the Adam slots when the dict carries them per variable).  The dict is validated BEFORE
-        anything is written: a caller that catches the error keeps its old state.  load_optimizer=False takes the
-        variables and global_step only -- the way to use checkpoints whose optimizer state cannot be read (flat slots
-        written by an earlier build) for evaluation / demo.py."""
-        missing = [k for k in self.variables if k not in sd]
-        if strict and missing:
-            raise KeyError("missing variable %s" % missing[0])
-        for k, v in self.variables.items():
-            if k in sd and int(np.prod(np.shape(sd[k]))) != v.numel():
-                raise ValueError("variable %s has %r elements, expected %r" % (k, np.shape(sd[k]), tuple(v.shape)))
-        slots = [k for k in self.variables if k + "/Adam" in sd or k + "/Adam_1" in sd]
-        if load_optimizer:
-            half = [k for k in slots if not (k + "/Adam" in sd and k + "/Adam_1" in sd)]
-            if half:
-                raise ValueError("state dict carries only one of the two Adam slots (<var>/Adam, <var>/Adam_1) of %s" % half[0])
-            if "_adam_m" in sd and not slots:
-                # flat slots written by an older build: their offsets are those of THAT build's buffer layout (the alignment
-                # of the flat buffers has changed since) -- refuse loudly rather than load shifted slots
-                raise ValueError("state dict carries flat Adam slots (_adam_m / _adam_v) of an unknown buffer layout; it needs "
-                                 "per-variable slots (<var>/Adam, <var>/Adam_1) -- or load_state_dict(sd, load_optimizer=False) "
-                                 "for the variables alone")
-            for k in slots:
-                for slot in ("/Adam", "/Adam_1"):
-                    if int(np.prod(np.shape(sd[k + slot]))) != self.variables[k].numel():
-                        raise ValueError("slot %s has %r elements, expected %r" % (k + slot, np.shape(sd[k + slot]),
-                                                                                   tuple(self.variables[k].shape)))
-        global_step = int(sd["global_step"]) if "global_step" in sd else None       # (converted before the first write too)
-        for k, v in self.variables.items():
-            if k in sd:
-                v.copy_(torch.as_tensor(np.asarray(sd[k])).to(v.dtype).reshape(v.shape))
-        if global_step is not None:
-            self.istate[H.IST_GLOBAL_STEP] = global_step
-        if load_optimizer:
-            for k in slots:
-                v = self.variables[k]
-                self.adam_m[k].copy_(torch.as_tensor(np.asarray(sd[k + "/Adam"])).to(v.dtype).reshape(v.shape))
-                self.adam_v[k].copy_(torch.as_tensor(np.asarray(sd[k + "/Adam_1"])).to(v.dtype).reshape(v.shape))
-        self.shadow_stale = True
-
 
 _ANNEALABLE = {
     "z_pres_prior_log_odds": H.DYN_PRIOR_LOG_ODDS, "z_pres_temperature": H.DYN_TEMPERATURE,
@@ -320,26 +70,32 @@ def _enqueue(plan, stream):
         op(stream)
 
 
-class GeneratedScenes:
-    """What AIRModel.generate() / decode() return: device tensors, image-major like the rec_* attributes, all max_steps
-    steps (a step is an object of scene b while masks[b, t] == 1: the first num_digits[b] of them).  They are VIEWS of the
-    model's generation buffers: the next generate() / decode() call overwrites them."""
-    __slots__ = ("canvas", "num_digits", "scales", "shifts", "z_pres", "masks", "latents", "windows", "st_back")
-
-    def __init__(self, **kw):
-        for k in self.__slots__:
-            setattr(self, k, kw[k])
-
-    def st_back_matrices(self):
-        """[B, N, 2, 3] window -> canvas matrices (air_model.py:353-356), the form air.visualize draws boxes from"""
-        return _st_matrices(self.st_back)
-
-
-def _st_matrices(a):
-    """[..., 3] = (1/s, -x/s, -y/s) -> [..., 2, 3] axis-aligned spatial-transformer matrices"""
-    z = torch.zeros_like(a[..., 0])
-    return torch.stack([torch.stack([a[..., 0], z, a[..., 1]], -1),
-                        torch.stack([z, a[..., 0], a[..., 2]], -1)], -2)
+# Entry point of the library -> the kernel it launches, as rocprofv3 prints it: every entry point AIRModel._call takes
+# (air_gemm's kernels come from air_gemm_kernel_name, _gemm).  A template names the instantiation by a model attribute,
+# filled in by _call; None: the library names the kernel of the descriptor (air_*_kernel_name, _build_backward).
+# tests/test_kernel_names.py holds every name against the symbols of the built library.
+KERNEL_NAMES = {
+    "air_step_begin": "step_begin_kernel",
+    "air_lstm_first_step": "lstm_first_step_kernel<{slabs}>",           # <4> split-K slabs, or <0>: a run-time count
+    "air_attend_fwd": "attend_fwd_kernel",
+    "air_vae_bottleneck_fwd": "bottleneck_fwd_kernel<256, {twins}>",    # (bf16 path only) per operand form: bf16 twins or fp32
+    "air_write_fwd": "write_fwd{gauss}_kernel<1024>",                   # (a __global__ per likelihood over one body)
+    "air_finalize": "finalize_kernel",
+    "air_write_bwd": None,
+    "air_write_fwd_bwd": None,
+    "air_vae_bottleneck_bwd": "bottleneck_bwd_kernel<256, {twins}>",
+    "air_attend_bwd": "attend_bwd_kernel",
+    "air_wgrad_grouped": "wgrad_grouped{bf16}_kernel",
+    "air_colsum": "colsum_kernel",
+    "air_grad_sqnorm": "grad_sqnorm_kernel",
+    "air_adam_clip_step": "adam_clip_kernel",
+    "air_adam_clip_step_panels": "adam_panels_kernel",
+    "air_cnn_fwd": "cnn_fwd_kernel<{filters}>",
+    "air_cnn_bwd_sq": "cnn_bwd_kernel<{filters}>",                      # (its second launch is cnn_reduce_sq_kernel)
+    "air_philox_fill": "philox_fill_kernel",
+    "air_scene_records": "scene_records_kernel",
+    "air_render": "render_kernel",
+}
 
 
 def _step_lds(max_steps, canvas_size, windows_size, Hs, Hh, Hz, wout_ld):
@@ -590,9 +346,7 @@ class AIRModel:
         self._graph = None
         self._dirty = True
         self._steps_executed = None
-        self._gen = None                          # buffers + launch lists of generate() / decode(), built at their first call
-        self._gen_calls = 0                       # the device RNG's call counter of generate() (never global_step)
-        self._gen_injected = False
+        self._generator = Generator(self)         # generate() / decode(): buffers + launch lists, built at their first call
         self._alloc()
         self._build_programs()
 
@@ -779,27 +533,13 @@ class AIRModel:
                    + (4 * N if bias is not None else 0) + extra_bytes,
                    flops=2 * M * N * K, kernel=kbuf.value.decode())
 
-    _KERNEL_OF = {"air_lstm_first_step": "lstm_first_step_kernel", "air_step_begin": "step_begin_kernel", "air_attend_fwd": "attend_fwd_kernel",
-                  "air_attend_bwd": "attend_bwd_kernel", "air_write_fwd": "write_fwd_kernel<1024>",
-                  "air_write_bwd": "write_bwd_kernel", "air_finalize": "finalize_kernel",
-                  "air_grad_sqnorm": "grad_sqnorm_kernel", "air_adam_clip_step": "adam_clip_kernel",
-                  "air_adam_clip_step_panels": "adam_panels_kernel", "air_scene_records": "scene_records_kernel",
-                  "air_render": "render_kernel", "air_philox_fill": "philox_fill_kernel"}
-    # (air_cnn_fwd: cnn_fwd_kernel<F>; air_cnn_bwd_sq is two launches, cnn_bwd_kernel<F> and cnn_reduce_sq_kernel: _call)
-
     def _call(self, name, *args, nbytes=0, flops=0, tag=None):
         fn = getattr(self.lib, name)
-        kernel = self._KERNEL_OF.get(name)
-        if name == "air_lstm_first_step":                    # instantiated per slab count: <4> in the train step, <0> = run-time count
-            kernel = "lstm_first_step_kernel<%d>" % (4 if args[1] == 4 else 0)
-        if name in ("air_vae_bottleneck_fwd", "air_vae_bottleneck_bwd"):   # (bf16 path only) instantiated per operand form: bf16 twins or fp32 operands
-            kernel = "bottleneck_%s_kernel<256, %s>" % (name[-3:], "true" if self._twins else "false")
-        if name == "air_wgrad_grouped":
-            kernel = "wgrad_grouped_bf16_kernel" if self._prec else "wgrad_grouped_kernel"
-        if name in ("air_cnn_fwd", "air_cnn_bwd_sq"):        # (the backward's second launch is cnn_reduce_sq_kernel)
-            kernel = "cnn_%s_kernel<%d>" % (name[8:11], self.cnn_filters)
-        if name == "air_write_fwd" and self.likelihood == "gaussian":      # a __global__ of its own over write_fwd_kernel's body
-            kernel = "write_fwd_gauss_kernel<1024>"
+        kernel = KERNEL_NAMES[name]
+        if kernel is not None:
+            kernel = kernel.format(slabs=4 if self._xw_slabs == 4 else 0, twins="true" if self._twins else "false",
+                                   bf16="_bf16" if self._prec else "", filters=self.cnn_filters,
+                                   gauss="_gauss" if self.likelihood == "gaussian" else "")
         return _Op(tag or name, lambda s, fn=fn, args=args, name=name: H.check(fn(*args, s), name),
                    nbytes=nbytes, flops=flops, kernel=kernel)
 
@@ -873,8 +613,7 @@ class AIRModel:
             keep.append(cf)
             self._cnn_fwd = self._call("air_cnn_fwd", C.byref(cf), nbytes=4 * (B * (D + Din) + sum(v.numel() for v in cv)),
                                        flops=2 * 25 * B * F * (S * S + F * ((S // 2) ** 2 + (S // 4) ** 2)), tag="cnn_fwd")
-        if self._gen is not None:
-            self._gen["ops"] = None             # (the generation launch list is rebuilt with these; its buffers stay)
+        self._generator.drop_ops()              # (the generation launch lists are rebuilt with these; its buffers stay)
 
         def gemm(*args, **kw):
             fwd.append(self._gemm(*args, **kw))
@@ -1614,90 +1353,15 @@ class AIRModel:
 
     __call__ = forward
 
-    # --------------------------------------------------------------- generation
-    # The generative half of the loop body (reference :288-439, 582; vae.py:26-41) with the posterior heads replaced by
-    # the priors: no image, no LSTM, no recognition network.  Own noise / record / output buffers, own RNG call counter:
-    # a forward() / training() result, the model's noise buffers, global_step, the schedules and a captured graph are not
-    # touched.  Launches: [air_philox_fill ->] air_scene_records -> the generative GEMMs and gen_mean with the forward's
-    # descriptors -> air_render (include/air_hip.h).
-    def _gen_state(self):
-        g = self._gen
-        if g is None:
-            dm, dv = self.store.dims, self.input_images.device
-            B, N = self.batch_size, self.max_steps
-            D, d, Z = dm["D"], dm["d"], dm["Z"]
-            f, h16 = self._f32, self._i16
-            g = self._gen = dict(ops=None)
-            g["normals"], g["uniforms"] = f(N * B * (1 + 2 + Z + d)), f(N * B)
-            g["eps_scale"], g["eps_shift"], g["eps_z"], g["eps_x"], g["u"] = _carve_noise(g["normals"], g["uniforms"], N, B, Z, d)
-            # decode(): the caller's tensors, step-major
-            g["in_s"], g["in_xy"], g["in_z"], g["in_p"] = f(N, B), f(N, B, 2), f(N, B, Z), f(N, B)
-            g["att"] = f(N, B, H.ATT_STRIDE)
-            # (rows of Z elements: the operand layout of the forward's unfused first generative GEMM, lda = K = Z)
-            g["z"], g["z16"] = f(N, B, Z), h16(N, B, Z)
-            g["act"] = [f(N, B, u) for u in self.vae_generative_units]
-            g["act16"] = [h16(N, B, u) for u in self.vae_generative_units]
-            g["vrec"] = f(N, B, d)
-            g["canvas"] = f(B, D)
-            g["digits"] = torch.zeros(B, dtype=torch.int32, device=dv)
-        if g["ops"] is None:
-            g["ops"] = self._build_generate(g)
-        return g
-
-    def _build_generate(self, g):
-        """The generation launch lists; the decoder's GEMMs are the forward's (_generative_ops) on the generation buffers."""
-        dm = self.store.dims
-        B, N, NB = self.batch_size, self.max_steps, self.max_steps * self.batch_size
-        d, Z = dm["d"], dm["Z"]
-        ops = {}
-        for mode, srcs in (("sample", ("eps_scale", "eps_shift", "eps_z", "u")), ("given", ("in_s", "in_xy", "in_z", "in_p"))):
-            r = H.SceneRecords(*[_ptr(g[k]) for k in srcs], _ptr(self.dyn), _ptr(g["att"]), _ptr(g["z"]), _ptr(g["z16"]),
-                               B, N, Z, Z, 1 if mode == "given" else 0)
-            self._keep.append(r)
-            ops[mode] = self._call("air_scene_records", C.byref(r), nbytes=NB * (4 * (4 + 2 * Z) + 64), tag="scene_records_" + mode)
-        for name, sigma in (("out_noise", float(self.vae_likelihood_std)), ("out_mean", 0.0)):
-            dec = self._generative_ops(g["z"], g["z16"], g["act"], g["act16"], g["vrec"], g["eps_x"], sigma)
-            ops["decoder"], ops[name] = dec[:-1], dec[-1]          # (the layers' descriptors do not depend on sigma)
-        rd = H.Render(_ptr(g["vrec"]), _ptr(g["att"]), _ptr(g["canvas"]), _ptr(g["digits"]), B, N,
-                      self.canvas_size, self.windows_size)
-        self._keep.append(rd)
-        ops["render"] = self._call("air_render", C.byref(rd), nbytes=NB * (d * 4 + 64) + B * dm["D"] * 4, tag="render")
-        return ops
-
+    # ------------------------------------------------- generation (air/_generate.py)
     def generate_ops(self, likelihood_noise=False, given=False, fill=True):
         """The launches of one generate() (given=False) or decode() call, in order (profiling tools)."""
-        g = self._gen_state()
-        o = g["ops"]
-        ops = [self._gen_fill_op()] if fill else []
-        return ops + [o["given" if given else "sample"]] + o["decoder"] + [o["out_noise" if likelihood_noise else "out_mean"], o["render"]]
-
-    def _gen_fill_op(self):
-        g, seed, call = self._gen, self._seed, self._gen_calls
-        return self._call("air_philox_fill", _ptr(g["normals"]), g["normals"].numel(), _ptr(g["uniforms"]), g["uniforms"].numel(),
-                          C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(call),
-                          nbytes=4 * (g["normals"].numel() + g["uniforms"].numel()), tag="philox_fill")
-
-    def _gen_run(self, given, likelihood_noise, needs_noise):
-        g = self._gen_state()
-        self._fresh_shadow()
-        s = self._stream()
-        fill = needs_noise and not self._gen_injected
-        _enqueue(self.generate_ops(likelihood_noise, given, fill), s)
-        if fill:
-            self._gen_calls += 1
-        self._gen_injected = False
-        a = g["att"]
-        return GeneratedScenes(canvas=g["canvas"], num_digits=g["digits"],
-                               scales=a[:, :, H.ATT_S:H.ATT_S + 1].transpose(0, 1), shifts=a[:, :, H.ATT_X:H.ATT_Y + 1].transpose(0, 1),
-                               z_pres=a[:, :, H.ATT_Z].t(), masks=a[:, :, H.ATT_MASK].t(), latents=g["z"].transpose(0, 1),
-                               windows=g["vrec"].transpose(0, 1), st_back=a[:, :, H.ATT_ST_BACK:H.ATT_ST_BACK + 3].transpose(0, 1))
+        return self._generator.launch_list(likelihood_noise, given, fill)
 
     def set_generate_noise(self, noise):
         """Injects eps_scale [N,B,1], eps_shift [N,B,2], eps_z [N,B,Z], eps_x [N,B,d], u [N,B] (the dict of set_noise) for
         ONE generate() / decode() call; the device RNG is back after it."""
-        g = self._gen_state()
-        _copy_noise(noise, g.__getitem__)
-        self._gen_injected = True
+        self._generator.set_noise(noise)
 
     def generate(self, likelihood_noise=False):
         """Draws batch_size scenes from the model's priors and renders them: z_pres from the Concrete prior (rounded, as at
@@ -1707,22 +1371,13 @@ class AIRModel:
         noise before the sigmoid (vae.py:36-41).  Noise comes from the device Philox stream keyed by (seed, number of
         earlier drawing calls): the same seed and call index give the same scenes, successive calls differ.  Works on train
         and test models; returns a GeneratedScenes.  No gradients flow through it."""
-        return self._gen_run(False, bool(likelihood_noise), True)
+        return self._generator.run(False, bool(likelihood_noise), True)
 
     def decode(self, latents, scales, shifts, z_pres, likelihood_noise=False):
         """Renders the scenes described by the caller's DEVICE tensors latents [B,N,Z], scales [B,N,1] (or [B,N]), shifts
         [B,N,2] and z_pres [B,N] (used as given -- it may be relaxed; the masks are re-derived by the stopping rule), the
         way generate() renders its own.  likelihood_noise=True draws eps_x (or takes set_generate_noise's)."""
-        g = self._gen_state()
-        B, N, Z = self.batch_size, self.max_steps, self.vae_latent_dimensions
-        for name, t, shape, dst in (("latents", latents, (B, N, Z), g["in_z"]), ("scales", scales, (B, N, 1), g["in_s"]),
-                                    ("shifts", shifts, (B, N, 2), g["in_xy"]), ("z_pres", z_pres, (B, N, 1), g["in_p"])):
-            if not (torch.is_tensor(t) and t.is_cuda):
-                raise H.AirHipError("%s must be a CUDA/HIP device tensor: this path has no CPU fallback" % name)
-            if t.dtype != torch.float32 or t.numel() != B * N * shape[2] or tuple(t.shape[:2]) != (B, N):
-                raise ValueError("%s must be float32 %r" % (name, shape))
-            dst.copy_(t.reshape(shape).transpose(0, 1).reshape(dst.shape))
-        return self._gen_run(True, bool(likelihood_noise), bool(likelihood_noise))
+        return self._generator.decode(latents, scales, shifts, z_pres, likelihood_noise)
 
     # ------------------------------------------------------------------ outputs
     def _ensure(self):
@@ -1766,37 +1421,19 @@ class AIRModel:
 
     def summary_names(self):
         """Names of the reference's numeric summaries (self.num_summaries of air_model.py:160-209, 608-625), in its order."""
-        names = ["loss", "accuracy"]
-
-        def by_digit(name):
-            names.extend("%s_%d_dig" % (name, i) for i in range(self.max_digits + 1))
-            names.append(name + "_all_dig")
-        for n in ("steps", "rec_loss", "digit_acc", "total_loss"):
-            by_digit(n)
-        for n in ("scale", "z_pres_prob", "z_pres_kl", "scale_kl", "shift_kl", "vae_kl"):
-            for i in range(self.max_steps):
-                by_digit("%s_%d_step" % (n, i + 1))
-        return names
+        return ["loss", "accuracy"] + _summaries.numeric_names(self.max_steps, self.max_digits)
 
     def numeric_summaries(self, out=None):
         """The values of summary_names() for the last pass, as ONE launch on the current stream (air_summaries,
         include/air_hip.h) into the float32 device vector `out` (allocated when None) -- what sess.run(num_summaries)
         evaluates at training.py:171-180.  No host synchronisation: the caller copies `out` when it wants the numbers."""
         self._ensure()
-        n = self.lib.air_summaries_count(self.max_steps, self.max_digits)
-        if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=self.input_images.device)
-        if out.numel() != n or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 vector of %d elements" % n)
-        a = H.Summaries(_ptr(self.att), _ptr(self.target_num_digits), _ptr(self.run_digits), _ptr(self._rec_loss),
-                        _ptr(self._loss_item), _ptr(self.scalars), _ptr(out), self.batch_size, self.max_steps, self.max_digits)
-        H.check(self.lib.air_summaries(C.byref(a), self._stream()), "air_summaries")
-        return out
+        return _summaries.numeric_summaries(self, out)
 
-    # ---- histogram summaries (air_model.py:642-687): air_histograms over strided views of the flat buffers -----------
+    # ---- histogram summaries (air_model.py:642-687): air_histograms over strided views of the flat buffers (air/summaries.py)
     def _summary_tags(self):
-        from .summaries import summary_tags
-        return summary_tags(self.max_steps, self.max_digits, self.vae_recognition_units, self.vae_generative_units, self.scope)
+        return _summaries.summary_tags(self.max_steps, self.max_digits, self.vae_recognition_units, self.vae_generative_units,
+                                       self.scope)
 
     def _no_cnn_histograms(self):
         if self.cnn:
@@ -1817,46 +1454,13 @@ class AIRModel:
         self._no_cnn_histograms()
         return self._summary_tags().gradients[::3]
 
-    def _histogram_plan(self, which):
-        """descriptors + workspace of one of the two launches, built once (the views never move)"""
-        if which not in self._hist_plans:
-            from .summaries import variable_order, view_2d
-            order = variable_order(len(self.vae_recognition_units), len(self.vae_generative_units))
-            views = self.store.variables if which == "var" else self.store.gradients
-            kinds = (0,) if which == "var" else (1, 2)
-            descs = []
-            for kind in kinds:
-                for name in order:
-                    v = views[name]
-                    rows, cols, ld = view_2d(v)
-                    descs.append(H.HistogramDesc(v.data_ptr(), rows, cols, ld, kind))
-            arr = (H.HistogramDesc * len(descs))(*descs)
-            nout = self.lib.air_histograms_output_bytes(arr, len(descs))
-            nws = self.lib.air_histograms_workspace_bytes(arr, len(descs))
-            if nout < 0 or nws < 0:
-                H.check(int(min(nout, nws)), "air_histograms_workspace_bytes")
-            ws = torch.empty(int(nws), dtype=torch.uint8, device=self.input_images.device)
-            self._hist_plans[which] = (arr, int(nout), ws)
-        return self._hist_plans[which]
-
-    def _histograms(self, which, out):
-        arr, nout, ws = self._histogram_plan(which)
-        if out is None:
-            out = torch.empty(nout, dtype=torch.uint8, device=self.input_images.device)
-        if out.numel() != nout or out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda:
-            raise ValueError("out must be a contiguous uint8 device vector of %d bytes" % nout)
-        a = H.Histograms(arr, len(arr), 1.0 / self._world(), _ptr(self.dyn), _ptr(self.store.gnorm), _ptr(out), _ptr(ws),
-                         nout, ws.numel())
-        H.check(self.lib.air_histograms(C.byref(a), self._stream()), "air_histograms")
-        return out
-
     def var_summaries(self, out=None):
         """TensorFlow's histograms of the variables (tf.summary.histogram(v.name, v.value()), air_model.py:642-649), tags
         var_summary_names(), as ONE call of air_histograms (include/air_hip.h) on the current stream over the strided views
         of the flat variable buffer -- nothing is copied out variable by variable.  `out`: a uint8 device vector
         (allocated when None) that air.summaries.decode_histograms() reads once fetched.  No host synchronisation."""
         self._no_cnn_histograms()
-        return self._histograms("var", out)
+        return _summaries.histograms(self, "var", out)
 
     def grad_summaries(self, out=None):
         """The histograms of the gradients, original and applied (air_model.py:657-687), tags grad_summary_names(), as ONE
@@ -1867,11 +1471,11 @@ class AIRModel:
         if not self.train:
             raise H.AirHipError("grad_summaries: the model was built with train=False and has no gradients")
         self._no_cnn_histograms()
-        return self._histograms("grad", out)
+        return _summaries.histograms(self, "grad", out)
 
     @property
     def rec_st_back(self):
-        return _st_matrices(self._stack(self.att[:, :, H.ATT_ST_BACK:H.ATT_ST_BACK + 3]))   # [B,T',3] = 1/s, -x/s, -y/s
+        return st_matrices(self._stack(self.att[:, :, H.ATT_ST_BACK:H.ATT_ST_BACK + 3]))   # [B,T',3] = 1/s, -x/s, -y/s
 
     def state_dict(self):
         return self.store.state_dict()

@@ -1,6 +1,9 @@
-"""The reference's TensorBoard summaries, host side: their tags, and the decoding of what air_histograms leaves in a buffer.
+"""The reference's TensorBoard summaries, host side: their tags, the two launches that compute them for a model
+(air_summaries, air_histograms), and the decoding of what air_histograms leaves in a buffer.
 
-Pure host code (no GPU, no model instance).  The reference builds four merged groups (training.py:144-149):
+The tags, view_2d and the decoding are pure host code (no GPU, no model instance); numeric_summaries() and histograms()
+take a built AIRModel -- its public methods of those names are thin calls of them -- and import torch and the library
+when they run, not when this module is imported.  The reference builds four merged groups (training.py:144-149):
   numeric    88 scalars of the test model             air_model.py:160-209, 613-625
   variables  36 histograms of the trainable variables :642-649
   image      1 image summary ("reconstruction")       :627-640
@@ -8,6 +11,7 @@ Pure host code (no GPU, no model instance).  The reference builds four merged gr
 A tf.summary node is named after its tag inside the model's name scope, and that name is what TensorBoard shows: the train
 model (built first) owns the name scope "<scope>", the variable-sharing test model "<scope>_1"; a variable's name
 "<scope>/rnn/<name>:0" becomes "<scope>/rnn/<name>_0"."""
+import ctypes as C
 from collections import OrderedDict, namedtuple
 
 import numpy as np
@@ -90,7 +94,6 @@ def histogram_limits():
     """the bucket limits of TF 1.3's histogram (float64, ascending), from the library's host function"""
     global _LIMITS
     if _LIMITS is None:
-        import ctypes as C
         from . import _hip as H
         n = H.lib().air_histogram_num_buckets()
         buf = (C.c_double * n)()
@@ -126,4 +129,60 @@ def gradient_summaries(histograms):
         out[tag] = h
         out[tag + "_norm"] = float(np.sqrt(h.sum_squares))
         out[tag + "_avg"] = h.sum / h.num
+    return out
+
+
+# ---- the launches, for a built AIRModel `m` (AIRModel.numeric_summaries / var_summaries / grad_summaries) ---------------
+def numeric_summaries(m, out=None):
+    """air_summaries on the model's stream over the records of its last pass, into `out` (allocated when None)"""
+    import torch
+    from . import _hip as H
+    n = m.lib.air_summaries_count(m.max_steps, m.max_digits)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=m.input_images.device)
+    if out.numel() != n or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 vector of %d elements" % n)
+    a = H.Summaries(H.ptr(m.att), H.ptr(m.target_num_digits), H.ptr(m.run_digits), H.ptr(m._rec_loss),
+                    H.ptr(m._loss_item), H.ptr(m.scalars), H.ptr(out), m.batch_size, m.max_steps, m.max_digits)
+    H.check(m.lib.air_summaries(C.byref(a), m._stream()), "air_summaries")
+    return out
+
+
+def _histogram_plan(m, which):
+    """descriptors + workspace of one of the two launches ("var" / "grad"), built once per model (the views never move)"""
+    import torch
+    from . import _hip as H
+    if which not in m._hist_plans:
+        order = variable_order(len(m.vae_recognition_units), len(m.vae_generative_units))
+        views = m.store.variables if which == "var" else m.store.gradients
+        kinds = (0,) if which == "var" else (1, 2)
+        descs = []
+        for kind in kinds:
+            for name in order:
+                v = views[name]
+                rows, cols, ld = view_2d(v)
+                descs.append(H.HistogramDesc(v.data_ptr(), rows, cols, ld, kind))
+        arr = (H.HistogramDesc * len(descs))(*descs)
+        nout = m.lib.air_histograms_output_bytes(arr, len(descs))
+        nws = m.lib.air_histograms_workspace_bytes(arr, len(descs))
+        if nout < 0 or nws < 0:
+            H.check(int(min(nout, nws)), "air_histograms_workspace_bytes")
+        ws = torch.empty(int(nws), dtype=torch.uint8, device=m.input_images.device)
+        m._hist_plans[which] = (arr, int(nout), ws)
+    return m._hist_plans[which]
+
+
+def histograms(m, which, out=None):
+    """air_histograms on the model's stream over the strided views of its flat variable ("var") or gradient ("grad")
+    buffer, into the uint8 device vector `out` (allocated when None) that decode_histograms() reads once fetched"""
+    import torch
+    from . import _hip as H
+    arr, nout, ws = _histogram_plan(m, which)
+    if out is None:
+        out = torch.empty(nout, dtype=torch.uint8, device=m.input_images.device)
+    if out.numel() != nout or out.dtype != torch.uint8 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("out must be a contiguous uint8 device vector of %d bytes" % nout)
+    a = H.Histograms(arr, len(arr), 1.0 / m._world(), H.ptr(m.dyn), H.ptr(m.store.gnorm), H.ptr(out), H.ptr(ws),
+                     nout, ws.numel())
+    H.check(m.lib.air_histograms(C.byref(a), m._stream()), "air_histograms")
     return out

@@ -30,9 +30,9 @@ from collections import OrderedDict
 import torch
 
 from . import _hip as H
-from . import air_model as _am
 from ._hip import MAX_WGRAD_PROBLEMS  # noqa: F401  -- (this module's public name of the limit; _hip.py owns the value)
 from ._layers import VaeLayers, load_variables
+from ._store import xavier_uniform_
 
 _ACTIVATIONS = {"softplus": (H.ACT_SOFTPLUS, H.GRAD_SOFTPLUS), "relu": (H.ACT_RELU, H.GRAD_RELU)}
 _SALT = 0x56414531            # keeps this module's noise apart from others keyed by the same user seed
@@ -130,7 +130,7 @@ class _VaeFn(torch.autograd.Function):
 
 class VAE(torch.nn.Module):
     """vae.py:5-43 as a module.  precision: "fp32" (exact-fp32 MFMA), "bf16" (operands rounded to bf16 on their way into LDS,
-    fp32 accumulate) or None for the package default (air_model.GEMM_PRECISION)."""
+    fp32 accumulate) or None for the package default (GEMM_PRECISION of air._hip; air_model reads the same)."""
 
     def __init__(self, input_dim, rec_hidden_units, latent_dim, gen_hidden_units, likelihood_std=0.0, activation="softplus",
                  precision=None, device="cuda", seed=0):
@@ -139,7 +139,7 @@ class VAE(torch.nn.Module):
         if activation not in _ACTIVATIONS:
             raise ValueError("activation must be one of %s (the activations air_gemm has), got %r"
                              % (sorted(_ACTIVATIONS), activation))
-        prec = precision or _am.GEMM_PRECISION
+        prec = precision or H.GEMM_PRECISION
         if prec not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32', 'bf16' or None")
         if len(rec) + len(gen) + 2 > H.MAX_WGRAD_PROBLEMS:
@@ -159,7 +159,7 @@ class VAE(torch.nn.Module):
         for k, shp in shapes.items():
             setattr(self, k, torch.nn.Parameter(torch.zeros(*shp, dtype=torch.float32, device=device)))
         self._names = tuple(shapes)
-        _am.xavier_uniform_(self.variables(), seed)
+        xavier_uniform_(self.variables(), seed)
 
     def _fused(self):
         """the parameters under their fused names (rec<i>_w/_b, ml_w/_b, gen<i>_w/_b, out_w/_b), in layer order"""

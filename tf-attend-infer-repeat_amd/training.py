@@ -179,13 +179,13 @@ class TensorBoardWriter:
 
     def image(self, step):
         from air import _hip as H
-        from air.air_model import _st_matrices
+        from air.air_model import st_matrices
         from air.visualize import visualize_reconstructions
         m = self.test_model
         n = min(m.num_summary_images, m.batch_size)
         # every max_steps record (no read of T' on the host): a step the loop did not reach draws no box, no image has
         # more digits than steps were run (air_model.py:224-231 pads those steps with zeros)
-        st_back = _st_matrices(m.att[:, :n, H.ATT_ST_BACK:H.ATT_ST_BACK + 3].transpose(0, 1))
+        st_back = st_matrices(m.att[:, :n, H.ATT_ST_BACK:H.ATT_ST_BACK + 3].transpose(0, 1))
         img = visualize_reconstructions(m.input_images[:n], m.reconstruction[:n], st_back, m.rec_num_digits[:n],
                                         m.canvas_size, m.windows_size, m.max_steps, zoom=2).contiguous()
         tag = self.tags.image[0]
