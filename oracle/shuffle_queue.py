@@ -11,6 +11,7 @@ size > min_after_dequeue.  The reader threads out-run a train step by orders of 
 whenever a batch is taken (the assumption of air_shuffle_batch_t in include/air_hip.h, stated there).
 
 tf_queue_batches() is that queue written out literally (python list, pops and appends) and takes ANY uint32 source;
+literal_dequeue() is one dequeue of it on a full queue image, from any stream position (tests that start from a given state);
 philox4x32_10() is the device's generator, so that model and kernel can be compared pick for pick."""
 import numpy as np
 
@@ -57,6 +58,22 @@ def tf_queue_batches(n_records, capacity, batch, min_after_dequeue, num_batches,
             queue.pop()
         out.append(picks)
     return np.asarray(out, np.int64)
+
+
+def literal_dequeue(queue, batch, r, stream_pos, n_records):
+    """ONE dequeue of the literal queue from ANY state: `queue` is the full image (capacity record indices), r the batch's
+    uint32 draws, stream_pos the number of records enqueued so far.  RandomShuffleQueue::TryDequeueMany -- index = r_k mod
+    size; emit queue[index]; queue[index] = queue[size - 1]; size -= 1 -- then the freed slots at the back refilled from
+    the stream in order.  Returns (picks, new queue); the stream position afterwards is stream_pos + batch."""
+    new, size, picks = [int(v) for v in queue], len(queue), []
+    for k in range(batch):
+        i = int(r[k]) % size
+        picks.append(new[i])
+        new[i] = new[size - 1]
+        size -= 1
+    for t in range(batch):
+        new[size + t] = (stream_pos + t) % n_records
+    return picks, new
 
 
 def parallel_dequeue(queue, batch, r, stream_pos, n_records):
