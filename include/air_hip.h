@@ -1087,6 +1087,84 @@ int air_glyph_jitter_prepare(const air_glyph_jitter_t* a);
 /* bytes of dynamic LDS per workgroup, or AIR_EINVAL / AIR_ELIMIT for a (gd, od) the entry point refuses -- no GPU is touched */
 int64_t air_glyph_jitter_lds(int gd, int od);
 
+/* ---- handwriting bank: base glyphs distorted into MNIST's geometry (additive to ABI 6) ------------------------------------
+ * ONE launch that turns base glyphs (whole gd x gd planes, values in [0, 1]) into V distorted variants: an elastic field
+ * (Simard et al. 2003) and an affine map, a stroke of drawn width, an ink ramp, the box fitted to `ink` pixels a side and the
+ * glyph put by its centre of mass into an od x od frame -- MNIST's 20-in-28 layout at ink = 20, od = 28.  The outputs have the
+ * shapes and the meaning of air_glyph_jitter's: a bank the scene source draws from.  multi_mnist.DeviceHandwritingBank is
+ * the caller; it makes taps and field_gain.
+ *
+ * One variant, by one workgroup of 256 threads, its planes in LDS; every intermediate is fp64 unless said otherwise, the build
+ * has -ffp-contract=off, and tests/glyph_distort_cases.py restates every operation below.  generation = *counter (null: 0).
+ * Parameter stream: draw j of variant v is word j & 3 of Philox4x32-10(key = (seed low, seed high), counter = (v, j >> 2,
+ * (uint32_t)generation, 0x47445350)).  Word 0 picks the base glyph g = umulhi(word, G).  A real takes two words,
+ * u = ((a >> 5) * 2^26 + (b >> 6)) / 2^53, value = lo + (hi - lo) * u.  In this order, each only when its bounds are not
+ * neutral: angle in [-max_ang, max_ang] (degrees; when max_ang != 0), shear k in [-max_shear, max_shear] (when max_shear !=
+ * 0), sx then sy in [min_scale, max_scale] (when one of the two is not 1.0), and one word for the stroke,
+ * n = min_stroke + umulhi(word, max_stroke - min_stroke + 1) (when the two are not both 0).
+ * Field stream (only when field_gain != 0): element j = plane * gd * gd + y * gd + x of the two planes is word j & 3 of
+ * Philox4x32-10(same key, counter = (v, j >> 2, (uint32_t)generation, 0x47445346)); value = ((word >> 8) + 0.5) * 2^-23 - 1.
+ *
+ *   1. Field.  Each plane is smoothed along axis 0, then along axis 1: out[i] = sum over t = 0 .. 2 radius, ascending, of
+ *      taps[t] * in[i + t - radius], the terms whose pixel lies outside the plane left out (zeros outside); the axis-1 sums are
+ *      multiplied by field_gain.  Plane 0 displaces y, plane 1 displaces x.  With taps a normalised Gaussian and
+ *      field_gain = alpha / ((1 / sqrt 3) * sum taps^2) the field has standard deviation alpha pixels away from the border.
+ *   2. Warp.  c, s = cos, sin of the angle (the angle less its nearest multiple of 90 is exact, sincospi of that / 180, the
+ *      quadrant put back by sign and swap -- air_glyph_jitter's).  isy = 1 / sy, isx = 1 / sx; A = R (1 k; 0 1) diag(isy, isx)
+ *      with R = (c s; -s c) over (y, x):  a00 = c isy, a01 = (c k + s) isx, a10 = (-s) isy, a11 = ((-s) k + c) isx.
+ *      ctr = (gd - 1) / 2, dy = y - ctr, dx = x - ctr;  qy = (ctr + (a00 dy + a01 dx)) + field0[y, x],
+ *      qx = (ctr + (a10 dy + a11 dx)) + field1[y, x] (the field terms only when field_gain != 0).  fy = floor(qy), ty = qy - fy,
+ *      uy = 1 - ty, likewise in x; v00 .. v11 the base plane at (fy, fx), (fy, fx + 1), (fy + 1, fx), (fy + 1, fx + 1), zero
+ *      outside the plane;  value = float32(((v00 (uy ux) + v01 (uy tx)) + v10 (ty ux)) + v11 (ty tx)).
+ *   3. Stroke.  |n| passes, each behind a barrier: every pixel becomes the maximum (n > 0) or the minimum (n < 0) of itself
+ *      and its upper, lower, left and right neighbours, those outside the plane left out.
+ *   4. Ramp.  t = (value - lo) / (hi - lo), clipped to [0, 1], rounded to float32; values < 0.05 become 0.  h x w = the box of
+ *      what is left; status 1 when nothing is.
+ *   5. Fit.  f = ink / max(h, w); h' = max(1, floor(h f + 0.5)), w' likewise.  Area average along axis 0 (h -> h'), then along
+ *      axis 1 (w -> w'): with r = h / h', out[i] = (sum over j = 0 .. h - 1, ascending, of in[j] * max(0, min(j + 1, (i + 1) r)
+ *      - max(j, i r))) / r.  The axis-1 result is rounded to float32, values < 0.05 become 0, and the box of what is left is
+ *      taken again (it may be smaller than h' x w'; status 1 when nothing is left): from here on h' x w' is that box.
+ *   6. Centre.  Per row of the box, m_r = sum of v and mx_r = sum of v * x, x ascending from the box's left edge (x = 0);
+ *      then m = sum m_r, my = sum m_r * r, mx = sum mx_r, rows ascending; cy = my / m, cx = mx / m.
+ *      y0 = clamp(floor((od - 1) / 2 - cy + 0.5), 0, od - h'), x0 likewise.
+ *
+ * Outputs (every element is written): bank [V, od * od] float32, the glyph with its box's corner at (x0, y0), +0 elsewhere;
+ * bank_crops [V, 4] = (x0, y0, w', h'); source [V], the base glyph; params [V, 8] fp64: angle, shear, sx, sy, c, s, n, f
+ * (0, 0, 1, 1, 1, 0, 0 for what was not drawn; f = 0 when the ramp left nothing); status [V]: 0 usable, 1 nothing left
+ * after the ramp or the fit, 2 a box larger than od (ink <= od rules it out; checked before the frame is written).  A
+ * non-zero status writes an all-zero frame and an all-zero box: the scene kernel restarts a scene that draws it.
+ *
+ * Limits, answered on the host before any HIP call: an invalid size before a limit, a limit before a null pointer, a null
+ * pointer before the alignment.  AIR_EINVAL: a null descriptor; V, G, gd, od or ink < 1; radius < 0; ink > od; field_gain or
+ * a real bound that is not finite; min_scale > max_scale; min_stroke > max_stroke; lo >= hi; min_scale <= 0; then a null
+ * pointer (counter may be null).  AIR_ELIMIT: gd > AIR_DISTORT_MAX_PLANE; od > AIR_SCENE_MAX_GLYPH; radius >
+ * AIR_DISTORT_MAX_RADIUS (a tap line may be wider than the plane); |max_ang| > 180; a stroke bound outside +-
+ * AIR_DISTORT_MAX_STROKE.  AIR_EALIGN: bank_crops not 16-byte aligned; params or taps not 8-byte aligned.
+ * Dynamic LDS: air_glyph_distort_lds(gd, od, radius) = 3 * 8 S S (field planes) + 8 (2 radius + 1) (taps) + 4 S S (the base
+ * plane, then the fitted glyph) + 32 (boxes) with S = max(gd, od): 45 864 bytes at the limits, 45 224 at the preset (gd 40,
+ * radius 24) -- below 48 KiB, so air_glyph_distort_prepare is the checks (and would take the grant if the limits grew). */
+typedef struct {
+    const float* glyphs;                 /* [G, gd * gd]                                                                */
+    const int64_t* counter;              /* nullable: one device int64, the bank generation                             */
+    const double* taps;                  /* device [2 * radius + 1]                                                     */
+    float* bank;                         /* out [V, od * od]                                                            */
+    int32_t* bank_crops;                 /* out [V, 4]                                                                  */
+    int32_t* source;                     /* out [V]                                                                     */
+    double* params;                      /* out [V, 8]                                                                  */
+    int32_t* status;                     /* out [V]                                                                     */
+    int32_t V, G, gd, od, ink, radius, min_stroke, max_stroke;
+    double field_gain, max_ang, max_shear, min_scale, max_scale, lo, hi;
+    uint64_t seed;
+} air_glyph_distort_t;
+#define AIR_DISTORT_MAX_PLANE 40
+#define AIR_DISTORT_MAX_RADIUS 64
+#define AIR_DISTORT_MAX_STROKE 4
+int air_glyph_distort(const air_glyph_distort_t* a, void* stream);
+/* the checks and the LDS grant of air_glyph_distort without its launch */
+int air_glyph_distort_prepare(const air_glyph_distort_t* a);
+/* bytes of dynamic LDS per workgroup, or AIR_EINVAL / AIR_ELIMIT for sizes the entry point refuses -- no GPU is touched */
+int64_t air_glyph_distort_lds(int gd, int od, int radius);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,6 +224,19 @@ class GlyphJitter(C.Structure):
                 ("min_ang", C.c_double), ("max_ang", C.c_double), ("seed", C.c_uint64)]
 
 
+DISTORT_MAX_PLANE, DISTORT_MAX_RADIUS, DISTORT_MAX_STROKE = 40, 64, 4
+
+
+class GlyphDistort(C.Structure):
+    """air_glyph_distort_t: base glyphs (whole planes) and the host-made Gaussian taps in, a bank of V distorted variants
+    (frames, boxes, base glyph, drawn parameters, status) out; counter is a nullable device int64, the bank generation"""
+    _fields_ = [("glyphs", _p), ("counter", _p), ("taps", _p), ("bank", _p), ("bank_crops", _p), ("source", _p),
+                ("params", _p), ("status", _p), ("V", _i), ("G", _i), ("gd", _i), ("od", _i), ("ink", _i), ("radius", _i),
+                ("min_stroke", _i), ("max_stroke", _i),
+                ("field_gain", C.c_double), ("max_ang", C.c_double), ("max_shear", C.c_double), ("min_scale", C.c_double),
+                ("max_scale", C.c_double), ("lo", C.c_double), ("hi", C.c_double), ("seed", C.c_uint64)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -307,6 +320,9 @@ _SIGNATURES = {
     "air_glyph_jitter": (C.c_int, [C.POINTER(GlyphJitter), _p]),
     "air_glyph_jitter_prepare": (C.c_int, [C.POINTER(GlyphJitter)]),
     "air_glyph_jitter_lds": (C.c_int64, [C.c_int, C.c_int]),
+    "air_glyph_distort": (C.c_int, [C.POINTER(GlyphDistort), _p]),
+    "air_glyph_distort_prepare": (C.c_int, [C.POINTER(GlyphDistort)]),
+    "air_glyph_distort_lds": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -95,6 +95,7 @@ KERNEL_NAMES = {
     "air_philox_fill": "philox_fill_kernel",
     "air_scene_records": "scene_records_kernel",
     "air_render": "render_kernel",
+    "air_glyph_distort": "glyph_distort_kernel",                        # (multi_mnist.DeviceHandwritingBank launches it)
 }
 
 

@@ -15,12 +15,16 @@ follows the reference.
   python multi_mnist.py [--max-digits 2] [--images-per-digit 20000] [--test-set-size 1000]
                         [--digit-gap 0] [--canvas-margin 0] [--bg-path X --bg-max-intensity 1.0]
   python multi_mnist.py --device 60000 [--seed 0] [...]     the same files, composed on the GPU (DeviceSceneSource; with
-                        --min-width-scale ... --max-rotation-angle from a DeviceGlyphBank remade for every batch)
+                        --min-width-scale ... --max-rotation-angle from a DeviceGlyphBank remade for every batch; with
+                        --glyph-style mnist-like from a DeviceHandwritingBank remade for every batch)
 
 DeviceSceneSource is that default path as device work: one HIP launch composes a fresh batch of canvases into the train
 model's input buffers (training.py --online-data), eagerly or inside a captured replay.  DeviceGlyphBank is the scale and
 rotation jitter (:113-135) as device work: one launch makes a bank of jittered variants of the glyphs, with scipy's order-5
-spline arithmetic, and a scene source built on the bank draws from those.
+spline arithmetic, and a scene source built on the bank draws from those.  DeviceHandwritingBank is a bank of another kind
+(--glyph-style mnist-like): the 8x8 handwritten digits up-sampled to 40x40 (load_base_glyphs) and distorted on the device
+into MNIST's geometry -- elastic field, affine map, stroke width, ink ramp, a 20-pixel box centred by its centre of mass in a
+28x28 frame -- by one launch per bank (air_glyph_distort).
 """
 import argparse
 import gzip
@@ -64,6 +68,16 @@ def load_glyphs():
         o = (IMAGE_SIZE - big.shape[0]) // 2
         out[i, o:o + big.shape[0], o:o + big.shape[1]] = big
     return out.reshape(-1, IMAGE_SIZE * IMAGE_SIZE), d["labels"].astype(np.int64), "digits8x8"
+
+
+def load_base_glyphs(side=40):
+    """[n, side * side] float32 in [0, 1] + labels: the committed 8x8 handwritten digits up-sampled (cubic) to side x side
+    and clipped -- the base planes of DeviceHandwritingBank, which gives them stroke, ramp, size and place itself"""
+    import scipy.ndimage as nd
+    d = np.load(os.path.join(HERE, "data", "digits8x8.npz"))
+    small = d["images"].astype(np.float32) / 16.0
+    out = np.stack([np.clip(nd.zoom(g, side / 8.0, order=3), 0.0, 1.0) for g in small]).astype(np.float32)
+    return out.reshape(-1, side * side), d["labels"].astype(np.int64)
 
 
 def read_image(path, max_intensity):
@@ -419,6 +433,96 @@ class DeviceGlyphBank:
         return bool(np.any((w <= canvas_dim) & (h <= canvas_dim)))
 
 
+# The handwriting bank's starting values (a CPU prototype of the recipe read as MNIST at a glance with them): 40-pixel base
+# planes, a 20-pixel box in a 28-pixel frame, an elastic field of sigma 6 / alpha 1.5 base pixels (Simard's 4 / 34 at 28
+# pixels is a far stronger field; this one is judged at 40 and halved by the fit), +-12 degrees, shear +-0.2, scale
+# 0.85 .. 1.15 per axis, one pass of erosion or dilation at the most, and an ink ramp that saturates the strokes.
+MNIST_LIKE = dict(side=40, ink=20, od=28, sigma=6.0, alpha=1.5, max_ang=12.0, max_shear=0.2, min_scale=0.85, max_scale=1.15,
+                  min_stroke=-1, max_stroke=1, lo=0.3, hi=0.7)
+
+
+def gaussian_taps(sigma, radius=None):
+    """-> (taps [2 R + 1] float64, a normalised Gaussian; R = int(4 sigma + 0.5) unless given)"""
+    R = int(4.0 * float(sigma) + 0.5) if radius is None else int(radius)
+    x = np.arange(-R, R + 1, dtype=np.float64)
+    t = np.exp(-0.5 * (x / float(sigma)) ** 2)
+    return t / t.sum(), R
+
+
+class DeviceHandwritingBank:
+    """Base glyphs distorted into MNIST's geometry on the device, as a bank: ONE launch (air_glyph_distort, one workgroup per
+    variant) turns the whole planes `base_glyphs` [G, gd * gd] (values in [0, 1], gd <= 40) into `variants` glyphs -- base
+    glyph, angle, shear, two scales and stroke passes drawn per variant, an elastic displacement field of standard deviation
+    `alpha` base pixels smoothed by a Gaussian of `sigma` -- each with its box fitted to `ink` pixels a side and put by its
+    centre of mass into an od x od frame.  include/air_hip.h states every operation; tests/glyph_distort_cases.py restates
+    them in numpy, bit for bit.  The taps (a normalised Gaussian of radius int(4 sigma + 0.5), or `radius`) and the field's
+    gain alpha / ((1 / sqrt 3) * sum taps^2) are made here, on the host.
+
+    The attributes and methods are DeviceGlyphBank's, and DeviceSceneSource takes either: refresh() (the launch, then the
+    generation counter advanced by one, on the current stream), bank [V, od * od], bank_crops [V, 4] = (x0, y0, w, h) inside
+    the frame, source [V], params [V, 8] (angle, shear, sx, sy, cos, sin, stroke passes, fit factor), status [V] (0 usable,
+    1 nothing left after the ramp or the fit, 2 larger than od), counter, labels(), status_counts(), fits()."""
+
+    def __init__(self, base_glyphs, variants, od=28, ink=20, seed=0, max_ang=0.0, max_shear=0.0, min_scale=1.0, max_scale=1.0,
+                 min_stroke=0, max_stroke=0, lo=0.0, hi=1.0, sigma=1.0, alpha=0.0, radius=None, device=None):
+        import ctypes as C
+        import torch
+        from air import _hip as H
+        self._C, self._torch, self._H = C, torch, H
+        g, gd = _glyph_array(base_glyphs)
+        if g.max() > 1:
+            raise ValueError("glyph values must be <= 1")
+        if not (np.isfinite(sigma) and sigma > 0 and np.isfinite(alpha)):
+            raise ValueError("sigma must be positive, sigma and alpha finite")
+        self.variants, self.gd, self.od, self.ink = int(variants), gd, int(od), int(ink)
+        self.bounds = dict(max_ang=float(max_ang), max_shear=float(max_shear), min_scale=float(min_scale),
+                           max_scale=float(max_scale), min_stroke=int(min_stroke), max_stroke=int(max_stroke), lo=float(lo),
+                           hi=float(hi), sigma=float(sigma), alpha=float(alpha))
+        taps, self.radius = gaussian_taps(sigma, radius)
+        self.field_gain = float(alpha) / ((1.0 / np.sqrt(3.0)) * float(np.sum(taps * taps))) if alpha != 0.0 else 0.0
+        V = self.variants
+        # the argument checks first, before anything is allocated: they need no device (the pointers are placeholders that
+        # the checks only compare with null and test for alignment)
+        b = self.bounds
+        self._a = H.GlyphDistort(16, None, 16, 16, 16, 16, 16, 16, V, len(g), gd, self.od, self.ink, self.radius,
+                                 b["min_stroke"], b["max_stroke"], self.field_gain, b["max_ang"], b["max_shear"], b["min_scale"],
+                                 b["max_scale"], b["lo"], b["hi"], int(seed) & 0xFFFFFFFFFFFFFFFF)
+        H.check(H.lib().air_glyph_distort_prepare(C.byref(self._a)), "air_glyph_distort_prepare")
+        if device is None and not torch.cuda.is_available():
+            raise H.AirHipError("DeviceHandwritingBank: needs a GPU (no CPU fallback)")
+        dev = self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise H.AirHipError("DeviceHandwritingBank: device must be a GPU (no CPU fallback)")
+        self.glyphs = torch.tensor(g, device=dev)
+        self.taps = torch.tensor(taps, dtype=torch.float64, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)           # the bank generation (device: replays move it)
+        self.bank = torch.zeros(V, self.od * self.od, device=dev)
+        self.bank_crops = torch.zeros(V, 4, dtype=torch.int32, device=dev)
+        self.source = torch.zeros(V, dtype=torch.int32, device=dev)
+        self.params = torch.zeros(V, 8, dtype=torch.float64, device=dev)
+        self.status = torch.ones(V, dtype=torch.int32, device=dev)             # (nothing is usable before the first refresh)
+        for k in ("glyphs", "taps", "counter", "bank", "bank_crops", "source", "params", "status"):
+            setattr(self._a, k, getattr(self, k).data_ptr())
+        with torch.cuda.device(dev):
+            H.check(H.lib().air_glyph_distort_prepare(C.byref(self._a)), "air_glyph_distort_prepare")
+
+    def refresh(self):
+        H = self._H
+        s = H.stream(self.device)
+        H.check(H.lib().air_glyph_distort(self._C.byref(self._a), s), "air_glyph_distort")
+        H.check(H.lib().air_scene_source_advance(self.counter.data_ptr(), 1, s), "air_scene_source_advance")
+
+    labels = DeviceGlyphBank.labels
+    status_counts = DeviceGlyphBank.status_counts
+
+    def fits(self, canvas_dim, margin):
+        """whether a usable variant, whose larger side is at most `ink` pixels, fits the canvas"""
+        return self.ink + 2 * margin <= canvas_dim
+
+
+_BANKS = (DeviceGlyphBank, DeviceHandwritingBank)
+
+
 class DeviceSceneSource:
     """generate_multi_image (:82-183) on the device, default path only (pixel overlap with the optional gap buffer, margin,
     background): every batch is COMPOSED by one launch (air_scene_source_compose, one workgroup per canvas) straight into
@@ -436,8 +540,8 @@ class DeviceSceneSource:
     sampler, -1 = given up after max_restarts: an empty canvas with 0 digits).  gave_up(): a device scalar, the number of
     such canvases over all batches so far; nothing here synchronises.
 
-    `glyphs` may be a DeviceGlyphBank instead: the source then draws from the bank's jittered variants (its frames and crop
-    boxes, gd = the bank's od; meta()['indices'] are bank indices, bank.source maps them to base glyphs), and
+    `glyphs` may be a DeviceGlyphBank or a DeviceHandwritingBank instead: the source then draws from the bank's variants (its
+    frames and crop boxes, gd = the bank's od; meta()['indices'] are bank indices, bank.source maps them to base glyphs), and
     graph_hooks(steps) enqueues bank.refresh() in front of the first compose of every replay.  next_batch() does not
     refresh: the caller decides when the bank turns over.
 
@@ -465,7 +569,7 @@ class DeviceSceneSource:
         H.require_device(out_digits, "out_digits", "DeviceSceneSource")
         self._C, self._torch, self._H = C, torch, H
         dev = self.device = out_images.device
-        self.bank = glyphs if isinstance(glyphs, DeviceGlyphBank) else None
+        self.bank = glyphs if isinstance(glyphs, _BANKS) else None
         if self.bank is not None:
             if self.bank.device != dev:
                 raise ValueError("the glyph bank lives on %s, out_images on %s" % (self.bank.device, dev))
@@ -559,23 +663,41 @@ class DeviceSceneSource:
         return self._gave_up.sum()
 
 
+def handwriting_bank(variants, seed, device, **override):
+    """the DeviceHandwritingBank of the MNIST_LIKE preset on load_base_glyphs -> (bank, base labels)"""
+    kw = dict(MNIST_LIKE, **override)
+    base, labels = load_base_glyphs(kw.pop("side"))
+    return DeviceHandwritingBank(base, variants, seed=seed, device=device, **kw), labels
+
+
 def compose_on_device(num_images, max_digits=2, canvas_dim=CANVAS_SIZE, bg=None, gap=0, margin=0, seed=0, batch_size=1000,
-                      variants=4096, **generator_options):
+                      variants=4096, glyph_style="standin", **generator_options):
     """`num_images` canvases from DeviceSceneSource (cuda:0), with the metadata generate_strata keeps: -> (dict of numpy
     arrays images [n, canvas_dim^2], digits, indices, positions, boxes, labels [n, max_digits] (slots behind digits[i] are
     0) and status [n], glyph source).  generator_options: scale / rotation bounds that are not neutral put a DeviceGlyphBank
     of `variants` jittered glyphs under the source, refreshed before every batch (`indices` are then indices into that
-    batch's bank; `labels` are mapped through it); what the device does not compose is refused by the source."""
+    batch's bank; `labels` are mapped through it); what the device does not compose is refused by the source.
+    glyph_style "mnist-like": the digits come from a DeviceHandwritingBank of the MNIST_LIKE preset instead, remade before
+    every batch in the same way; it has distortions of its own, so it is refused together with scale / rotation bounds."""
     import torch
-    glyphs, labels, source = load_glyphs()
+    if glyph_style not in ("standin", "mnist-like"):
+        raise ValueError("glyph_style must be 'standin' or 'mnist-like'")
     dev = torch.device("cuda", 0)
     B = min(batch_size, num_images)
     images = torch.zeros(B, canvas_dim * canvas_dim, device=dev)
     digits = torch.zeros(B, dtype=torch.int32, device=dev)
     jitter = {k: float(generator_options.pop(k)) for k in JITTER_NEUTRAL if k in generator_options}
-    bank = None
-    if any(v != JITTER_NEUTRAL[k] for k, v in jitter.items()):
-        bank = DeviceGlyphBank(glyphs, variants, seed=seed, device=dev, **jitter)
+    bank = glyphs = None
+    jittered = any(v != JITTER_NEUTRAL[k] for k, v in jitter.items())
+    if glyph_style == "mnist-like":
+        if jittered:
+            raise ValueError("glyph_style='mnist-like' distorts the glyphs itself: leave the scale / rotation bounds neutral")
+        bank, labels = handwriting_bank(variants, seed, dev)
+        source = "digits8x8, mnist-like"
+    else:
+        glyphs, labels, source = load_glyphs()
+        if jittered:
+            bank = DeviceGlyphBank(glyphs, variants, seed=seed, device=dev, **jitter)
     src = DeviceSceneSource(glyphs if bank is None else bank, B, images, digits, canvas_dim=canvas_dim, max_digits=max_digits,
                             margin=margin, gap=gap, bg=bg, seed=seed, **generator_options)
     out = {k: [] for k in ("images", "digits", "indices", "positions", "boxes", "status", "labels")}
@@ -653,15 +775,23 @@ if __name__ == "__main__":
                         help="compose N canvases on the GPU instead (DeviceSceneSource: 0 .. --max-digits digits each, drawn "
                              "uniformly) and write them with their metadata to common.npz / test.npz")
     parser.add_argument("--seed", type=int, default=0, help="--device: the seed of the scene source")
+    parser.add_argument("--glyph-style", default="standin", choices=["standin", "mnist-like"],
+                        help="--device: mnist-like draws the digits from a DeviceHandwritingBank (the 8x8 digits up-sampled to "
+                             "40 pixels and distorted on the device into a 20-pixel box centred in a 28-pixel frame)")
     args = parser.parse_args()
+    jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
+                  max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
+    if args.glyph_style != "standin" and not args.device:
+        parser.error("--glyph-style %s is made on the device: give --device N" % args.glyph_style)
+    if args.glyph_style == "mnist-like" and jitter != JITTER_NEUTRAL:
+        parser.error("--glyph-style mnist-like distorts the glyphs itself: leave the scale / rotation flags neutral")
     os.makedirs(MULTI_MNIST_FOLDER, exist_ok=True)
     bg = read_image(args.bg_path, args.bg_max_intensity) if args.bg_path else None
     if args.device:
-        jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
-                      max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
         ds, source = compose_on_device(args.device, max_digits=args.max_digits, canvas_dim=args.canvas_size, bg=bg,
                                        gap=args.digit_gap, margin=args.canvas_margin, seed=args.seed,
-                                       use_pixel_overlap=not args.use_bounding_box_overlap, **jitter)
+                                       use_pixel_overlap=not args.use_bounding_box_overlap,
+                                       glyph_style=args.glyph_style, **jitter)
         T = min(args.test_set_size, args.device)
         np.savez(MULTI_MNIST_FOLDER + "common.npz", **{k: v[T:] for k, v in ds.items()})
         np.savez(MULTI_MNIST_FOLDER + "test.npz", **{k: v[:T] for k, v in ds.items()})

@@ -23,6 +23,9 @@ batches were composed and how many canvases the bounded rejection sampler gave u
 rotation flags (--min-width-scale ... --max-rotation-angle) the digits come from a bank of --jitter-bank jittered glyphs
 (multi_mnist.DeviceGlyphBank), remade on the device every --graph-steps steps -- by the replay itself when there is one, so
 the batches are the same with and without --no-graph; the last line then also counts the banks and the unusable variants.
+--glyph-style mnist-like takes the digits from a multi_mnist.DeviceHandwritingBank instead (the 8x8 handwritten digits
+distorted on the device into MNIST's 20-in-28 geometry), remade at the same steps; the evaluation set is then 1 000 scenes
+composed once on the device from a bank with a seed of its own, and the host generator does not run at all.
 """
 import argparse
 import json
@@ -33,7 +36,8 @@ import time
 import numpy as np
 import torch
 
-from multi_mnist import JITTER_NEUTRAL, DeviceGlyphBank, DeviceSceneSource, ShuffleBatchQueue, generate_dataset, load_glyphs, shift_zero_digits_images
+from multi_mnist import (JITTER_NEUTRAL, DeviceGlyphBank, DeviceSceneSource, ShuffleBatchQueue, generate_dataset, handwriting_bank,
+                         load_glyphs, shift_zero_digits_images)
 from air.air_model import AIRModel
 
 EPOCHS = 300
@@ -49,6 +53,8 @@ NUM_IMAGES_TO_SAVE = 60
 
 MIN_AFTER_DEQUEUE = 10000                 # multi_mnist.py:246-247 (capacity = this + 10 * batch)
 DEFAULT_READER_THREADS = 4
+ONLINE_TRAIN_SET_SIZE = 3 * 20000 - 1000   # generate_dataset's defaults: what an epoch counts where there is no train set
+TEST_SET_SIZE = 1000
 DEFAULT_RESULTS_FOLDER = "air_results"
 TRAIN_DATA_FILE = "multi_mnist_data/common.npz"
 TEST_DATA_FILE = "multi_mnist_data/test.npz"
@@ -83,6 +89,19 @@ def load_data(bg_path="", bg_max_intensity=1.0):
     print("Generating multi-digit dataset in memory (multi_mnist.py defaults)...")
     ds = generate_dataset(bg=load_background(bg_path, bg_max_intensity))
     return ds["train_images"], ds["train_digits"], ds["test_images"], ds["test_digits"]
+
+
+def device_test_set(dev, variants, seed, max_digits, margin, gap, bg):
+    """--glyph-style mnist-like: TEST_SET_SIZE scenes composed once on the device from one handwriting bank with a seed of its
+    own -> (images, digits) as numpy arrays; the bank and the source are dropped"""
+    images = torch.zeros(TEST_SET_SIZE, CANVAS_SIZE ** 2, device=dev)
+    digits = torch.zeros(TEST_SET_SIZE, dtype=torch.int32, device=dev)
+    bank, _ = handwriting_bank(variants, 0x54455354 + seed, dev)
+    source = DeviceSceneSource(bank, TEST_SET_SIZE, images, digits, canvas_dim=CANVAS_SIZE, max_digits=max_digits, margin=margin,
+                               gap=gap, bg=bg, seed=0x5445535453 + seed)
+    bank.refresh()
+    source.next_batch()
+    return images.cpu().numpy(), digits.cpu().numpy()
 
 
 class SummaryWriter:
@@ -265,7 +284,19 @@ def main():
     parser.add_argument("--jitter-bank", type=int, default=4096, metavar="V",
                         help="--online-data with jitter: digits are drawn from a bank of V jittered glyphs made on the device "
                              "(multi_mnist.DeviceGlyphBank), a fresh bank every --graph-steps steps")
+    parser.add_argument("--glyph-style", default="standin", choices=["standin", "mnist-like"],
+                        help="--online-data: mnist-like draws the digits from a bank of --jitter-bank handwritten digits "
+                             "distorted on the device into MNIST's geometry (multi_mnist.DeviceHandwritingBank: a 20-pixel "
+                             "box centred in a 28-pixel frame), a fresh bank every --graph-steps steps; the evaluation set is "
+                             "composed on the device too")
     args = parser.parse_args()
+    jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
+                  max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
+    mnist_like = args.glyph_style == "mnist-like"
+    if mnist_like and not args.online_data:
+        parser.error("--glyph-style mnist-like is made on the device: give --online-data")
+    if mnist_like and jitter != JITTER_NEUTRAL:
+        parser.error("--glyph-style mnist-like distorts the glyphs itself: leave the scale / rotation flags neutral")
     if args.cnn and args.tensorboard:
         parser.error("--tensorboard writes histogram summaries, which a --cnn model does not have yet")
 
@@ -286,7 +317,11 @@ def main():
 
     dev = torch.device("cuda", 0)
     print("Creating input pipeline...")
-    tr_im, tr_dg, te_im, te_dg = load_data(args.bg_path, args.bg_max_intensity)
+    if mnist_like:                                                   # no host generator: the test set is device work too
+        te_im, te_dg = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin,
+                                       args.digit_gap, load_background(args.bg_path, args.bg_max_intensity))
+    else:
+        tr_im, tr_dg, te_im, te_dg = load_data(args.bg_path, args.bg_max_intensity)
     te_im, te_dg = shift_zero_digits_images(te_im, te_dg)
     if not args.online_data:
         train_images = torch.tensor(tr_im, device=dev)
@@ -327,7 +362,7 @@ def main():
             )
         )
     train_model, test_model = models
-    n_train = tr_im.shape[0]
+    n_train = ONLINE_TRAIN_SET_SIZE if mnist_like else tr_im.shape[0]
     total = args.iterations if args.iterations > 0 else (n_train // BATCH_SIZE) * EPOCHS
 
     # The input queue is device work too (read_and_decode, multi_mnist.py:228-249): the RandomShuffleQueue's resident
@@ -338,9 +373,9 @@ def main():
     # glyphs (same hooks: next_batch() eagerly, graph_hooks() inside the replay).
     bank = None
     if args.online_data:
-        jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
-                      max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
-        if jitter != JITTER_NEUTRAL:
+        if mnist_like:
+            bank, _ = handwriting_bank(args.jitter_bank, 0x4A4954 + args.seed, dev)
+        elif jitter != JITTER_NEUTRAL:
             bank = DeviceGlyphBank(load_glyphs()[0], args.jitter_bank, seed=0x4A4954 + args.seed, device=dev, **jitter)
         batches = DeviceSceneSource(load_glyphs()[0] if bank is None else bank, BATCH_SIZE, train_data, train_targets, canvas_dim=CANVAS_SIZE,
                                     max_digits=args.online_max_digits, margin=args.canvas_margin, gap=args.digit_gap,
