@@ -1165,6 +1165,82 @@ int air_glyph_distort_prepare(const air_glyph_distort_t* a);
 /* bytes of dynamic LDS per workgroup, or AIR_EINVAL / AIR_ELIMIT for sizes the entry point refuses -- no GPU is touched */
 int64_t air_glyph_distort_lds(int gd, int od, int radius);
 
+/* ---- localisation metrics (additive to ABI 6) ---------------------------------------------------------------------------
+ * The attention boxes of an inference pass scored against the ground-truth boxes of its images: box IoU, recall, cover,
+ * centre distance and the confusion matrix of the counts.  air/metrics.py (Localization) is the caller; the first seven
+ * fields are those of air_embed_collect_t, in its layouts, so one set of device arrays serves both.
+ *
+ * All arithmetic is fp64 in exactly the order written here (the translation unit has -ffp-contract=off), and
+ * tests/localization_cases.py restates every operation below.  C = canvas_size; n_i = run_digits[i] clamped to [0, T];
+ * c_i = gt_count[i] clamped to [0, G]; i < k.
+ *
+ * Inferred box of object t < n_i of image i.  q = (C - 1.001) / 2.0 (the transformer's pixel map, transformer.py:75-76, in
+ * fp64); (s, x, y) = att[t][i][AIR_ATT_S, AIR_ATT_X, AIR_ATT_Y] widened;
+ *   l1 = (x - s + 1.0) * q     r1 = (x + s + 1.0) * q + 1.0     t1 = (y - s + 1.0) * q     b1 = (y + s + 1.0) * q + 1.0
+ * (the sample points of the window span the pixel indices l1 .. r1 - 1; pixel j is the cell [j, j + 1)), then every edge v
+ * is clipped:  v < 0 ? 0 : (v > C ? C : v)  -- a NaN passes through.  a_inf = (r1 - l1) * (b1 - t1).
+ * Ground-truth box of digit g < c_i: (x, y) = gt_positions[i][g], (w, h) = gt_boxes[i][g], widened one by one:
+ *   l2 = x     r2 = x + w     t2 = y     b2 = y + h     a_gt = w * h
+ * Pair (g, t):  iw = min(r1, r2) - max(l1, l2),  ih = min(b1, b2) - max(t1, t2)  (min(a, b) = a < b ? a : b, max alike with
+ * >).  When iw > 0 && ih > 0:  inter = iw * ih,  uni = a_inf + a_gt - inter,  and when uni > 0:  iou = inter / uni,
+ * cover = inter / a_gt.  In every other case (a NaN anywhere among them) iou = cover = 0.
+ * dist, the reference's centre distance in transformer units (embeddings.py:39-44, 113-114, as air_embed_collect has it):
+ *   cx = ((x + x + w) - 1.0) / 2.0 (an int32 sum, widened),  x1 = cx / ((C - 1) / 2.0) - 1.0,  cy / y1 alike,
+ *   dist = sqrt((xa - x1) * (xa - x1) + (ya - y1) * (ya - y1)),  (xa, ya) = att[t][i][AIR_ATT_X, AIR_ATT_Y] widened.
+ *
+ * Match, per image: greedy on IoU, at most min(n_i, c_i) rounds.  A round scans the pairs of unused digits and unused
+ * objects, g outer and t inner, and keeps the first pair whose iou is strictly greater than the best so far (the best
+ * starts at 0): a tie goes to the smaller g, then the smaller t, and a pair with iou 0 is never taken.  The round takes the
+ * kept pair (digit and object are used from then on); the first round that keeps none ends the image.
+ * match[i][g] = the object taken with digit g, or -1; iou[i][g] = the iou of that pair, or 0.  g in [c_i, G) gets -1 and 0.
+ *
+ * Accumulators: the caller zeroes them once; a call ADDS, so the chunks of a data set add up.
+ *   counts[AIR_LOC_IMAGES] += k, [PRESENT] += sum c_i, [INFERRED] += sum n_i, [MATCHED] += taken pairs, [HITS] += taken
+ *   pairs with iou >= iou_threshold, [COUNT_CORRECT] += images with n_i == c_i, and the confusion matrix
+ *   counts[AIR_LOC_COUNTS + c_i * (T + 1) + n_i] += 1  ((G + 1) rows of (T + 1)).  Integer atomics: any order, the same sums.
+ *   sums[AIR_LOC_IOU / COVER / DIST] += the iou / cover / dist of the taken pairs, each of the three in this ONE order,
+ *   which depends on (k, G) alone:
+ *     1. image i:  p_i = (((+0.0 + v_0) + v_1) + ...) over its digits g = 0 .. c_i - 1 in order, v_g the value of digit g's
+ *        pair, an unmatched digit skipped;
+ *     2. group j = images [AIR_LOC_GROUP * j, AIR_LOC_GROUP * (j + 1)): its AIR_LOC_GROUP values p (+0.0 for an image >= k)
+ *        are folded by the adjacent pairwise tree -- v[m] = v[2 m] + v[2 m + 1], eight times, 256 values to one;
+ *     3. the batch total = (((+0.0 + group 0) + group 1) + ...) in group order;
+ *     4. sums[.] = incoming sums[.] + the batch total.
+ * No floating-point atomics: the same inputs (and incoming accumulators) give the same bits.
+ *
+ * Two launches on the caller's stream (a thread per image in workgroups of AIR_LOC_GROUP, which leave one partial triple
+ * per group in the workspace; one small fold), no synchronisation, no host read.  Rows >= k of att / run_digits are never
+ * read, the ground truth has k rows, and match / iou rows >= k are never written.  match and iou are nullable TOGETHER.
+ *
+ * Refusals, on the host before any HIP call, in this order.  AIR_EINVAL: a null descriptor; T, B, k or G < 1; k > B.
+ * AIR_ELIMIT: T > AIR_LOC_MAX_STEPS, G > AIR_LOC_MAX_DIGITS.  AIR_EINVAL: canvas_size < 2; iou_threshold not in (0, 1]
+ * (NaN included); a null att, run_digits, gt_count, gt_positions, gt_boxes, counts, sums or workspace; exactly one of
+ * match / iou null. */
+#define AIR_LOC_MAX_STEPS 16
+#define AIR_LOC_MAX_DIGITS 16
+#define AIR_LOC_GROUP 256
+enum { AIR_LOC_IMAGES = 0, AIR_LOC_PRESENT = 1, AIR_LOC_INFERRED = 2, AIR_LOC_MATCHED = 3, AIR_LOC_HITS = 4,
+       AIR_LOC_COUNT_CORRECT = 5, AIR_LOC_COUNTS = 6 };
+enum { AIR_LOC_IOU = 0, AIR_LOC_COVER = 1, AIR_LOC_DIST = 2, AIR_LOC_SUMS = 3 };
+typedef struct {
+    const float* att;                    /* [T, B, AIR_ATT_STRIDE] of the pass just run                                 */
+    const int32_t* run_digits;           /* [B] inferred object counts                                                  */
+    const int32_t* gt_count;             /* [k]                                                                         */
+    const int32_t* gt_positions;         /* [k, G, 2] (x, y): the memory layout of DeviceSceneSource.positions          */
+    const int32_t* gt_boxes;             /* [k, G, 2] (w, h)                                                            */
+    int32_t* match;                      /* out [k, G], nullable with iou                                               */
+    double* iou;                         /* out [k, G], nullable with match                                             */
+    int64_t* counts;                     /* in / out [AIR_LOC_COUNTS + (G + 1) * (T + 1)]                               */
+    double* sums;                        /* in / out [AIR_LOC_SUMS]                                                     */
+    int32_t T, B, k, G, canvas_size;
+    double iou_threshold;
+} air_localization_t;
+/* `workspace`: a device buffer of at least air_localization_workspace_bytes(T, B, k, G) bytes, 8-byte aligned (the
+ * per-group partial sums) */
+int air_localization(const air_localization_t* args, void* workspace, void* stream);
+/* bytes of `workspace`, or AIR_EINVAL / AIR_ELIMIT for a (T, B, k, G) the entry point refuses -- no GPU is touched */
+int64_t air_localization_workspace_bytes(int T, int B, int k, int G);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,20 @@ class GlyphDistort(C.Structure):
                 ("max_scale", C.c_double), ("lo", C.c_double), ("hi", C.c_double), ("seed", C.c_uint64)]
 
 
+LOC_MAX_STEPS = LOC_MAX_DIGITS = 16
+LOC_GROUP = 256
+LOC_IMAGES, LOC_PRESENT, LOC_INFERRED, LOC_MATCHED, LOC_HITS, LOC_COUNT_CORRECT, LOC_COUNTS = 0, 1, 2, 3, 4, 5, 6
+LOC_IOU, LOC_COVER, LOC_DIST, LOC_SUMS = 0, 1, 2, 3
+
+
+class Localization(C.Structure):
+    """air_localization_t: the records of an inference pass and the padded ground truth of its first k images in, the
+    optional per-digit match / IoU out, and the int64 / fp64 accumulators a call adds to"""
+    _fields_ = [("att", _p), ("run_digits", _p), ("gt_count", _p), ("gt_positions", _p), ("gt_boxes", _p),
+                ("match", _p), ("iou", _p), ("counts", _p), ("sums", _p),
+                ("T", _i), ("B", _i), ("k", _i), ("G", _i), ("canvas_size", _i), ("iou_threshold", C.c_double)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -323,6 +337,8 @@ _SIGNATURES = {
     "air_glyph_distort": (C.c_int, [C.POINTER(GlyphDistort), _p]),
     "air_glyph_distort_prepare": (C.c_int, [C.POINTER(GlyphDistort)]),
     "air_glyph_distort_lds": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "air_localization": (C.c_int, [C.POINTER(Localization), _p, _p]),
+    "air_localization_workspace_bytes": (C.c_int64, [C.c_int] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

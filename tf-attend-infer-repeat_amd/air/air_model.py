@@ -96,6 +96,7 @@ KERNEL_NAMES = {
     "air_scene_records": "scene_records_kernel",
     "air_render": "render_kernel",
     "air_glyph_distort": "glyph_distort_kernel",                        # (multi_mnist.DeviceHandwritingBank launches it)
+    "air_localization": "loc_match_kernel",                             # (air.metrics.Localization; then loc_fold_kernel)
 }
 
 

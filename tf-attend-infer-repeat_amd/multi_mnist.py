@@ -243,8 +243,25 @@ def generate_dataset(max_digits=2, images_per_digit=20000, test_set_size=1000, s
     digits = np.asarray([d for st in strata for d in st["digits"]], np.int32)
     perm = rng.permutation(len(images))                                 # shuffle_lists :215-225
     images, digits = images[perm], digits[perm]
+    # the ground truth of the test rows, carried through the same shuffle: [test_set_size, max(max_digits, 1), 2] int32
+    test = perm[:test_set_size]
+    positions, boxes = ([lst for st in strata for lst in st[k]] for k in ("positions", "boxes"))
     return dict(train_images=images[test_set_size:], train_digits=digits[test_set_size:],
-                test_images=images[:test_set_size], test_digits=digits[:test_set_size], source=source)
+                test_images=images[:test_set_size], test_digits=digits[:test_set_size], source=source,
+                test_positions=padded_truth([positions[i] for i in test], digits[:test_set_size], max_digits),
+                test_boxes=padded_truth([boxes[i] for i in test], digits[:test_set_size], max_digits))
+
+
+def padded_truth(lists, digits, max_digits=None):
+    """per-image flat lists [x0, y0, x1, y1, ...] (positions, or boxes as w, h) -> int32 [n, G, 2], zeros behind digits[i];
+    G = max_digits (at least 1), or the largest count when None: the layout air_embed_collect and air_localization read"""
+    digits = np.asarray(digits, np.int64).reshape(-1)
+    G = max(1, int(digits.max()) if max_digits is None and len(digits) else int(max_digits or 1))
+    out = np.zeros((len(digits), G, 2), np.int32)
+    for i, n in enumerate(digits):
+        if n:
+            out[i, :n] = np.asarray(lists[i], np.int32).reshape(-1)[:2 * n].reshape(n, 2)
+    return out
 
 
 # ----------------------------------------------------------------------------- reference file format
@@ -748,6 +765,16 @@ def shift_zero_digits_images(images, digits):
     return images[order], digits[order]
 
 
+def shift_zero_digits_order(digits):
+    """the permutation shift_zero_digits_images applies, as an index array: whatever belongs to the images (ground-truth
+    boxes) follows them by a[order]"""
+    empty = [i for i in range(len(digits)) if digits[i] == 0]
+    non_empty = [i for i in range(len(digits)) if digits[i] > 0]
+    if not empty:
+        return np.arange(len(digits))
+    return np.asarray([empty[0]] + non_empty + empty[1:], np.int64)
+
+
 _shift_zero = shift_zero_digits_images        # read_test_data's flag shadows the function name
 
 
@@ -820,5 +847,8 @@ if __name__ == "__main__":
     np.savez(MULTI_MNIST_FOLDER + "common.npz", images=np.stack(common["images"][T:]).astype(np.float32),
              digits=np.asarray(common["digits"][T:], np.int32))
     np.savez(MULTI_MNIST_FOLDER + "test.npz", images=np.stack(common["images"][:T]).astype(np.float32),
-             digits=np.asarray(common["digits"][:T], np.int32))
+             digits=np.asarray(common["digits"][:T], np.int32),
+             # the test set's ground truth, [n, 2 * max_digits] as --device writes it (training.py --localization reads it)
+             positions=padded_truth(common["positions"][:T], common["digits"][:T], args.max_digits).reshape(-1, 2 * max(args.max_digits, 1)),
+             boxes=padded_truth(common["boxes"][:T], common["digits"][:T], args.max_digits).reshape(-1, 2 * max(args.max_digits, 1)))
     print("glyph source: %s; wrote %d train / %d test images" % (source, len(perm) - T, T))

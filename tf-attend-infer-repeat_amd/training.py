@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from multi_mnist import (JITTER_NEUTRAL, DeviceGlyphBank, DeviceSceneSource, ShuffleBatchQueue, generate_dataset, handwriting_bank,
-                         load_glyphs, shift_zero_digits_images)
+                         load_glyphs, padded_truth, shift_zero_digits_images, shift_zero_digits_order)
 from air.air_model import AIRModel
 
 EPOCHS = 300
@@ -58,6 +58,9 @@ TEST_SET_SIZE = 1000
 DEFAULT_RESULTS_FOLDER = "air_results"
 TRAIN_DATA_FILE = "multi_mnist_data/common.npz"
 TEST_DATA_FILE = "multi_mnist_data/test.npz"
+# --localization: what a row of scalars.jsonl gains (as loc_<name>) and TensorBoard shows (as localization/<name>); the
+# sixth number of air.metrics.Localization, count_accuracy, is the row's `accuracy`
+LOCALIZATION_KEYS = ("mean_iou", "recall", "precision", "cover", "center_dist")
 
 
 def load_background(bg_path="", bg_max_intensity=1.0):
@@ -74,26 +77,44 @@ def load_background(bg_path="", bg_max_intensity=1.0):
     return read_image(bg_path, bg_max_intensity)
 
 
-def load_data(bg_path="", bg_max_intensity=1.0):
+def cache_without_truth():
+    """the cached data set load_data would read, when its test file holds no ground-truth boxes; None otherwise"""
+    if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
+        with np.load(TEST_DATA_FILE) as te:
+            if "positions" not in te.files or "boxes" not in te.files:
+                return TEST_DATA_FILE
+    return None
+
+
+def load_data(bg_path="", bg_max_intensity=1.0, truth=False):
+    """-> train images, train digits, test images, test digits; truth: and the test set's ground-truth boxes, positions
+    (x, y) and boxes (w, h) as int32 [n, G, 2] (zeros behind an image's digits)"""
     if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
         tr, te = np.load(TRAIN_DATA_FILE), np.load(TEST_DATA_FILE)
-        return tr["images"], tr["digits"], te["images"], te["digits"]
+        out = tr["images"], tr["digits"], te["images"], te["digits"]
+        if not truth:
+            return out
+        n = len(te["digits"])
+        return out + (te["positions"].astype(np.int32).reshape(n, -1, 2), te["boxes"].astype(np.int32).reshape(n, -1, 2))
     rec_tr, rec_te = TRAIN_DATA_FILE.replace(".npz", ".tfrecords"), TEST_DATA_FILE.replace(".npz", ".tfrecords")
     if os.path.exists(rec_tr) and os.path.exists(rec_te):
         # the reference's own files (training.py:23-24: multi_mnist_data/common.tfrecords, test.tfrecords)
         from multi_mnist import read_test_data
         print("Reading the reference's TFRecord files...")
         tri, trd, *_ = read_test_data(rec_tr)
-        tei, ted, *_ = read_test_data(rec_te)
-        return tri, trd.astype(np.int32), tei, ted.astype(np.int32)
+        tei, ted, _, tep, teb, _ = read_test_data(rec_te)
+        out = tri, trd.astype(np.int32), tei, ted.astype(np.int32)
+        return out + (padded_truth(tep, ted), padded_truth(teb, ted)) if truth else out
     print("Generating multi-digit dataset in memory (multi_mnist.py defaults)...")
     ds = generate_dataset(bg=load_background(bg_path, bg_max_intensity))
-    return ds["train_images"], ds["train_digits"], ds["test_images"], ds["test_digits"]
+    out = ds["train_images"], ds["train_digits"], ds["test_images"], ds["test_digits"]
+    return out + (ds["test_positions"], ds["test_boxes"]) if truth else out
 
 
-def device_test_set(dev, variants, seed, max_digits, margin, gap, bg):
+def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=False):
     """--glyph-style mnist-like: TEST_SET_SIZE scenes composed once on the device from one handwriting bank with a seed of its
-    own -> (images, digits) as numpy arrays; the bank and the source are dropped"""
+    own -> (images, digits) as numpy arrays; the bank and the source are dropped.  truth: and source.meta()'s positions and
+    boxes, int32 [n, max_digits, 2]"""
     images = torch.zeros(TEST_SET_SIZE, CANVAS_SIZE ** 2, device=dev)
     digits = torch.zeros(TEST_SET_SIZE, dtype=torch.int32, device=dev)
     bank, _ = handwriting_bank(variants, 0x54455354 + seed, dev)
@@ -101,7 +122,11 @@ def device_test_set(dev, variants, seed, max_digits, margin, gap, bg):
                                gap=gap, bg=bg, seed=0x5445535453 + seed)
     bank.refresh()
     source.next_batch()
-    return images.cpu().numpy(), digits.cpu().numpy()
+    out = images.cpu().numpy(), digits.cpu().numpy()
+    if truth:
+        meta = source.meta()
+        out += tuple(meta[k].cpu().numpy().reshape(TEST_SET_SIZE, -1, 2) for k in ("positions", "boxes"))
+    return out
 
 
 class SummaryWriter:
@@ -110,19 +135,31 @@ class SummaryWriter:
     launch into a device vector; the vector is copied into a pinned host ring without blocking and a row is written
     when the NEXT evaluation has been enqueued, so the host never waits for the step it has just launched."""
 
-    def __init__(self, model, path, t0, slots=2, on_row=None):
+    def __init__(self, model, path, t0, slots=2, on_row=None, localization=None, on_localization=None):
+        """localization: (air.metrics.Localization of `model`, (gt_count, gt_positions, gt_boxes) on the device) -- every
+        evaluation is then also scored against the ground truth (reset + update + values: a few launches behind the
+        summaries one, fetched through the same ring) and the row gains the loc_* keys; on_localization(step, values)"""
         self.model, self.t0, self.on_row = model, t0, on_row
         self.names = model.summary_names()
         self.dev = torch.empty(len(self.names), dtype=torch.float32, device=model.input_images.device)
         self.host = torch.empty(slots, len(self.names), dtype=torch.float32).pin_memory()
         self.events = [torch.cuda.Event() for _ in range(slots)]
         self.pending, self.k, self.file = [], 0, open(path, "w")
+        self.loc, self.on_localization = localization, on_localization
+        if localization is not None:
+            self.loc_names = localization[0].names()
+            self.loc_host = torch.empty(slots, len(self.loc_names), dtype=torch.float64).pin_memory()
 
     def push(self, step):
         slot = self.k % len(self.events)
         self.k += 1
         self.model.numeric_summaries(self.dev)
         self.host[slot].copy_(self.dev, non_blocking=True)
+        if self.loc is not None:
+            loc, truth = self.loc
+            loc.reset()
+            loc.update(*truth)
+            self.loc_host[slot].copy_(loc.values(), non_blocking=True)
         self.events[slot].record()
         self.pending.append((slot, step))
         while len(self.pending) > 1:
@@ -133,10 +170,15 @@ class SummaryWriter:
         self.events[slot].synchronize()
         row = {"step": step, "wall_s": round(time.perf_counter() - self.t0, 3)}
         row.update({k: (round(v, 5) if v == v else None) for k, v in zip(self.names, self.host[slot].tolist())})
+        if self.loc is not None:
+            located = dict(zip(self.loc_names, self.loc_host[slot].tolist()))
+            row.update({"loc_" + k: (round(located[k], 5) if located[k] == located[k] else None) for k in LOCALIZATION_KEYS})
         self.file.write(json.dumps(row) + "\n")
         self.file.flush()
         if self.on_row is not None:
             self.on_row(step, self.host[slot].tolist())
+        if self.loc is not None and self.on_localization is not None:
+            self.on_localization(step, [located[k] for k in LOCALIZATION_KEYS])
 
     def flush(self):
         while self.pending:
@@ -190,6 +232,10 @@ class TensorBoardWriter:
     def numeric(self, step, values):
         """SummaryWriter's row of `step` (AIRModel.summary_names() order: loss, accuracy, then the reference's scalars)"""
         self.events.add_scalars(step, zip(self.tags.numeric, values[2:]))
+
+    def localization(self, step, values):
+        """--localization: the five LOCALIZATION_KEYS of the evaluation at `step`"""
+        self.events.add_scalars(step, [("localization/" + k, v) for k, v in zip(LOCALIZATION_KEYS, values)])
 
     def variables(self, step):
         from air.summaries import decode_histograms
@@ -289,7 +335,19 @@ def main():
                              "distorted on the device into MNIST's geometry (multi_mnist.DeviceHandwritingBank: a 20-pixel "
                              "box centred in a 28-pixel frame), a fresh bank every --graph-steps steps; the evaluation set is "
                              "composed on the device too")
+    parser.add_argument("--localization", action="store_true",
+                        help="score the test model's attention boxes against the test set's ground-truth boxes at every "
+                             "evaluation (air.metrics.Localization: box IoU, recall, precision, cover, centre distance): the "
+                             "rows of summary/scalars.jsonl gain loc_* keys, --tensorboard gains localization/* scalars, and the "
+                             "run ends with the confusion matrix of the counts")
+    parser.add_argument("--localization-iou", type=float, default=0.5, help="--localization: the IoU from which a matched box is a hit")
     args = parser.parse_args()
+    if args.localization and not 0.0 < args.localization_iou <= 1.0:
+        parser.error("--localization-iou must lie in (0, 1]")
+    if args.localization and args.glyph_style != "mnist-like" and cache_without_truth():
+        parser.error("--localization needs the ground-truth boxes of the test set, and %s holds none (no 'positions' / 'boxes'): "
+                     "regenerate the cache with multi_mnist.py (or multi_mnist.py --device N), which writes them, or remove it "
+                     "to have the data set generated in memory" % cache_without_truth())
     jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
                   max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
     mnist_like = args.glyph_style == "mnist-like"
@@ -318,10 +376,14 @@ def main():
     dev = torch.device("cuda", 0)
     print("Creating input pipeline...")
     if mnist_like:                                                   # no host generator: the test set is device work too
-        te_im, te_dg = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin,
-                                       args.digit_gap, load_background(args.bg_path, args.bg_max_intensity))
+        te_im, te_dg, *te_truth = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin,
+                                                  args.digit_gap, load_background(args.bg_path, args.bg_max_intensity),
+                                                  truth=args.localization)
     else:
-        tr_im, tr_dg, te_im, te_dg = load_data(args.bg_path, args.bg_max_intensity)
+        tr_im, tr_dg, te_im, te_dg, *te_truth = load_data(args.bg_path, args.bg_max_intensity, truth=args.localization)
+    if args.localization:                                            # the ground truth follows the images' permutation
+        order = shift_zero_digits_order(te_dg)
+        te_truth = [torch.tensor(np.ascontiguousarray(a[order]).astype(np.int32), device=dev) for a in te_truth]
     te_im, te_dg = shift_zero_digits_images(te_im, te_dg)
     if not args.online_data:
         train_images = torch.tensor(tr_im, device=dev)
@@ -406,7 +468,12 @@ def main():
     order = train_model.backward
     t0 = time.perf_counter()
     board = TensorBoardWriter(summaries_folder, train_model, test_model) if args.tensorboard else None
-    writer = SummaryWriter(test_model, summaries_folder + "scalars.jsonl", t0, on_row=board.numeric if board else None)
+    located = None
+    if args.localization:
+        from air.metrics import Localization
+        located = (Localization(test_model, int(te_truth[0].shape[1]), args.localization_iou), (test_targets, *te_truth))
+    writer = SummaryWriter(test_model, summaries_folder + "scalars.jsonl", t0, on_row=board.numeric if board else None,
+                           localization=located, on_localization=board.localization if board else None)
     while step < total:
         if step % NUM_SUMMARIES_EACH_ITERATIONS == 0:
             test_model.forward()
@@ -442,6 +509,16 @@ def main():
     print("training has ended")
     print("test accuracy {:.4f}  test loss {:.3f}  ({} iterations, {:.1f} s)".format(
         float(test_model.accuracy), float(test_model.loss), step, time.perf_counter() - t0))
+    if located:                                                      # the evaluation just made, the last of the run
+        loc, truth = located
+        loc.reset()
+        loc.update(*truth)
+        res = loc.result()
+        print("localization at IoU {:g}: ".format(loc.iou_threshold) + "  ".join(
+            "{} {:.4f}".format(k, res[k]) for k in LOCALIZATION_KEYS))
+        print("count confusion (rows: digits present 0..{}, columns: objects inferred 0..{}):".format(loc.G, loc.T))
+        for row in res["confusion"]:
+            print("  " + " ".join("{:6d}".format(int(v)) for v in row))
     if args.online_data:
         print("online data: {} batches composed on the device, {} canvases given up".format(
             int(batches.counter), int(batches.gave_up())) + ("" if bank is None else
