@@ -1241,6 +1241,100 @@ int air_localization(const air_localization_t* args, void* workspace, void* stre
 /* bytes of `workspace`, or AIR_EINVAL / AIR_ELIMIT for a (T, B, k, G) the entry point refuses -- no GPU is touched */
 int64_t air_localization_workspace_bytes(int T, int B, int k, int G);
 
+/* ---- segmentation metrics (additive to ABI 6) -----------------------------------------------------------------------------
+ * The decomposition of an inference pass scored per pixel: which object explains which ink.  Two entry points:
+ * air_scene_masks builds the ground-truth instance labels of composed scenes from the scene source's metadata, and
+ * air_segmentation derives the predicted instance labels of a pass from its records and decoded windows and scores them
+ * against a label plane -- the foreground adjusted Rand index (FG-ARI) and the best mask IoU of every ground-truth object.
+ * air/metrics.py (Segmentation) is the caller; tests/segmentation_cases.py restates every operation below.
+ *
+ * air_scene_masks.  glyphs [Gn, gd * gd] and crops [Gn, 4] (x0, y0, w, h) are the arrays air_scene_source_compose reads;
+ * digits [B], indices [B, max_digits] and positions [B, 2 * max_digits] (x, y) are its outputs.  One workgroup per scene.
+ * mask [B, C * C] uint8, every element written: pixel (py, px) of scene b gets the label g + 1 of the SMALLEST
+ * g < clamp(digits[b], 0, max_digits) with, for idx = indices[b][g], (x0, y0, w, h) = crops[idx], (x_g, y_g) =
+ * positions[b][g]:
+ *   0 <= px - x_g < w  and  0 <= py - y_g < h  and  glyphs[idx][(y0 + py - y_g) * gd + (x0 + px - x_g)] > ink_threshold,
+ * and 0 where there is none.  A digit whose idx lies outside [0, Gn), or whose crop box leaves its gd x gd frame (x0 < 0,
+ * y0 < 0, w < 0, h < 0, x0 + w > gd or y0 + h > gd), labels nothing.  (A NaN glyph value is not ink.)
+ * Refusals, on the host before any HIP call, in this order.  AIR_EINVAL: a null descriptor; B, G, gd, C or max_digits < 1;
+ * ink_threshold < 0 or NaN.  AIR_ELIMIT: C > AIR_SCENE_MAX_CANVAS, gd > AIR_SCENE_MAX_GLYPH, max_digits >
+ * AIR_SCENE_MAX_DIGITS.  AIR_EINVAL: a null pointer.  16-byte stores where C * C is a multiple of 16 and mask is 16-byte
+ * aligned, byte stores otherwise.
+ *
+ * air_segmentation.  One workgroup per image i < k; the taps and windows of all T steps are staged in LDS exactly as
+ * air_render stages them (the same device code), <= 160 KB: AIR_ELIMIT beyond.
+ * Predicted label of canvas pixel (py, px).  The term of step t is the one compose adds for it:
+ *   c_t = z_pres_t * (((wa * Ia + wb * Ib) + wc * Ic) + wd * Id)
+ * -- the window -> canvas taps of theta_recon, fp32, the same operations in the same order (the translation unit has
+ * -ffp-contract=off) -- taken only for ACTIVE steps (att[t][i][AIR_ATT_MASK] != 0).  Walk t = 0 .. T - 1 with
+ * best = pred_threshold, label = 0:  if (c_t > best) { best = c_t; label = t + 1; }.  A tie keeps the smaller t, a NaN never
+ * takes the pixel, and a pixel no step lifts above pred_threshold is background (label 0).
+ * Table of image i: n[r][c] = the number of its C * C pixels with truth r and prediction c, int32, r = 0 .. G, c = 0 .. T;
+ * the truth of a pixel is gt_mask[i][p], a value > G counting as 0.
+ * FG-ARI, over the rows r >= 1 only, in int64:  a_r = sum_c n[r][c],  b_c = sum_{r>=1} n[r][c],  N = sum_{r>=1} a_r,
+ *   S = sum_{r>=1,c} n (n - 1) / 2,  A = sum_{r>=1} a_r (a_r - 1) / 2,  Bs = sum_c b_c (b_c - 1) / 2,  P = N (N - 1) / 2.
+ * The image is SCORED only when N >= 2; then in fp64, in this order:
+ *   E = (double)A * (double)Bs / (double)P;   M = ((double)A + (double)Bs) / 2.0;
+ *   ari = (M == E) ? 1.0 : ((double)S - E) / (M - E).
+ * Mask IoU.  Digit r >= 1 is PRESENT when a_r > 0.  With colsum_c = sum_{r>=0} n[r][c]:  v = 0.0; for c = 1 .. T in order:
+ *   q = (double)n[r][c] / (double)(a_r + colsum_c - n[r][c]);  if (q > v) v = q.     An absent digit has v = 0.
+ * Outputs, each nullable on its own: pred_mask [k, C * C] uint8; tables [k, (G + 1) * (T + 1)] int32; ari [k] fp64 (NaN for
+ * an unscored image); mask_iou [k, G] fp64 (digit r at column r - 1).
+ * Accumulators: the caller zeroes them once; a call ADDS.
+ *   counts[AIR_SEG_IMAGES] += k, [SCORED] += scored images, [PRESENT] += present digits, [FG_PIXELS] += sum N,
+ *   [FG_MISSED] += sum_{r>=1} n[r][0], [BG_CLAIMED] += sum_{c>=1} n[0][c].  Integers: any order, the same sums.
+ *   sums[AIR_SEG_ARI / AIR_SEG_MASK_IOU] += in the ONE order of air_localization, with its group AIR_LOC_GROUP:
+ *     1. image i:  ARI: its ari, +0.0 for an unscored image.  MASK_IOU: (((+0.0 + v_1) + v_2) + ...) over its present digits
+ *        in order;
+ *     2. the adjacent pairwise tree over each group of AIR_LOC_GROUP images (+0.0 for an image >= k);
+ *     3. the batch total = (((+0.0 + group 0) + group 1) + ...) in group order;
+ *     4. sums[.] = incoming sums[.] + the batch total.
+ * Two launches on the caller's stream (the per-image kernel, which leaves the images' two values and five integer totals in
+ * the workspace; one small fold), no synchronisation, no host read, no atomics on memory: the same inputs give the same bits.  Rows >= k of
+ * att / vrec are never read, gt_mask has k rows, and rows >= k of the outputs are never written.  pred_mask is stored 16
+ * bytes at a time where C * C is a multiple of 16 and pred_mask is 16-byte aligned, byte by byte otherwise.
+ * Refusals, on the host before any HIP call, in this order.  AIR_EINVAL: a null descriptor; T, B, k or G < 1; k > B.
+ * AIR_ELIMIT: T > AIR_SEG_MAX_STEPS, G > AIR_SEG_MAX_DIGITS.  AIR_EINVAL: C < 2, w < 2.  AIR_ELIMIT: C > AIR_SEG_MAX_CANVAS,
+ * w > AIR_SEG_MAX_WINDOW, more than 160 KB of LDS.  AIR_EINVAL: pred_threshold not in [0, 1) (NaN included); a null att,
+ * vrec, gt_mask, counts, sums or workspace. */
+typedef struct {
+    const float* glyphs;                 /* [G, gd * gd]                                                                */
+    const int32_t* crops;                /* [G, 4] x0, y0, w, h                                                         */
+    const int32_t* digits;               /* [B]                                                                         */
+    const int32_t* indices;              /* [B, max_digits]                                                             */
+    const int32_t* positions;            /* [B, 2 * max_digits] (x, y)                                                  */
+    uint8_t* mask;                       /* out [B, C * C]                                                              */
+    int32_t B, G, gd, C, max_digits;
+    float ink_threshold;
+} air_scene_masks_t;
+int air_scene_masks(const air_scene_masks_t* args, void* stream);
+
+#define AIR_SEG_MAX_STEPS 16
+#define AIR_SEG_MAX_DIGITS 16
+#define AIR_SEG_MAX_CANVAS 128
+#define AIR_SEG_MAX_WINDOW 32
+enum { AIR_SEG_IMAGES = 0, AIR_SEG_SCORED = 1, AIR_SEG_PRESENT = 2, AIR_SEG_FG_PIXELS = 3, AIR_SEG_FG_MISSED = 4,
+       AIR_SEG_BG_CLAIMED = 5, AIR_SEG_COUNTS = 6 };
+enum { AIR_SEG_ARI = 0, AIR_SEG_MASK_IOU = 1, AIR_SEG_SUMS = 2 };
+typedef struct {
+    const float* att;                    /* [T, B, AIR_ATT_STRIDE] of the pass just run                                 */
+    const float* vrec;                   /* [T, B, w * w] the decoded windows of the pass                               */
+    const uint8_t* gt_mask;              /* [k, C * C] instance labels, 0 the background                                */
+    uint8_t* pred_mask;                  /* out, nullable [k, C * C]                                                    */
+    int32_t* tables;                     /* out, nullable [k, (G + 1) * (T + 1)]                                        */
+    double* ari;                         /* out, nullable [k]                                                           */
+    double* mask_iou;                    /* out, nullable [k, G]                                                        */
+    int64_t* counts;                     /* in / out [AIR_SEG_COUNTS]                                                   */
+    double* sums;                        /* in / out [AIR_SEG_SUMS]                                                     */
+    int32_t T, B, k, G, C, w;
+    float pred_threshold;
+} air_segmentation_t;
+/* `workspace`: a device buffer of at least air_segmentation_workspace_bytes(T, B, k, G) bytes, 8-byte aligned (the two
+ * values and the five integer totals of every image: 56 k bytes) */
+int air_segmentation(const air_segmentation_t* args, void* workspace, void* stream);
+/* bytes of `workspace`, or AIR_EINVAL / AIR_ELIMIT for a (T, B, k, G) the entry point refuses -- no GPU is touched */
+int64_t air_segmentation_workspace_bytes(int T, int B, int k, int G);
+
 #ifdef __cplusplus
 }
 #endif

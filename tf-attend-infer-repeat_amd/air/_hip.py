@@ -251,6 +251,27 @@ class Localization(C.Structure):
                 ("T", _i), ("B", _i), ("k", _i), ("G", _i), ("canvas_size", _i), ("iou_threshold", C.c_double)]
 
 
+SEG_MAX_STEPS = SEG_MAX_DIGITS = 16
+SEG_MAX_CANVAS, SEG_MAX_WINDOW = 128, 32
+SEG_IMAGES, SEG_SCORED, SEG_PRESENT, SEG_FG_PIXELS, SEG_FG_MISSED, SEG_BG_CLAIMED, SEG_COUNTS = 0, 1, 2, 3, 4, 5, 6
+SEG_ARI, SEG_MASK_IOU, SEG_SUMS = 0, 1, 2
+
+
+class SceneMasks(C.Structure):
+    """air_scene_masks_t: the scene source's glyph table and the metadata of a composed batch in, the uint8 instance labels
+    of its canvases out"""
+    _fields_ = [("glyphs", _p), ("crops", _p), ("digits", _p), ("indices", _p), ("positions", _p), ("mask", _p),
+                ("B", _i), ("G", _i), ("gd", _i), ("C", _i), ("max_digits", _i), ("ink_threshold", _f)]
+
+
+class Segmentation(C.Structure):
+    """air_segmentation_t: the records and decoded windows of an inference pass and the label planes of its first k images
+    in, the optional per-image outputs out, and the int64 / fp64 accumulators a call adds to"""
+    _fields_ = [("att", _p), ("vrec", _p), ("gt_mask", _p), ("pred_mask", _p), ("tables", _p), ("ari", _p), ("mask_iou", _p),
+                ("counts", _p), ("sums", _p),
+                ("T", _i), ("B", _i), ("k", _i), ("G", _i), ("C", _i), ("w", _i), ("pred_threshold", _f)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -339,6 +360,9 @@ _SIGNATURES = {
     "air_glyph_distort_lds": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "air_localization": (C.c_int, [C.POINTER(Localization), _p, _p]),
     "air_localization_workspace_bytes": (C.c_int64, [C.c_int] * 4),
+    "air_scene_masks": (C.c_int, [C.POINTER(SceneMasks), _p]),
+    "air_segmentation": (C.c_int, [C.POINTER(Segmentation), _p, _p]),
+    "air_segmentation_workspace_bytes": (C.c_int64, [C.c_int] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

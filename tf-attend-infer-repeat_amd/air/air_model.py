@@ -97,6 +97,8 @@ KERNEL_NAMES = {
     "air_render": "render_kernel",
     "air_glyph_distort": "glyph_distort_kernel",                        # (multi_mnist.DeviceHandwritingBank launches it)
     "air_localization": "loc_match_kernel",                             # (air.metrics.Localization; then loc_fold_kernel)
+    "air_segmentation": "seg_image_kernel",                             # (air.metrics.Segmentation; then seg_fold_kernel)
+    "air_scene_masks": "scene_masks_kernel",                            # (Segmentation.scene_masks)
 }
 
 

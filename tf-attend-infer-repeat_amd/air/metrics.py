@@ -13,7 +13,18 @@ blocking; ``result()`` is the one method that synchronises.
     loc.result()                                        # dict of floats + "confusion" [G + 1, T + 1] (truth x inferred)
 
 The ground truth has the layouts of air_embed_collect and of multi_mnist.DeviceSceneSource: positions (x, y) and boxes
-(w, h) as [k, G, 2] or [k, 2 G], so ``source.meta()`` can be passed straight in.  There is no CPU fallback."""
+(w, h) as [k, G, 2] or [k, 2 G], so ``source.meta()`` can be passed straight in.  There is no CPU fallback.
+
+``Segmentation(model, max_gt_digits)`` is the per-pixel instrument beside it: which object explains which ink?  One call of
+air_segmentation per ``update()`` derives the predicted instance labels of the pass (``att`` and the decoded windows
+``vrec``; the step whose compose term is the largest above ``pred_threshold``) and scores them against uint8 label planes:
+the foreground adjusted Rand index and the best mask IoU of every ground-truth object, accumulated as above.
+
+    seg = Segmentation(test_model, max_gt_digits=2)
+    masks = Segmentation.scene_masks(source, digits)    # uint8 [B, C * C] from the glyph table of a DeviceSceneSource
+    test_model.forward()
+    seg.update(masks)
+    seg.values()                                        # float64 [4] on the device: fg_ari, mask_iou, fg_missed, bg_claimed"""
 import ctypes as C
 
 import numpy as np
@@ -115,3 +126,131 @@ class Localization:
                    matched=int(counts[H.LOC_MATCHED]), hits=int(counts[H.LOC_HITS]),
                    confusion=counts[H.LOC_COUNTS:].reshape(self.G + 1, self.T + 1).copy(), sums=sums)
         return out
+
+
+SEG_NAMES = ("fg_ari", "mask_iou", "fg_missed", "bg_claimed")
+
+
+class Segmentation:
+    """fg_ari = ARI / SCORED (images with at least two foreground pixels), mask_iou = MASK_IOU / PRESENT (the best IoU of a
+    predicted mask with every ground-truth object), fg_missed = FG_MISSED / FG_PIXELS (ink no object claims), bg_claimed =
+    BG_CLAIMED / (IMAGES * C * C - FG_PIXELS) (background an object claims); a zero denominator gives NaN.  keep=True also
+    keeps ``pred_mask`` [B, C * C] uint8, ``tables`` [B, G + 1, T + 1] int32 (truth x prediction), ``ari`` [B] and
+    ``mask_iou`` [B, G] float64 of the last update (rows >= k are not written)."""
+
+    def __init__(self, model, max_gt_digits, pred_threshold=0.5, keep=False):
+        T, B, G = int(model.max_steps), int(model.batch_size), int(max_gt_digits)
+        Cc, w = int(model.canvas_size), int(model.windows_size)
+        if G < 1:
+            raise ValueError("Segmentation: max_gt_digits must be positive")
+        if T > H.SEG_MAX_STEPS or G > H.SEG_MAX_DIGITS:
+            raise NotImplementedError("Segmentation: %d steps, %d digits in one image: the kernel holds %d and %d"
+                                      % (T, G, H.SEG_MAX_STEPS, H.SEG_MAX_DIGITS))
+        if Cc > H.SEG_MAX_CANVAS or w > H.SEG_MAX_WINDOW:
+            raise NotImplementedError("Segmentation: a %d x %d canvas, %d x %d windows: the kernel holds %d and %d"
+                                      % (Cc, Cc, w, w, H.SEG_MAX_CANVAS, H.SEG_MAX_WINDOW))
+        thr = float(pred_threshold)
+        if not 0.0 <= thr < 1.0:
+            raise ValueError("Segmentation: pred_threshold must lie in [0, 1)")
+        nbytes = H.lib().air_segmentation_workspace_bytes(T, B, B, G)
+        if nbytes < 0:
+            H.check(int(nbytes), "air_segmentation_workspace_bytes")
+        H.require_device(model.input_images, "the model's input buffer", "Segmentation")
+        dev = self.device = model.input_images.device
+        self.model, self.T, self.B, self.G, self.C, self.w, self.pred_threshold = model, T, B, G, Cc, w, thr
+        self.counts = torch.zeros(H.SEG_COUNTS, dtype=torch.int64, device=dev)
+        self.sums = torch.zeros(H.SEG_SUMS, dtype=torch.float64, device=dev)
+        self.workspace = torch.empty(int(nbytes) // 8, dtype=torch.float64, device=dev)
+        self.pred_mask = torch.zeros(B, Cc * Cc, dtype=torch.uint8, device=dev) if keep else None
+        self.tables = torch.zeros(B, G + 1, T + 1, dtype=torch.int32, device=dev) if keep else None
+        self.ari = torch.full((B,), float("nan"), dtype=torch.float64, device=dev) if keep else None
+        self.mask_iou = torch.zeros(B, G, dtype=torch.float64, device=dev) if keep else None
+        self._nan = torch.full((len(SEG_NAMES),), float("nan"), dtype=torch.float64, device=dev)
+
+    @staticmethod
+    def names():
+        return list(SEG_NAMES)
+
+    def reset(self):
+        """zeroes the accumulators on the current stream"""
+        self.counts.zero_()
+        self.sums.zero_()
+
+    def update(self, gt_mask, k=None):
+        """One air_segmentation call over the model's last pass: its first k images (default: all rows of gt_mask) against
+        gt_mask [>= k, C * C] or [>= k, C, C] uint8 (a device tensor, or a numpy array: copied), 0 the background."""
+        m = self.model
+        m._ensure()
+        H.require_device(m.att, "the model's records", "Segmentation.update")
+        H.require_device(m.vrec, "the model's decoded windows", "Segmentation.update")
+        if not torch.is_tensor(gt_mask):
+            gt_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(gt_mask), dtype=np.uint8)).to(self.device)
+        H.require_device(gt_mask, "gt_mask", "Segmentation.update")
+        if gt_mask.dtype != torch.uint8 or not gt_mask.is_contiguous() or gt_mask.device != self.device:
+            raise ValueError("Segmentation.update: gt_mask must be a contiguous uint8 tensor on %s" % self.device)
+        if k is None:
+            k = int(gt_mask.shape[0]) if gt_mask.dim() else 0
+        k = int(k)
+        if not 1 <= k <= self.B:
+            raise ValueError("Segmentation.update: k = %d images, the model's batch holds %d" % (k, self.B))
+        if gt_mask.dim() < 2 or int(gt_mask.shape[0]) < k or gt_mask.numel() != int(gt_mask.shape[0]) * self.C * self.C:
+            raise ValueError("Segmentation.update: gt_mask must hold %d labels for each of at least %d images, got %r"
+                             % (self.C * self.C, k, tuple(gt_mask.shape)))
+        a = H.Segmentation(H.ptr(m.att), H.ptr(m.vrec), H.ptr(gt_mask), H.ptr(self.pred_mask), H.ptr(self.tables),
+                           H.ptr(self.ari), H.ptr(self.mask_iou), H.ptr(self.counts), H.ptr(self.sums),
+                           self.T, self.B, k, self.G, self.C, self.w, self.pred_threshold)
+        H.launch("air_segmentation", self.device, C.byref(a), H.ptr(self.workspace))
+
+    def values(self, out=None):
+        """float64 [len(names())] on the device, from the accumulators as they stand on the current stream; never blocks"""
+        c, s = self.counts, self.sums
+        num = torch.stack((s[H.SEG_ARI], s[H.SEG_MASK_IOU], c[H.SEG_FG_MISSED].double(), c[H.SEG_BG_CLAIMED].double()))
+        den = torch.stack((c[H.SEG_SCORED], c[H.SEG_PRESENT], c[H.SEG_FG_PIXELS],
+                           c[H.SEG_IMAGES] * (self.C * self.C) - c[H.SEG_FG_PIXELS])).double()
+        v = torch.where(den == 0, self._nan, num / den)
+        if out is None:
+            return v
+        out.copy_(v)
+        return out
+
+    def result(self):
+        """the values as a dict of floats and the raw totals -- synchronises"""
+        values, counts, sums = self.values().cpu().tolist(), self.counts.cpu().numpy(), self.sums.cpu().numpy()
+        out = dict(zip(SEG_NAMES, values))
+        out.update(images=int(counts[H.SEG_IMAGES]), scored=int(counts[H.SEG_SCORED]), present=int(counts[H.SEG_PRESENT]),
+                   fg_pixels=int(counts[H.SEG_FG_PIXELS]), fg_missed_pixels=int(counts[H.SEG_FG_MISSED]),
+                   bg_claimed_pixels=int(counts[H.SEG_BG_CLAIMED]), sums=sums)
+        return out
+
+    @staticmethod
+    def scene_masks(source_or_arrays, digits, ink_threshold=0.0):
+        """uint8 [B, C * C] instance labels of composed scenes, one air_scene_masks launch on the current stream: pixel p of
+        scene b is g + 1 for the first digit g < digits[b] whose glyph has ink (a value > ink_threshold) there, 0 elsewhere.
+        source_or_arrays: a multi_mnist.DeviceSceneSource (its glyphs, crops and meta() of the last batch), or a dict of
+        device tensors glyphs [Gn, gd * gd] float32, crops [Gn, 4], indices [B, max_digits], positions [B, 2 max_digits]
+        int32 and the int canvas_dim.  digits: int32 [B] on the device."""
+        src = source_or_arrays
+        if isinstance(src, dict):
+            glyphs, crops, indices, positions, Cc = (src[key] for key in ("glyphs", "crops", "indices", "positions", "canvas_dim"))
+        else:
+            meta = src.meta()
+            glyphs, crops, indices, positions, Cc = src.glyphs, src.crops, meta["indices"], meta["positions"], src.canvas_dim
+        for t, what, dtype in ((glyphs, "glyphs", torch.float32), (crops, "crops", torch.int32), (digits, "digits", torch.int32),
+                               (indices, "indices", torch.int32), (positions, "positions", torch.int32)):
+            H.require_device(t, what, "Segmentation.scene_masks")
+            if t.dtype != dtype or not t.is_contiguous() or t.device != glyphs.device:
+                raise ValueError("Segmentation.scene_masks: %s must be a contiguous %s tensor on %s" % (what, dtype, glyphs.device))
+        if glyphs.dim() != 2 or crops.dim() != 2 or tuple(crops.shape) != (int(glyphs.shape[0]), 4):
+            raise ValueError("Segmentation.scene_masks: glyphs must be [Gn, gd * gd] and crops [Gn, 4]")
+        Gn, gd, Cc, B = int(glyphs.shape[0]), int(round(float(glyphs.shape[1]) ** 0.5)), int(Cc), int(digits.numel())
+        if gd * gd != int(glyphs.shape[1]):
+            raise ValueError("Segmentation.scene_masks: a glyph must be a square plane, got %d values" % int(glyphs.shape[1]))
+        md = indices.numel() // B if B else 0
+        if B < 1 or md < 1 or indices.numel() != B * md or positions.numel() != 2 * B * md:
+            raise ValueError("Segmentation.scene_masks: indices [B, max_digits] and positions [B, 2 max_digits] must go with digits "
+                             "[B], got %r, %r and %r" % (tuple(indices.shape), tuple(positions.shape), tuple(digits.shape)))
+        mask = torch.empty(B, Cc * Cc, dtype=torch.uint8, device=glyphs.device)
+        a = H.SceneMasks(H.ptr(glyphs), H.ptr(crops), H.ptr(digits), H.ptr(indices), H.ptr(positions), H.ptr(mask),
+                         B, Gn, gd, Cc, md, float(ink_threshold))
+        H.launch("air_scene_masks", glyphs.device, C.byref(a))
+        return mask

@@ -83,6 +83,28 @@ def visualize_scenes(canvas, st_back, steps, canvas_size, windows_size, max_step
     return torch.cat([plain, stripe, draw_colored_bounding_boxes(large, boxes, steps)], dim=2)
 
 
+def colour_masks(mask, canvas):
+    """Instance labels as a picture (air.metrics.Segmentation: scene_masks, or pred_mask with keep=True).  mask [n, C*C] or
+    [n, C, C] integer labels, 0 the background; canvas: the images [n, C*C] the labels lie over, or the int C for a black
+    base -> [n, C, C, 3] float in [0, 1].  The colour convention of draw_colored_bounding_boxes: label s is added to channel
+    (s - 1) % 3 and subtracted from the other two, so an object is red, green or blue and the background keeps the grey of
+    the canvas."""
+    n = mask.shape[0]
+    if isinstance(canvas, int):
+        C = canvas
+        base = torch.zeros(n, C, C, device=mask.device)
+    else:
+        C = int(round(float(canvas[0].numel()) ** 0.5))
+        base = canvas.reshape(n, C, C).float()
+    label = mask.reshape(n, C, C).long()
+    channels = []
+    for c in range(3):
+        mine = (label > 0) & ((label - 1) % 3 == c)
+        other = (label > 0) & ~mine
+        channels.append(torch.where(mine, torch.ones_like(base), torch.where(other, torch.zeros_like(base), base)))
+    return torch.stack(channels, dim=3)
+
+
 def save_image_grid(images, path, columns=10, pad=2):
     """[n, H, W, 3] float in [0,1] -> one PNG (rows of `columns` images), like images/rec_samples.png."""
     import numpy as np

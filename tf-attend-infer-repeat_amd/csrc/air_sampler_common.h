@@ -163,6 +163,24 @@ __device__ __forceinline__ float compose_pixel(const int* sh_act, const float* s
     return R;
 }
 
+// which step explains canvas pixel (i, j): the terms compose_pixel adds for it (the same operations in the same order),
+// compared instead of summed -- the first active step whose term is strictly above `best` and above every earlier one;
+// t + 1, or 0 where no term is above `best` (a NaN term never is).  air_segmentation's predicted instance label
+__device__ __forceinline__ int compose_label(const int* sh_act, const float* sh_z, const Tap* sh_tx, const Tap* sh_ty,
+                                             const float* sh_win, int N, int C, int w, int i, int j, float best) {
+    int label = 0;
+    for (int t = 0; t < N; ++t) {
+        if (!sh_act[t]) continue;
+        const Tap tx = sh_tx[(size_t)t * C + j], ty = sh_ty[(size_t)t * C + i];
+        const float* win = sh_win + (size_t)t * w * w;
+        const float wr = bilinear4(tx, ty, win[ty.i0 * w + tx.i0], win[ty.i1 * w + tx.i0],
+                                   win[ty.i0 * w + tx.i1], win[ty.i1 * w + tx.i1]);
+        const float c = sh_z[t] * wr;
+        if (c > best) { best = c; label = t + 1; }
+    }
+    return label;
+}
+
 // clipped_rec :582 of running_recon R (returned), and the arguments of the two logs of the Bernoulli cross-entropy :586-589
 __device__ __forceinline__ float compose_clip(float R, float& p1, float& p0) {
     const float r = fmaxf(fminf(R, 1.0f), 0.0f);

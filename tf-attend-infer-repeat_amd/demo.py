@@ -11,6 +11,9 @@ images/rec_samples.png) and a JSON with the inferred digit counts and [s, x, y] 
 --generate N needs no data: N scenes are drawn from the model's priors and rendered on the device (AIRModel.generate);
 it writes generated_samples.png ([scene | scene + attention boxes]) and generated.json.
 
+--segmentation also writes segmentation_samples.png: [input | predicted instance masks], every pixel in the colour of the
+object that explains it (air.metrics.Segmentation; red, green, blue for the first, second, third step).
+
 The interactive tkinter window (demo/demo_window.py, pixel_canvas.py) is out of scope.
 """
 import argparse
@@ -21,7 +24,7 @@ import numpy as np
 import torch
 
 from air.air_model import AIRModel, saved_cnn_arguments
-from air.visualize import save_image_grid, visualize_reconstructions, visualize_scenes
+from air.visualize import colour_masks, save_image_grid, visualize_reconstructions, visualize_scenes
 from demo.model_wrapper import ModelWrapper
 
 CANVAS_SIZE = 50
@@ -41,6 +44,10 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="--generate: seed of the device noise stream")
     ap.add_argument("--prior-log-odds", type=float, default=None,
                     help="--generate: z_pres prior log-odds (default: the model's constructor value)")
+    ap.add_argument("--segmentation", action="store_true",
+                    help="also write segmentation_samples.png: the inputs beside the predicted instance masks")
+    ap.add_argument("--segmentation-threshold", type=float, default=0.5,
+                    help="--segmentation: an object claims a pixel where its part of the reconstruction is above this")
     args = ap.parse_args()
 
     dev = torch.device("cuda", 0)
@@ -88,6 +95,15 @@ def main():
         json.dump(rows, f, indent=1)
     acc = float(np.mean([r["target_digits"] == r["inferred_digits"] for r in rows]))
     print("wrote %s and inference.json (%d images, digit-count accuracy %.3f)" % (png, n, acc))
+    if args.segmentation:
+        from air.metrics import Segmentation
+        seg = Segmentation(air_model, 1, pred_threshold=args.segmentation_threshold, keep=True)
+        seg.update(torch.zeros(n, CANVAS_SIZE ** 2, dtype=torch.uint8, device=dev))      # (no truth here: the labels are the point)
+        plain = air_model.input_images.reshape(n, CANVAS_SIZE, CANVAS_SIZE)
+        left = torch.stack([plain, plain, plain], dim=3)
+        stripe = torch.ones(n, CANVAS_SIZE, 2, 3, device=dev)
+        grid = torch.cat([left, stripe, colour_masks(seg.pred_mask, air_model.input_images)], dim=2)
+        print("wrote %s" % save_image_grid(grid, os.path.join(args.out, "segmentation_samples.png"), columns=10))
 
 
 def generate(args, air_model, wrapper, dev):

@@ -61,6 +61,8 @@ TEST_DATA_FILE = "multi_mnist_data/test.npz"
 # --localization: what a row of scalars.jsonl gains (as loc_<name>) and TensorBoard shows (as localization/<name>); the
 # sixth number of air.metrics.Localization, count_accuracy, is the row's `accuracy`
 LOCALIZATION_KEYS = ("mean_iou", "recall", "precision", "cover", "center_dist")
+# --segmentation: likewise seg_<name> and segmentation/<name>, the four numbers of air.metrics.Segmentation
+SEGMENTATION_KEYS = ("fg_ari", "mask_iou", "fg_missed", "bg_claimed")
 
 
 def load_background(bg_path="", bg_max_intensity=1.0):
@@ -111,10 +113,11 @@ def load_data(bg_path="", bg_max_intensity=1.0, truth=False):
     return out + (ds["test_positions"], ds["test_boxes"]) if truth else out
 
 
-def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=False):
+def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=False, masks=False):
     """--glyph-style mnist-like: TEST_SET_SIZE scenes composed once on the device from one handwriting bank with a seed of its
     own -> (images, digits) as numpy arrays; the bank and the source are dropped.  truth: and source.meta()'s positions and
-    boxes, int32 [n, max_digits, 2]"""
+    boxes, int32 [n, max_digits, 2].  masks: and, last, the scenes' instance labels, uint8 [n, CANVAS_SIZE^2]
+    (air.metrics.Segmentation.scene_masks: made here, while the bank's glyph table is still the one the scenes came from)"""
     images = torch.zeros(TEST_SET_SIZE, CANVAS_SIZE ** 2, device=dev)
     digits = torch.zeros(TEST_SET_SIZE, dtype=torch.int32, device=dev)
     bank, _ = handwriting_bank(variants, 0x54455354 + seed, dev)
@@ -126,6 +129,9 @@ def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=Fals
     if truth:
         meta = source.meta()
         out += tuple(meta[k].cpu().numpy().reshape(TEST_SET_SIZE, -1, 2) for k in ("positions", "boxes"))
+    if masks:
+        from air.metrics import Segmentation
+        out += (Segmentation.scene_masks(source, digits).cpu().numpy(),)
     return out
 
 
@@ -135,10 +141,13 @@ class SummaryWriter:
     launch into a device vector; the vector is copied into a pinned host ring without blocking and a row is written
     when the NEXT evaluation has been enqueued, so the host never waits for the step it has just launched."""
 
-    def __init__(self, model, path, t0, slots=2, on_row=None, localization=None, on_localization=None):
+    def __init__(self, model, path, t0, slots=2, on_row=None, localization=None, on_localization=None, segmentation=None,
+                 on_segmentation=None):
         """localization: (air.metrics.Localization of `model`, (gt_count, gt_positions, gt_boxes) on the device) -- every
         evaluation is then also scored against the ground truth (reset + update + values: a few launches behind the
-        summaries one, fetched through the same ring) and the row gains the loc_* keys; on_localization(step, values)"""
+        summaries one, fetched through the same ring) and the row gains the loc_* keys; on_localization(step, values).
+        segmentation: (air.metrics.Segmentation of `model`, the label planes on the device), in the same way: seg_* keys,
+        on_segmentation(step, values)"""
         self.model, self.t0, self.on_row = model, t0, on_row
         self.names = model.summary_names()
         self.dev = torch.empty(len(self.names), dtype=torch.float32, device=model.input_images.device)
@@ -149,6 +158,10 @@ class SummaryWriter:
         if localization is not None:
             self.loc_names = localization[0].names()
             self.loc_host = torch.empty(slots, len(self.loc_names), dtype=torch.float64).pin_memory()
+        self.seg, self.on_segmentation = segmentation, on_segmentation
+        if segmentation is not None:
+            self.seg_names = segmentation[0].names()
+            self.seg_host = torch.empty(slots, len(self.seg_names), dtype=torch.float64).pin_memory()
 
     def push(self, step):
         slot = self.k % len(self.events)
@@ -160,6 +173,11 @@ class SummaryWriter:
             loc.reset()
             loc.update(*truth)
             self.loc_host[slot].copy_(loc.values(), non_blocking=True)
+        if self.seg is not None:
+            seg, planes = self.seg
+            seg.reset()
+            seg.update(planes)
+            self.seg_host[slot].copy_(seg.values(), non_blocking=True)
         self.events[slot].record()
         self.pending.append((slot, step))
         while len(self.pending) > 1:
@@ -173,12 +191,17 @@ class SummaryWriter:
         if self.loc is not None:
             located = dict(zip(self.loc_names, self.loc_host[slot].tolist()))
             row.update({"loc_" + k: (round(located[k], 5) if located[k] == located[k] else None) for k in LOCALIZATION_KEYS})
+        if self.seg is not None:
+            segmented = dict(zip(self.seg_names, self.seg_host[slot].tolist()))
+            row.update({"seg_" + k: (round(segmented[k], 5) if segmented[k] == segmented[k] else None) for k in SEGMENTATION_KEYS})
         self.file.write(json.dumps(row) + "\n")
         self.file.flush()
         if self.on_row is not None:
             self.on_row(step, self.host[slot].tolist())
         if self.loc is not None and self.on_localization is not None:
             self.on_localization(step, [located[k] for k in LOCALIZATION_KEYS])
+        if self.seg is not None and self.on_segmentation is not None:
+            self.on_segmentation(step, [segmented[k] for k in SEGMENTATION_KEYS])
 
     def flush(self):
         while self.pending:
@@ -236,6 +259,10 @@ class TensorBoardWriter:
     def localization(self, step, values):
         """--localization: the five LOCALIZATION_KEYS of the evaluation at `step`"""
         self.events.add_scalars(step, [("localization/" + k, v) for k, v in zip(LOCALIZATION_KEYS, values)])
+
+    def segmentation(self, step, values):
+        """--segmentation: the four SEGMENTATION_KEYS of the evaluation at `step`"""
+        self.events.add_scalars(step, [("segmentation/" + k, v) for k, v in zip(SEGMENTATION_KEYS, values)])
 
     def variables(self, step):
         from air.summaries import decode_histograms
@@ -341,7 +368,21 @@ def main():
                              "rows of summary/scalars.jsonl gain loc_* keys, --tensorboard gains localization/* scalars, and the "
                              "run ends with the confusion matrix of the counts")
     parser.add_argument("--localization-iou", type=float, default=0.5, help="--localization: the IoU from which a matched box is a hit")
+    parser.add_argument("--segmentation", action="store_true",
+                        help="score the test model's decomposition per pixel at every evaluation (air.metrics.Segmentation: "
+                             "foreground adjusted Rand index, best mask IoU per digit, ink missed, background claimed) against "
+                             "the instance masks of the test set: the rows of summary/scalars.jsonl gain seg_* keys and "
+                             "--tensorboard gains segmentation/* scalars.  Needs --glyph-style mnist-like: the masks come from "
+                             "the glyph table of the source that composes the test set on the device")
+    parser.add_argument("--segmentation-threshold", type=float, default=0.5,
+                        help="--segmentation: an object claims a pixel where its part of the reconstruction is above this")
     args = parser.parse_args()
+    if args.segmentation and not 0.0 <= args.segmentation_threshold < 1.0:
+        parser.error("--segmentation-threshold must lie in [0, 1)")
+    if args.segmentation and args.glyph_style != "mnist-like":
+        parser.error("--segmentation needs a test set composed on the device (--online-data --glyph-style mnist-like): the "
+                     "instance masks come from the glyph table of the composing source, which a host-generated or cached "
+                     "test set does not have")
     if args.localization and not 0.0 < args.localization_iou <= 1.0:
         parser.error("--localization-iou must lie in (0, 1]")
     if args.localization and args.glyph_style != "mnist-like" and cache_without_truth():
@@ -378,12 +419,16 @@ def main():
     if mnist_like:                                                   # no host generator: the test set is device work too
         te_im, te_dg, *te_truth = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin,
                                                   args.digit_gap, load_background(args.bg_path, args.bg_max_intensity),
-                                                  truth=args.localization)
+                                                  truth=args.localization, masks=args.segmentation)
+        if args.segmentation:
+            *te_truth, te_masks = te_truth
     else:
         tr_im, tr_dg, te_im, te_dg, *te_truth = load_data(args.bg_path, args.bg_max_intensity, truth=args.localization)
     if args.localization:                                            # the ground truth follows the images' permutation
         order = shift_zero_digits_order(te_dg)
         te_truth = [torch.tensor(np.ascontiguousarray(a[order]).astype(np.int32), device=dev) for a in te_truth]
+    if args.segmentation:                                            # ... and so do the instance masks
+        te_masks = torch.tensor(np.ascontiguousarray(te_masks[shift_zero_digits_order(te_dg)]), device=dev)
     te_im, te_dg = shift_zero_digits_images(te_im, te_dg)
     if not args.online_data:
         train_images = torch.tensor(tr_im, device=dev)
@@ -472,8 +517,13 @@ def main():
     if args.localization:
         from air.metrics import Localization
         located = (Localization(test_model, int(te_truth[0].shape[1]), args.localization_iou), (test_targets, *te_truth))
+    segmented = None
+    if args.segmentation:
+        from air.metrics import Segmentation
+        segmented = (Segmentation(test_model, args.online_max_digits, args.segmentation_threshold), te_masks)
     writer = SummaryWriter(test_model, summaries_folder + "scalars.jsonl", t0, on_row=board.numeric if board else None,
-                           localization=located, on_localization=board.localization if board else None)
+                           localization=located, on_localization=board.localization if board else None,
+                           segmentation=segmented, on_segmentation=board.segmentation if board else None)
     while step < total:
         if step % NUM_SUMMARIES_EACH_ITERATIONS == 0:
             test_model.forward()
@@ -519,6 +569,13 @@ def main():
         print("count confusion (rows: digits present 0..{}, columns: objects inferred 0..{}):".format(loc.G, loc.T))
         for row in res["confusion"]:
             print("  " + " ".join("{:6d}".format(int(v)) for v in row))
+    if segmented:
+        seg, planes = segmented
+        seg.reset()
+        seg.update(planes)
+        res = seg.result()
+        print("segmentation at {:g}: ".format(seg.pred_threshold) + "  ".join(
+            "{} {:.4f}".format(k, res[k]) for k in SEGMENTATION_KEYS))
     if args.online_data:
         print("online data: {} batches composed on the device, {} canvases given up".format(
             int(batches.counter), int(batches.gave_up())) + ("" if bank is None else
