@@ -1335,6 +1335,88 @@ int air_segmentation(const air_segmentation_t* args, void* workspace, void* stre
 /* bytes of `workspace`, or AIR_EINVAL / AIR_ELIMIT for a (T, B, k, G) the entry point refuses -- no GPU is touched */
 int64_t air_segmentation_workspace_bytes(int T, int B, int k, int G);
 
+/* ---- latent probe (additive to ABI 6) --------------------------------------------------------------------------------------
+ * What do the what-codes say?  Two label-based, training-free measurements of a set of latent codes (the posterior means
+ * air_embed_collect gathers): the leave-one-out k-nearest-neighbour accuracy of their labels with its confusion matrix, and
+ * the number of ACTIVE UNITS, the dimensions whose value varies over the set (Burda et al., Importance Weighted Autoencoders:
+ * variance > 0.01).  air/metrics.py (LatentProbe) and air/embeddings.py (probe) are the callers;
+ * tests/latent_probe_cases.py restates every operation below.  All arithmetic is fp64 in exactly the order written here (the
+ * translation unit has -ffp-contract=off).
+ *
+ * Rows.  M_eff = rows ? clamp(*rows, 0, M) : M -- `rows` points to ONE device int32 (a collector's cursor,
+ * counters[AIR_EMBED_MATCHED], can be passed without a host read).  Rows >= M_eff of latents and labels are never read; the
+ * launches are sized by M.  x[i][z] = latents[i * Z + z]; rows are only 4-byte aligned and are read float by float.
+ * Row i < M_eff is VALID when all its Z values are finite and 0 <= labels[i] < classes.  An invalid row is neither a query
+ * nor a neighbour.  V = the number of valid rows.
+ *
+ * Squared distance of two valid rows:  d2(i, j) = (((+0.0 + e_0 * e_0) + e_1 * e_1) + ...), z ascending,
+ *   e_z = (double)x[i][z] - (double)x[j][z].
+ * No square root (the order is defined on d2), never the |a|^2 + |b|^2 - 2 a.b form; d2(i, j) == d2(j, i) bit for bit.
+ *
+ * Neighbours of a valid row i: the valid rows j != i ordered by (d2 ascending, then j ascending); the first
+ * kk = min(k, V - 1) are kept.  kk == 0: the row is UNSCORED.  The order is total, so the result does not depend on how the
+ * kernels partition the rows (AIR_PROBE_QUERY_TILE, AIR_PROBE_REF_TILE, AIR_PROBE_PASS_ROWS and air_latent_probe_splits are
+ * facts of the launch, exported for the tests, not of the result).
+ * Vote: votes[c] = the neighbours with label c; the class with the most votes wins, a tie goes to the tied class whose first
+ * member comes earliest in the neighbour order.  pred[i] = that class.
+ *
+ * Outputs: EVERY element is written on EVERY call (nothing accumulates: k-NN is a whole-set operation).
+ *   pred [M] (nullable): the class, -1 for an invalid row, an unscored row and a row >= M_eff.
+ *   neighbours [M, k], neighbour_d2 [M, k] (nullable TOGETHER): the kept rows in order and their d2, then -1 and +0.0.
+ *   counts[AIR_PROBE_ROWS] = M_eff, [VALID] = V, [SCORED] = scored rows, [CORRECT] = those with pred == label,
+ *   [ACTIVE_UNITS] (below), then counts[AIR_PROBE_COUNTS + label * classes + pred] = the scored rows with that label and that
+ *   prediction (truth x predicted).  Integer atomics: any order, the same sums.
+ *   moments [2 Z]: mean_z at [z], var_z at [Z + z], over the valid rows:
+ *     S_z = the sum of (double)x[i][z] in the ONE order of air_localization's sums: rows in groups of AIR_LOC_GROUP, each folded
+ *     by the adjacent pairwise tree (v[m] = v[2 m] + v[2 m + 1], eight times), +0.0 for an absent or invalid row; the group
+ *     totals added one by one from +0.0 in group order.   mean_z = S_z / (double)V.
+ *     Q_z = the sum of (x - mean_z) * (x - mean_z) in the same order (+0.0 for an absent or invalid row).  var_z = Q_z / V.
+ *   counts[AIR_PROBE_ACTIVE_UNITS] = the z with var_z > au_threshold.  V == 0: every mean and variance is the quiet NaN
+ *   0x7FF8000000000000 and ACTIVE_UNITS is 0.
+ * No floating-point atomics anywhere: the same inputs give the same bits.
+ *
+ * Four launches on the caller's stream, no synchronisation, no host read: validity flags (a thread per row; zeroes counts);
+ * moments (a workgroup per dimension); pairs (a workgroup per AIR_PROBE_QUERY_TILE queries x one of
+ * air_latent_probe_splits(M) contiguous runs of AIR_PROBE_REF_TILE-row reference tiles; each of its four waves takes
+ * AIR_PROBE_PASS_ROWS rows of every tile for all the queries, the four lists are merged in the workgroup, and each query's k
+ * best of the run go to the workspace); merge, vote and count (a thread per row).
+ *
+ * Refusals, on the host before any HIP call, in this order.  AIR_EINVAL: a null descriptor; M, Z, k or classes < 1;
+ * au_threshold negative or NaN.  AIR_ELIMIT: k > AIR_PROBE_MAX_K, classes > AIR_PROBE_MAX_CLASSES, Z > AIR_PROBE_MAX_Z,
+ * M > AIR_PROBE_MAX_ROWS.  AIR_EINVAL: a null latents, labels, counts, moments or workspace; exactly one of neighbours /
+ * neighbour_d2 null.  AIR_EALIGN: moments, neighbour_d2 or the workspace not 8-byte aligned. */
+#define AIR_PROBE_MAX_K 16
+#define AIR_PROBE_MAX_CLASSES 64
+#define AIR_PROBE_MAX_Z 256
+#define AIR_PROBE_MAX_ROWS 32768
+#define AIR_PROBE_QUERY_TILE 64
+#define AIR_PROBE_REF_TILE 32
+#define AIR_PROBE_MAX_SPLITS 8
+#define AIR_PROBE_PASS_ROWS 8
+enum { AIR_PROBE_ROWS = 0, AIR_PROBE_VALID = 1, AIR_PROBE_SCORED = 2, AIR_PROBE_CORRECT = 3, AIR_PROBE_ACTIVE_UNITS = 4,
+       AIR_PROBE_COUNTS = 5 };
+typedef struct {
+    const float* latents;                /* [M, Z]                                                                      */
+    const int32_t* labels;               /* [M]                                                                         */
+    const int32_t* rows;                 /* nullable: ONE device int32, the rows in use (clamped to [0, M])             */
+    int32_t* pred;                       /* out [M], nullable                                                           */
+    int32_t* neighbours;                 /* out [M, k], nullable with neighbour_d2                                      */
+    double* neighbour_d2;                /* out [M, k], nullable with neighbours                                        */
+    int64_t* counts;                     /* out [AIR_PROBE_COUNTS + classes * classes]                                  */
+    double* moments;                     /* out [2 Z]: means, then variances                                            */
+    int32_t M, Z, k, classes;
+    double au_threshold;
+} air_latent_probe_t;
+/* `workspace`: a device buffer of at least air_latent_probe_workspace_bytes(M, Z, k) bytes, 8-byte aligned (the partial
+ * neighbour lists of every split and the validity flags) */
+int air_latent_probe(const air_latent_probe_t* args, void* workspace, void* stream);
+/* bytes of `workspace`, or AIR_EINVAL / AIR_ELIMIT for an (M, Z, k) the entry point refuses -- no GPU is touched */
+int64_t air_latent_probe_workspace_bytes(int M, int Z, int k);
+/* the reference runs the pairs launch splits M rows into: min(AIR_PROBE_MAX_SPLITS, ceil(M / AIR_PROBE_REF_TILE)); run s
+ * holds the reference tiles [s * tps, (s + 1) * tps), tps = ceil(tiles / splits).  AIR_EINVAL: M < 1; AIR_ELIMIT: M >
+ * AIR_PROBE_MAX_ROWS -- no GPU is touched */
+int air_latent_probe_splits(int M);
+
 #ifdef __cplusplus
 }
 #endif

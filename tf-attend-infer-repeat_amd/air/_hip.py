@@ -272,6 +272,19 @@ class Segmentation(C.Structure):
                 ("T", _i), ("B", _i), ("k", _i), ("G", _i), ("C", _i), ("w", _i), ("pred_threshold", _f)]
 
 
+PROBE_MAX_K, PROBE_MAX_CLASSES, PROBE_MAX_Z, PROBE_MAX_ROWS = 16, 64, 256, 32768
+PROBE_QUERY_TILE, PROBE_REF_TILE, PROBE_MAX_SPLITS, PROBE_PASS_ROWS = 64, 32, 8, 8     # facts of the pairs launch
+PROBE_ROWS, PROBE_VALID, PROBE_SCORED, PROBE_CORRECT, PROBE_ACTIVE_UNITS, PROBE_COUNTS = 0, 1, 2, 3, 4, 5
+
+
+class LatentProbe(C.Structure):
+    """air_latent_probe_t: latent codes and their labels in (rows: a nullable device int32, how many are in use), the
+    optional per-row outputs, the int64 counts with the confusion matrix and the fp64 moments out -- all written whole"""
+    _fields_ = [("latents", _p), ("labels", _p), ("rows", _p), ("pred", _p), ("neighbours", _p), ("neighbour_d2", _p),
+                ("counts", _p), ("moments", _p), ("M", _i), ("Z", _i), ("k", _i), ("classes", _i),
+                ("au_threshold", C.c_double)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -363,6 +376,9 @@ _SIGNATURES = {
     "air_scene_masks": (C.c_int, [C.POINTER(SceneMasks), _p]),
     "air_segmentation": (C.c_int, [C.POINTER(Segmentation), _p, _p]),
     "air_segmentation_workspace_bytes": (C.c_int64, [C.c_int] * 4),
+    "air_latent_probe": (C.c_int, [C.POINTER(LatentProbe), _p, _p]),
+    "air_latent_probe_workspace_bytes": (C.c_int64, [C.c_int] * 3),
+    "air_latent_probe_splits": (C.c_int, [C.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -99,6 +99,8 @@ KERNEL_NAMES = {
     "air_localization": "loc_match_kernel",                             # (air.metrics.Localization; then loc_fold_kernel)
     "air_segmentation": "seg_image_kernel",                             # (air.metrics.Segmentation; then seg_fold_kernel)
     "air_scene_masks": "scene_masks_kernel",                            # (Segmentation.scene_masks)
+    "air_latent_probe": "probe_pairs_kernel",                           # (air.metrics.LatentProbe; probe_valid / probe_moments
+    #                                                                      before, probe_merge after; the *16_kernel pair for k > 8)
 }
 
 

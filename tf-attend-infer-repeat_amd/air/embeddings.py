@@ -125,6 +125,41 @@ def sprite_sheet(windows):
     return plane
 
 
+def probe(result, k=5, classes=10, au_threshold=0.01):
+    """What the projector shows, as numbers: the leave-one-out k-nearest-neighbour accuracy of result.labels over
+    result.latents, its confusion matrix and the active units (one air_latent_probe call: air.metrics has the dict's keys).
+    result: an Embeddings with at least one row, on the device."""
+    from .metrics import _ProbeBuffers
+    latents, labels = result.latents, result.labels
+    H.require_device(latents, "latents", "embeddings.probe", capture_too=True)
+    H.require_device(labels, "labels", "embeddings.probe")
+    if latents.dim() != 2 or latents.dtype != torch.float32 or labels.dtype != torch.int32 or labels.dim() != 1 \
+            or labels.shape[0] != latents.shape[0] or labels.device != latents.device:
+        raise ValueError("embeddings.probe: latents must be float32 [M, Z] and labels int32 [M] on one device")
+    M, Z = int(latents.shape[0]), int(latents.shape[1])
+    if M < 1:
+        raise ValueError("embeddings.probe: no matched digits, nothing to probe")
+    buffers = _ProbeBuffers("embeddings.probe", latents.device, M, Z, k, classes, au_threshold, False).allocate()
+    buffers.run(latents.contiguous(), labels.contiguous())
+    return buffers.summary()
+
+
+def write_probe(folder, summary, name="latent_probe.json"):
+    """probe()'s dict as JSON beside the projector files; returns the path"""
+    import json
+    nan = lambda v: None if v != v else v                                       # noqa: E731
+    row = {key: (nan(v) if isinstance(v, float) else v) for key, v in summary.items() if not isinstance(v, np.ndarray)}
+    row["confusion"] = summary["confusion"].tolist()
+    for key in ("recall", "mean", "variance"):
+        row[key] = [nan(float(v)) for v in summary[key]]
+    path = os.path.join(os.path.abspath(folder), name)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(row, f, indent=1)
+        f.write("\n")
+    return path
+
+
 def _host(t):
     return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 

@@ -24,7 +24,17 @@ the foreground adjusted Rand index and the best mask IoU of every ground-truth o
     masks = Segmentation.scene_masks(source, digits)    # uint8 [B, C * C] from the glyph table of a DeviceSceneSource
     test_model.forward()
     seg.update(masks)
-    seg.values()                                        # float64 [4] on the device: fg_ari, mask_iou, fg_missed, bg_claimed"""
+    seg.values()                                        # float64 [4] on the device: fg_ari, mask_iou, fg_missed, bg_claimed
+
+``LatentProbe(model, max_gt_digits)`` asks the third question: do the what-codes say WHAT the digits are?  ``update()`` collects
+the latent means of the digits the pass matched (one air_embed_collect call), ``score()`` is one air_latent_probe call over
+them: exact leave-one-out k-nearest-neighbour digit accuracy with its confusion matrix, and the active units.
+
+    probe = LatentProbe(test_model, max_gt_digits=2)
+    test_model.forward()
+    probe.update(gt_count, gt_positions, gt_boxes, gt_labels)
+    probe.score()
+    probe.values()                                      # float64 [4] on the device: knn_accuracy, active_units, scored, matched_share"""
 import ctypes as C
 
 import numpy as np
@@ -254,3 +264,180 @@ class Segmentation:
                          B, Gn, gd, Cc, md, float(ink_threshold))
         H.launch("air_scene_masks", glyphs.device, C.byref(a))
         return mask
+
+
+PROBE_NAMES = ("knn_accuracy", "active_units", "scored", "matched_share")
+
+
+class _ProbeBuffers:
+    """the outputs and the workspace of air_latent_probe for up to M rows of Z dimensions, and the one call"""
+
+    def __init__(self, op, dev, M, Z, k, classes, au_threshold, per_row):
+        k, classes, au = int(k), int(classes), float(au_threshold)
+        if k < 1 or classes < 1 or M < 1 or Z < 1:
+            raise ValueError("%s: k, classes, the rows and their dimensions must be positive" % op)
+        if not au >= 0.0:
+            raise ValueError("%s: au_threshold must not be negative" % op)
+        if k > H.PROBE_MAX_K or classes > H.PROBE_MAX_CLASSES or Z > H.PROBE_MAX_Z or M > H.PROBE_MAX_ROWS:
+            raise NotImplementedError("%s: %d neighbours, %d classes, %d dimensions, %d rows: the kernel holds %d, %d, %d and %d"
+                                      % (op, k, classes, Z, M, H.PROBE_MAX_K, H.PROBE_MAX_CLASSES, H.PROBE_MAX_Z, H.PROBE_MAX_ROWS))
+        nbytes = H.lib().air_latent_probe_workspace_bytes(M, Z, k)
+        if nbytes < 0:
+            H.check(int(nbytes), "air_latent_probe_workspace_bytes")
+        self.op, self.device, self.M, self.Z, self.k, self.classes, self.au_threshold = op, dev, M, Z, k, classes, au
+        self.nbytes = int(nbytes)
+        self.per_row = bool(per_row)
+
+    def allocate(self):
+        dev, M = self.device, self.M
+        self.counts = torch.zeros(H.PROBE_COUNTS + self.classes * self.classes, dtype=torch.int64, device=dev)
+        self.moments = torch.full((2 * self.Z,), float("nan"), dtype=torch.float64, device=dev)
+        self.workspace = torch.empty(self.nbytes // 8, dtype=torch.float64, device=dev)
+        self.pred = torch.full((M,), -1, dtype=torch.int32, device=dev) if self.per_row else None
+        self.neighbours = torch.full((M, self.k), -1, dtype=torch.int32, device=dev) if self.per_row else None
+        self.neighbour_d2 = torch.zeros(M, self.k, dtype=torch.float64, device=dev) if self.per_row else None
+        return self
+
+    def run(self, latents, labels, rows=None):
+        """one air_latent_probe call on the current stream; rows: a device int32 tensor whose first element says how many
+        rows are in use, or None for all M"""
+        a = H.LatentProbe(H.ptr(latents), H.ptr(labels), H.ptr(rows), H.ptr(self.pred), H.ptr(self.neighbours),
+                          H.ptr(self.neighbour_d2), H.ptr(self.counts), H.ptr(self.moments), self.M, self.Z, self.k, self.classes,
+                          self.au_threshold)
+        H.launch("air_latent_probe", self.device, C.byref(a), H.ptr(self.workspace))
+
+    def summary(self):
+        """the counts, the confusion matrix, the per-class recall and the moments as a dict of host values -- synchronises"""
+        counts, moments, n = self.counts.cpu().numpy(), self.moments.cpu().numpy(), self.classes
+        confusion = counts[H.PROBE_COUNTS:].reshape(n, n).copy()
+        truth = confusion.sum(axis=1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            recall = np.where(truth == 0, np.nan, np.diag(confusion) / truth.astype(np.float64))
+        scored, correct = int(counts[H.PROBE_SCORED]), int(counts[H.PROBE_CORRECT])
+        return dict(knn_accuracy=correct / scored if scored else float("nan"), active_units=int(counts[H.PROBE_ACTIVE_UNITS]),
+                    scored=scored, correct=correct, rows=int(counts[H.PROBE_ROWS]), valid=int(counts[H.PROBE_VALID]),
+                    k=self.k, classes=n, au_threshold=self.au_threshold, confusion=confusion, recall=recall,
+                    mean=moments[:self.Z].copy(), variance=moments[self.Z:].copy())
+
+
+class LatentProbe:
+    """Do the what-codes say WHAT the digits are?  The latent codes (posterior means) of the matched digits of an evaluation
+    set, scored by air_latent_probe (include/air_hip.h has the semantics): the leave-one-out k-nearest-neighbour accuracy of
+    their labels with its confusion matrix, and the active units (dimensions whose mean varies over the set, variance >
+    au_threshold).  fp64 in a fixed order; nothing blocks but result().
+
+        probe = LatentProbe(test_model, max_gt_digits=2)
+        test_model.forward()
+        probe.update(gt_count, gt_positions, gt_boxes, gt_labels)   # one air_embed_collect call: the projector export's match
+        probe.score()                                               # one air_latent_probe call over the rows collected so far
+        probe.values()                                              # float64 [4] on the device, names() order
+
+    knn_accuracy = CORRECT / SCORED, active_units and scored as counted, matched_share = MATCHED / PRESENT (the share of the
+    ground-truth digits that were matched to an inferred object, and so probed); a zero denominator gives NaN.  The rows
+    live in the probe's own store ``latents`` [capacity, Z] / ``labels`` [capacity] with the collector's device counters as
+    the cursor; capacity defaults to batch_size * max_gt_digits (one pass), and digits beyond it set the overflow flag that
+    result() reports.  per_row=True keeps ``pred`` [capacity], ``neighbours`` and ``neighbour_d2`` [capacity, k] of the last
+    score()."""
+
+    def __init__(self, model, max_gt_digits, classes=10, k=5, capacity=None, au_threshold=0.01, per_row=False, max_distance=0.2):
+        T, B, G = int(model.max_steps), int(model.batch_size), int(max_gt_digits)
+        Z, w = int(model.vae_latent_dimensions), int(model.windows_size)
+        if G < 1:
+            raise ValueError("LatentProbe: max_gt_digits must be positive")
+        capacity = B * G if capacity is None else int(capacity)
+        if capacity < 1:
+            raise ValueError("LatentProbe: capacity must be positive")
+        if not float(max_distance) > 0.0:
+            raise ValueError("LatentProbe: max_distance must be positive")
+        self.buffers = _ProbeBuffers("LatentProbe", None, capacity, Z, k, classes, au_threshold, per_row)
+        nints = H.lib().air_embed_collect_workspace_ints(T, B, B, G)
+        if nints < 0:
+            raise NotImplementedError("LatentProbe: %d steps, %d digits in one image: the collector holds %d and %d"
+                                      % (T, G, H.EMBED_MAX_STEPS, H.EMBED_MAX_DIGITS))
+        H.require_device(model.input_images, "the model's input buffer", "LatentProbe", capture_too=True)
+        dev = self.device = self.buffers.device = model.input_images.device
+        self.model, self.T, self.B, self.G, self.Z, self.w = model, T, B, G, Z, w
+        self.k, self.classes, self.capacity, self.max_distance = self.buffers.k, self.buffers.classes, capacity, float(max_distance)
+        self.buffers.allocate()
+        self.counts, self.moments = self.buffers.counts, self.buffers.moments
+        self.pred, self.neighbours, self.neighbour_d2 = self.buffers.pred, self.buffers.neighbours, self.buffers.neighbour_d2
+        self.latents = torch.zeros(capacity, Z, dtype=torch.float32, device=dev)
+        self.labels = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        self.counters = torch.zeros(H.EMBED_COUNTERS, dtype=torch.int32, device=dev)
+        self._windows = torch.empty(capacity, w * w, dtype=torch.float32, device=dev)       # the collector writes them: unused
+        self._ids = torch.empty(capacity, dtype=torch.int32, device=dev)
+        self._match = torch.empty(B, G, dtype=torch.int32, device=dev)
+        self._workspace = torch.empty(int(nints), dtype=torch.int32, device=dev)
+        self._nan = torch.full((len(PROBE_NAMES),), float("nan"), dtype=torch.float64, device=dev)
+        self._one = torch.ones(1, dtype=torch.float64, device=dev)
+
+    @staticmethod
+    def names():
+        return list(PROBE_NAMES)
+
+    def reset(self):
+        """zeroes the row cursor and the counts on the current stream"""
+        self.counters.zero_()
+        self.counts.zero_()
+
+    def _truth(self, t, what, k, width):
+        if not torch.is_tensor(t):
+            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.int32)).to(self.device)
+        H.require_device(t, what, "LatentProbe.update")
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device:
+            raise ValueError("LatentProbe.update: %s must be a contiguous int32 tensor on %s" % (what, self.device))
+        if t.dim() < 1 or int(t.shape[0]) < k or t.numel() != int(t.shape[0]) * width:
+            raise ValueError("LatentProbe.update: %s must hold %d values for each of at least %d images, got %r"
+                             % (what, width, k, tuple(t.shape)))
+        return t
+
+    def update(self, gt_count, gt_positions, gt_boxes, gt_labels, k=None):
+        """One air_embed_collect call over the model's last pass: the digits of its first k images (default: all rows of
+        gt_count) matched to the inferred objects by centre distance, the latent means of the matched ones appended to the
+        store with gt_labels [>= k, G] as their labels.  gt_positions / gt_boxes: [>= k, G, 2] or [>= k, 2 G]."""
+        m = self.model
+        m._ensure()
+        H.require_device(m.att, "the model's records", "LatentProbe.update", capture_too=True)
+        if k is None:
+            k = int(gt_count.shape[0]) if hasattr(gt_count, "shape") else len(gt_count)
+        k = int(k)
+        if not 1 <= k <= self.B:
+            raise ValueError("LatentProbe.update: k = %d images, the model's batch holds %d" % (k, self.B))
+        gt = (self._truth(gt_count, "gt_count", k, 1), self._truth(gt_positions, "gt_positions", k, 2 * self.G),
+              self._truth(gt_boxes, "gt_boxes", k, 2 * self.G), self._truth(gt_labels, "gt_labels", k, self.G))
+        a = H.EmbedCollect(H.ptr(m.att), H.ptr(m.run_digits), H.ptr(m.ml), H.ptr(m.vrec), *(H.ptr(t) for t in gt), H.ptr(gt[3]),
+                           H.ptr(self._match), H.ptr(self.counters), H.ptr(self.latents), H.ptr(self._windows),
+                           H.ptr(self.labels), H.ptr(self._ids), self.T, self.B, k, self.G, self.Z, self.w, self.capacity,
+                           m.canvas_size, self.max_distance)
+        H.launch("air_embed_collect", self.device, C.byref(a), H.ptr(self._workspace))
+
+    def score(self):
+        """One air_latent_probe call over the rows collected so far (the device cursor says how many: no host read)"""
+        H.require_device(self.latents, "the store", "LatentProbe.score", capture_too=True)
+        self.buffers.run(self.latents, self.labels, self.counters[H.EMBED_MATCHED:])
+
+    def values(self, out=None):
+        """float64 [len(names())] on the device, from the counts of the last score() and the collector's counters as they
+        stand on the current stream; never blocks"""
+        c, n = self.counts.double(), self.counters.double()
+        num = torch.stack((c[H.PROBE_CORRECT], c[H.PROBE_ACTIVE_UNITS], c[H.PROBE_SCORED], n[H.EMBED_MATCHED]))
+        den = torch.stack((c[H.PROBE_SCORED], self._one[0], self._one[0], n[H.EMBED_PRESENT]))
+        v = torch.where(den == 0, self._nan, num / den)
+        if out is None:
+            return v
+        out.copy_(v)
+        return out
+
+    def confusion(self):
+        """int64 [classes, classes] view of the counts: rows the true class, columns the predicted one"""
+        return self.counts[H.PROBE_COUNTS:].view(self.classes, self.classes)
+
+    def result(self):
+        """the values as a dict of floats, the totals, the confusion matrix, the per-class recall and the moments as numpy
+        -- synchronises"""
+        values, counters = self.values().cpu().tolist(), self.counters.cpu().tolist()
+        out = self.buffers.summary()
+        out.update(zip(PROBE_NAMES, values))
+        out.update(matched=counters[H.EMBED_MATCHED], present=counters[H.EMBED_PRESENT], inferred=counters[H.EMBED_INFERRED],
+                   overflow=bool(counters[H.EMBED_OVERFLOW]), capacity=self.capacity)
+        return out

@@ -3,12 +3,14 @@ found to the ground truth and writes what TensorBoard's embedding projector open
 the latents as variable `air_mnist`, an event file, projector_config.pbtxt).
 
   python embeddings.py --model air_results/models/air-model-60000.pt [--data multi_mnist_data/test.tfrecords]
-                       [--out ./embeddings] [--max-distance 0.2] [--precision fp32] [--batch-size 64]
+                       [--out ./embeddings] [--max-distance 0.2] [--precision fp32] [--batch-size 64] [--knn 5]
 
   tensorboard --logdir ./embeddings
 
 The match, the gathering of latents and windows and the sprite sheet run on the device (air/embeddings.py).  The reference
-also reads MNIST, only to print a line; that is left out.
+also reads MNIST, only to print a line; that is left out.  --knn K scores what the projector shows as numbers
+(air.embeddings.probe: leave-one-out K-nearest-neighbour digit accuracy, confusion matrix, active units) and writes
+latent_probe.json beside the projector files.
 """
 import argparse
 import os
@@ -34,7 +36,12 @@ def main():
     ap.add_argument("--max-distance", type=float, default=0.2)
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--batch-size", type=int, default=64)
+    ap.add_argument("--knn", type=int, default=0, metavar="K",
+                    help="also score the matched latents: leave-one-out K-nearest-neighbour digit accuracy, its confusion "
+                         "matrix and the active units (air.embeddings.probe), printed and written to latent_probe.json")
     args = ap.parse_args()
+    if args.knn < 0 or args.knn > 16:
+        ap.error("--knn must lie in [1, 16] (0: no probe)")
 
     out = os.path.abspath(args.out)
     shutil.rmtree(out, ignore_errors=True)                                          # embeddings.py:145-146
@@ -75,8 +82,19 @@ def main():
 
     if result.matched == 0:
         raise SystemExit("no inferred object lies within %g of a ground-truth digit: nothing to export" % args.max_distance)
+    probed = None
+    if args.knn:
+        probed = embeddings.probe(result, k=args.knn, classes=max(10, max(label_dic) + 1))
+        print("Latent probe (leave-one-out {0}-NN over {1} matched digits):".format(args.knn, probed["scored"]))
+        print("k-NN digit accuracy: {0:.4f}".format(probed["knn_accuracy"]))
+        print("Active units (variance > {0:g}): {1} of {2}".format(probed["au_threshold"], probed["active_units"], len(probed["mean"])))
+        print("Confusion matrix (rows: true digit, columns: predicted):")
+        print(probed["confusion"])
+        print()
     print("Saving embeddings...")
     embeddings.write_projector(out, result)
+    if probed is not None:
+        embeddings.write_probe(out, probed)
 
 
 if __name__ == "__main__":

@@ -245,8 +245,9 @@ def generate_dataset(max_digits=2, images_per_digit=20000, test_set_size=1000, s
     images, digits = images[perm], digits[perm]
     # the ground truth of the test rows, carried through the same shuffle: [test_set_size, max(max_digits, 1), 2] int32
     test = perm[:test_set_size]
-    positions, boxes = ([lst for st in strata for lst in st[k]] for k in ("positions", "boxes"))
-    return dict(train_images=images[test_set_size:], train_digits=digits[test_set_size:],
+    positions, boxes, labels = ([lst for st in strata for lst in st[k]] for k in ("positions", "boxes", "labels"))
+    return dict(test_labels=padded_labels([labels[i] for i in test], digits[:test_set_size], max_digits),
+                train_images=images[test_set_size:], train_digits=digits[test_set_size:],
                 test_images=images[:test_set_size], test_digits=digits[:test_set_size], source=source,
                 test_positions=padded_truth([positions[i] for i in test], digits[:test_set_size], max_digits),
                 test_boxes=padded_truth([boxes[i] for i in test], digits[:test_set_size], max_digits))
@@ -261,6 +262,17 @@ def padded_truth(lists, digits, max_digits=None):
     for i, n in enumerate(digits):
         if n:
             out[i, :n] = np.asarray(lists[i], np.int32).reshape(-1)[:2 * n].reshape(n, 2)
+    return out
+
+
+def padded_labels(lists, digits, max_digits=None):
+    """per-image label lists -> int32 [n, G], zeros behind digits[i]; G as padded_truth has it"""
+    digits = np.asarray(digits, np.int64).reshape(-1)
+    G = max(1, int(digits.max()) if max_digits is None and len(digits) else int(max_digits or 1))
+    out = np.zeros((len(digits), G), np.int32)
+    for i, n in enumerate(digits):
+        if n:
+            out[i, :n] = np.asarray(lists[i], np.int32).reshape(-1)[:n]
     return out
 
 
@@ -850,5 +862,6 @@ if __name__ == "__main__":
              digits=np.asarray(common["digits"][:T], np.int32),
              # the test set's ground truth, [n, 2 * max_digits] as --device writes it (training.py --localization reads it)
              positions=padded_truth(common["positions"][:T], common["digits"][:T], args.max_digits).reshape(-1, 2 * max(args.max_digits, 1)),
-             boxes=padded_truth(common["boxes"][:T], common["digits"][:T], args.max_digits).reshape(-1, 2 * max(args.max_digits, 1)))
+             boxes=padded_truth(common["boxes"][:T], common["digits"][:T], args.max_digits).reshape(-1, 2 * max(args.max_digits, 1)),
+             labels=padded_labels(common["labels"][:T], common["digits"][:T], args.max_digits))   # (training.py --latent-probe)
     print("glyph source: %s; wrote %d train / %d test images" % (source, len(perm) - T, T))

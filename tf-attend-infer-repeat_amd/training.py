@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from multi_mnist import (JITTER_NEUTRAL, DeviceGlyphBank, DeviceSceneSource, ShuffleBatchQueue, generate_dataset, handwriting_bank,
-                         load_glyphs, padded_truth, shift_zero_digits_images, shift_zero_digits_order)
+                         load_glyphs, padded_labels, padded_truth, shift_zero_digits_images, shift_zero_digits_order)
 from air.air_model import AIRModel
 
 EPOCHS = 300
@@ -63,6 +63,8 @@ TEST_DATA_FILE = "multi_mnist_data/test.npz"
 LOCALIZATION_KEYS = ("mean_iou", "recall", "precision", "cover", "center_dist")
 # --segmentation: likewise seg_<name> and segmentation/<name>, the four numbers of air.metrics.Segmentation
 SEGMENTATION_KEYS = ("fg_ari", "mask_iou", "fg_missed", "bg_claimed")
+# --latent-probe: likewise lat_<name> and latents/<name>, the four numbers of air.metrics.LatentProbe
+LATENT_KEYS = ("knn_accuracy", "active_units", "scored", "matched_share")
 
 
 def load_background(bg_path="", bg_max_intensity=1.0):
@@ -88,39 +90,57 @@ def cache_without_truth():
     return None
 
 
-def load_data(bg_path="", bg_max_intensity=1.0, truth=False):
+def cache_without_labels():
+    """the cached data set load_data would read, when its test file holds no digit labels; None otherwise"""
+    if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
+        with np.load(TEST_DATA_FILE) as te:
+            if "labels" not in te.files:
+                return TEST_DATA_FILE
+    return None
+
+
+def load_data(bg_path="", bg_max_intensity=1.0, truth=False, labels=False):
     """-> train images, train digits, test images, test digits; truth: and the test set's ground-truth boxes, positions
-    (x, y) and boxes (w, h) as int32 [n, G, 2] (zeros behind an image's digits)"""
+    (x, y) and boxes (w, h) as int32 [n, G, 2] (zeros behind an image's digits); labels: and, last, the classes of the test
+    set's digits, int32 [n, G]"""
     if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
         tr, te = np.load(TRAIN_DATA_FILE), np.load(TEST_DATA_FILE)
         out = tr["images"], tr["digits"], te["images"], te["digits"]
-        if not truth:
-            return out
         n = len(te["digits"])
-        return out + (te["positions"].astype(np.int32).reshape(n, -1, 2), te["boxes"].astype(np.int32).reshape(n, -1, 2))
+        if truth:
+            out += (te["positions"].astype(np.int32).reshape(n, -1, 2), te["boxes"].astype(np.int32).reshape(n, -1, 2))
+        if labels:
+            out += (te["labels"].astype(np.int32).reshape(n, -1),)
+        return out
     rec_tr, rec_te = TRAIN_DATA_FILE.replace(".npz", ".tfrecords"), TEST_DATA_FILE.replace(".npz", ".tfrecords")
     if os.path.exists(rec_tr) and os.path.exists(rec_te):
         # the reference's own files (training.py:23-24: multi_mnist_data/common.tfrecords, test.tfrecords)
         from multi_mnist import read_test_data
         print("Reading the reference's TFRecord files...")
         tri, trd, *_ = read_test_data(rec_tr)
-        tei, ted, _, tep, teb, _ = read_test_data(rec_te)
+        tei, ted, _, tep, teb, tel = read_test_data(rec_te)
         out = tri, trd.astype(np.int32), tei, ted.astype(np.int32)
-        return out + (padded_truth(tep, ted), padded_truth(teb, ted)) if truth else out
+        if truth:
+            out += (padded_truth(tep, ted), padded_truth(teb, ted))
+        return out + (padded_labels(tel, ted),) if labels else out
     print("Generating multi-digit dataset in memory (multi_mnist.py defaults)...")
     ds = generate_dataset(bg=load_background(bg_path, bg_max_intensity))
     out = ds["train_images"], ds["train_digits"], ds["test_images"], ds["test_digits"]
-    return out + (ds["test_positions"], ds["test_boxes"]) if truth else out
+    if truth:
+        out += (ds["test_positions"], ds["test_boxes"])
+    return out + (ds["test_labels"],) if labels else out
 
 
-def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=False, masks=False):
+def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=False, masks=False, labels=False):
     """--glyph-style mnist-like: TEST_SET_SIZE scenes composed once on the device from one handwriting bank with a seed of its
     own -> (images, digits) as numpy arrays; the bank and the source are dropped.  truth: and source.meta()'s positions and
     boxes, int32 [n, max_digits, 2].  masks: and, last, the scenes' instance labels, uint8 [n, CANVAS_SIZE^2]
-    (air.metrics.Segmentation.scene_masks: made here, while the bank's glyph table is still the one the scenes came from)"""
+    (air.metrics.Segmentation.scene_masks: made here, while the bank's glyph table is still the one the scenes came from).
+    labels: and, behind the boxes, the classes of the scenes' digits, int32 [n, max_digits] (the base glyph of every variant
+    the scenes drew, read here for the same reason; 0 behind an image's digits)"""
     images = torch.zeros(TEST_SET_SIZE, CANVAS_SIZE ** 2, device=dev)
     digits = torch.zeros(TEST_SET_SIZE, dtype=torch.int32, device=dev)
-    bank, _ = handwriting_bank(variants, 0x54455354 + seed, dev)
+    bank, base_labels = handwriting_bank(variants, 0x54455354 + seed, dev)
     source = DeviceSceneSource(bank, TEST_SET_SIZE, images, digits, canvas_dim=CANVAS_SIZE, max_digits=max_digits, margin=margin,
                                gap=gap, bg=bg, seed=0x5445535453 + seed)
     bank.refresh()
@@ -129,6 +149,11 @@ def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=Fals
     if truth:
         meta = source.meta()
         out += tuple(meta[k].cpu().numpy().reshape(TEST_SET_SIZE, -1, 2) for k in ("positions", "boxes"))
+    if labels:
+        indices = source.meta()["indices"].cpu().numpy().reshape(TEST_SET_SIZE, -1)
+        of_variant = bank.labels(base_labels).astype(np.int32)
+        used = np.arange(indices.shape[1])[None, :] < out[1][:, None]
+        out += (np.where(used, of_variant[np.clip(indices, 0, len(of_variant) - 1)], 0).astype(np.int32),)
     if masks:
         from air.metrics import Segmentation
         out += (Segmentation.scene_masks(source, digits).cpu().numpy(),)
@@ -142,12 +167,13 @@ class SummaryWriter:
     when the NEXT evaluation has been enqueued, so the host never waits for the step it has just launched."""
 
     def __init__(self, model, path, t0, slots=2, on_row=None, localization=None, on_localization=None, segmentation=None,
-                 on_segmentation=None):
+                 on_segmentation=None, latent=None, on_latent=None):
         """localization: (air.metrics.Localization of `model`, (gt_count, gt_positions, gt_boxes) on the device) -- every
         evaluation is then also scored against the ground truth (reset + update + values: a few launches behind the
         summaries one, fetched through the same ring) and the row gains the loc_* keys; on_localization(step, values).
         segmentation: (air.metrics.Segmentation of `model`, the label planes on the device), in the same way: seg_* keys,
-        on_segmentation(step, values)"""
+        on_segmentation(step, values).  latent: (air.metrics.LatentProbe of `model`, (gt_count, gt_positions, gt_boxes,
+        gt_labels) on the device): reset + update + score + values, lat_* keys, on_latent(step, values)"""
         self.model, self.t0, self.on_row = model, t0, on_row
         self.names = model.summary_names()
         self.dev = torch.empty(len(self.names), dtype=torch.float32, device=model.input_images.device)
@@ -162,6 +188,10 @@ class SummaryWriter:
         if segmentation is not None:
             self.seg_names = segmentation[0].names()
             self.seg_host = torch.empty(slots, len(self.seg_names), dtype=torch.float64).pin_memory()
+        self.lat, self.on_latent = latent, on_latent
+        if latent is not None:
+            self.lat_names = latent[0].names()
+            self.lat_host = torch.empty(slots, len(self.lat_names), dtype=torch.float64).pin_memory()
 
     def push(self, step):
         slot = self.k % len(self.events)
@@ -178,6 +208,12 @@ class SummaryWriter:
             seg.reset()
             seg.update(planes)
             self.seg_host[slot].copy_(seg.values(), non_blocking=True)
+        if self.lat is not None:
+            lat, truth = self.lat
+            lat.reset()
+            lat.update(*truth)
+            lat.score()
+            self.lat_host[slot].copy_(lat.values(), non_blocking=True)
         self.events[slot].record()
         self.pending.append((slot, step))
         while len(self.pending) > 1:
@@ -194,6 +230,9 @@ class SummaryWriter:
         if self.seg is not None:
             segmented = dict(zip(self.seg_names, self.seg_host[slot].tolist()))
             row.update({"seg_" + k: (round(segmented[k], 5) if segmented[k] == segmented[k] else None) for k in SEGMENTATION_KEYS})
+        if self.lat is not None:
+            probed = dict(zip(self.lat_names, self.lat_host[slot].tolist()))
+            row.update({"lat_" + k: (round(probed[k], 5) if probed[k] == probed[k] else None) for k in LATENT_KEYS})
         self.file.write(json.dumps(row) + "\n")
         self.file.flush()
         if self.on_row is not None:
@@ -202,6 +241,8 @@ class SummaryWriter:
             self.on_localization(step, [located[k] for k in LOCALIZATION_KEYS])
         if self.seg is not None and self.on_segmentation is not None:
             self.on_segmentation(step, [segmented[k] for k in SEGMENTATION_KEYS])
+        if self.lat is not None and self.on_latent is not None:
+            self.on_latent(step, [probed[k] for k in LATENT_KEYS])
 
     def flush(self):
         while self.pending:
@@ -263,6 +304,10 @@ class TensorBoardWriter:
     def segmentation(self, step, values):
         """--segmentation: the four SEGMENTATION_KEYS of the evaluation at `step`"""
         self.events.add_scalars(step, [("segmentation/" + k, v) for k, v in zip(SEGMENTATION_KEYS, values)])
+
+    def latents(self, step, values):
+        """--latent-probe: the four LATENT_KEYS of the evaluation at `step` (a NaN, nothing scored yet, is left out)"""
+        self.events.add_scalars(step, [("latents/" + k, v) for k, v in zip(LATENT_KEYS, values) if v == v])
 
     def variables(self, step):
         from air.summaries import decode_histograms
@@ -376,7 +421,20 @@ def main():
                              "the glyph table of the source that composes the test set on the device")
     parser.add_argument("--segmentation-threshold", type=float, default=0.5,
                         help="--segmentation: an object claims a pixel where its part of the reconstruction is above this")
+    parser.add_argument("--latent-probe", action="store_true",
+                        help="score the what-codes of the test model at every evaluation (air.metrics.LatentProbe: the leave-one-"
+                             "out k-nearest-neighbour digit accuracy of the latent means of the matched digits, and the active "
+                             "units): the rows of summary/scalars.jsonl gain lat_* keys, --tensorboard gains latents/* scalars, "
+                             "and the run ends with the confusion matrix of the digits.  Needs the boxes and labels of the test set")
+    parser.add_argument("--latent-k", type=int, default=5, help="--latent-probe: the neighbours that vote (1 .. 16)")
     args = parser.parse_args()
+    if args.latent_probe and not 1 <= args.latent_k <= 16:
+        parser.error("--latent-k must lie in [1, 16]")
+    if args.latent_probe and args.glyph_style != "mnist-like" and (cache_without_truth() or cache_without_labels()):
+        parser.error("--latent-probe needs the ground-truth boxes and digit labels of the test set, and %s holds none (no "
+                     "'positions' / 'boxes' / 'labels'): regenerate the cache with multi_mnist.py (or multi_mnist.py --device N), "
+                     "which writes them, or remove it to have the data set generated in memory"
+                     % (cache_without_truth() or cache_without_labels()))
     if args.segmentation and not 0.0 <= args.segmentation_threshold < 1.0:
         parser.error("--segmentation-threshold must lie in [0, 1)")
     if args.segmentation and args.glyph_style != "mnist-like":
@@ -415,18 +473,22 @@ def main():
         os.makedirs(d)
 
     dev = torch.device("cuda", 0)
+    need_truth = args.localization or args.latent_probe
     print("Creating input pipeline...")
     if mnist_like:                                                   # no host generator: the test set is device work too
         te_im, te_dg, *te_truth = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin,
                                                   args.digit_gap, load_background(args.bg_path, args.bg_max_intensity),
-                                                  truth=args.localization, masks=args.segmentation)
+                                                  truth=need_truth, masks=args.segmentation, labels=args.latent_probe)
         if args.segmentation:
             *te_truth, te_masks = te_truth
     else:
-        tr_im, tr_dg, te_im, te_dg, *te_truth = load_data(args.bg_path, args.bg_max_intensity, truth=args.localization)
-    if args.localization:                                            # the ground truth follows the images' permutation
+        tr_im, tr_dg, te_im, te_dg, *te_truth = load_data(args.bg_path, args.bg_max_intensity, truth=need_truth,
+                                                          labels=args.latent_probe)
+    if need_truth:                                                   # the ground truth follows the images' permutation
         order = shift_zero_digits_order(te_dg)
         te_truth = [torch.tensor(np.ascontiguousarray(a[order]).astype(np.int32), device=dev) for a in te_truth]
+        if args.latent_probe:                                        # (positions, boxes | labels)
+            *te_truth, te_labels = te_truth
     if args.segmentation:                                            # ... and so do the instance masks
         te_masks = torch.tensor(np.ascontiguousarray(te_masks[shift_zero_digits_order(te_dg)]), device=dev)
     te_im, te_dg = shift_zero_digits_images(te_im, te_dg)
@@ -521,9 +583,14 @@ def main():
     if args.segmentation:
         from air.metrics import Segmentation
         segmented = (Segmentation(test_model, args.online_max_digits, args.segmentation_threshold), te_masks)
+    probed = None
+    if args.latent_probe:
+        from air.metrics import LatentProbe
+        probed = (LatentProbe(test_model, int(te_labels.shape[1]), k=args.latent_k), (test_targets, *te_truth, te_labels))
     writer = SummaryWriter(test_model, summaries_folder + "scalars.jsonl", t0, on_row=board.numeric if board else None,
                            localization=located, on_localization=board.localization if board else None,
-                           segmentation=segmented, on_segmentation=board.segmentation if board else None)
+                           segmentation=segmented, on_segmentation=board.segmentation if board else None,
+                           latent=probed, on_latent=board.latents if board else None)
     while step < total:
         if step % NUM_SUMMARIES_EACH_ITERATIONS == 0:
             test_model.forward()
@@ -576,6 +643,17 @@ def main():
         res = seg.result()
         print("segmentation at {:g}: ".format(seg.pred_threshold) + "  ".join(
             "{} {:.4f}".format(k, res[k]) for k in SEGMENTATION_KEYS))
+    if probed:
+        lat, truth = probed
+        lat.reset()
+        lat.update(*truth)
+        lat.score()
+        res = lat.result()
+        print("latent probe, {}-NN over {} matched digits: ".format(lat.k, res["scored"]) + "  ".join(
+            "{} {:.4f}".format(k, res[k]) for k in LATENT_KEYS) + ("  (the store overflowed)" if res["overflow"] else ""))
+        print("digit confusion (rows: true class 0..{}, columns: predicted):".format(lat.classes - 1))
+        for row in res["confusion"]:
+            print("  " + " ".join("{:6d}".format(int(v)) for v in row))
     if args.online_data:
         print("online data: {} batches composed on the device, {} canvases given up".format(
             int(batches.counter), int(batches.gave_up())) + ("" if bank is None else
