@@ -39,16 +39,9 @@ class Embeddings:
         self.sprites = sprites
 
 
-def _padded(lists, counts, G, width):
-    out = np.zeros((len(lists), G, width), np.int32)
-    for i, n in enumerate(counts):
-        if n:
-            out[i, :n] = np.asarray(lists[i], np.int32)[:n * width].reshape(n, width)
-    return out
-
-
 def collect(model, images, digits, indices, positions, boxes, labels, max_distance=0.2):
     """The six lists of multi_mnist.read_test_data -> Embeddings.  `model`: an inference AIRModel (train=False)."""
+    from multi_mnist import padded
     if getattr(model, "train", True):
         raise ValueError("embeddings.collect: the model must be built with train=False")
     dev = model.input_images.device
@@ -75,9 +68,8 @@ def collect(model, images, digits, indices, positions, boxes, labels, max_distan
         flat[i] = np.asarray(img, np.float32).reshape(-1)
     gt_count = np.zeros(rows, np.int32)
     gt_count[:n] = counts
-    pad = [()] * (rows - n)
-    gt = [up(a) for a in (gt_count, _padded(list(positions) + pad, gt_count, G, 2), _padded(list(boxes) + pad, gt_count, G, 2),
-                          _padded(list(labels) + pad, gt_count, G, 1), _padded(list(indices) + pad, gt_count, G, 1))]
+    gt = [up(a) for a in (gt_count, padded(positions, gt_count, 2, G), padded(boxes, gt_count, 2, G),
+                          padded(labels, gt_count, 1, G), padded(indices, gt_count, 1, G))]
     canvases = up(flat)                            # uploaded once, like the ground truth
 
     capacity = max(1, int(counts.sum()))           # every ground-truth digit matched: the rows cannot run out

@@ -34,7 +34,11 @@ them: exact leave-one-out k-nearest-neighbour digit accuracy with its confusion 
     test_model.forward()
     probe.update(gt_count, gt_positions, gt_boxes, gt_labels)
     probe.score()
-    probe.values()                                      # float64 [4] on the device: knn_accuracy, active_units, scored, matched_share"""
+    probe.values()                                      # float64 [4] on the device: knn_accuracy, active_units, scored, matched_share
+
+All three are one protocol (_Instrument): ``evaluate(*truth)`` is reset() + update(*truth) (+ score() for the probe), the
+model's last pass scored alone; ``prefix``, ``group``, ``reported`` and ``nan_in_events`` say how a driver names and writes
+the values, so training.py carries a list of instruments without knowing which they are."""
 import ctypes as C
 
 import numpy as np
@@ -45,54 +49,106 @@ from . import _hip as H
 NAMES = ("mean_iou", "recall", "precision", "cover", "center_dist", "count_accuracy")
 
 
-class Localization:
-    """mean_iou = IOU / PRESENT (an unmatched digit counts 0), recall = HITS / PRESENT, precision = HITS / INFERRED,
-    cover = COVER / PRESENT, center_dist = DIST / MATCHED (transformer units), count_accuracy = COUNT_CORRECT / IMAGES; a
-    zero denominator gives NaN.  per_digit=True also keeps ``match`` [B, G] int32 (the object matched to every digit, or
-    -1) and ``iou`` [B, G] float64 of the last update (rows >= k are not written)."""
+class _Instrument:
+    """What the three instruments share, and what a driver reads to carry one without knowing which it is (training.py):
+    ``prefix`` of its keys in a row of scalars.jsonl, ``group`` of its TensorBoard tags, ``reported``: the names() that are
+    written, ``nan_in_events``: whether a NaN value is written to the event file or left out.  evaluate(*truth) scores the
+    model's last pass from zero: the arguments are update()'s."""
+    NAMES = reported = ()
+    prefix = group = None
+    nan_in_events = True
 
-    def __init__(self, model, max_gt_digits, iou_threshold=0.5, per_digit=False):
-        T, B, G = int(model.max_steps), int(model.batch_size), int(max_gt_digits)
-        if G < 1:
-            raise ValueError("Localization: max_gt_digits must be positive")
-        if T > H.LOC_MAX_STEPS or G > H.LOC_MAX_DIGITS:
-            raise NotImplementedError("Localization: %d steps, %d digits in one image: the kernel holds %d and %d"
-                                      % (T, G, H.LOC_MAX_STEPS, H.LOC_MAX_DIGITS))
-        tau = float(iou_threshold)
-        if not 0.0 < tau <= 1.0:
-            raise ValueError("Localization: iou_threshold must lie in (0, 1]")
-        nbytes = H.lib().air_localization_workspace_bytes(T, B, B, G)
+    def __init__(self, model, max_gt_digits):
+        self.op = type(self).__name__
+        self.model, self.T, self.B, self.G = model, int(model.max_steps), int(model.batch_size), int(max_gt_digits)
+        if self.G < 1:
+            raise ValueError("%s: max_gt_digits must be positive" % self.op)
+
+    def _refuse_beyond(self, a, b, most_a, most_b, what):
+        if a > most_a or b > most_b:
+            raise NotImplementedError("%s: %s: the kernel holds %d and %d" % (self.op, what, most_a, most_b))
+
+    def _on_device(self, capture_too=False):
+        """the device of the model's input buffer, once it is known to be one"""
+        H.require_device(self.model.input_images, "the model's input buffer", self.op, capture_too=capture_too)
+        dev = self.device = self.model.input_images.device
+        self._nan = torch.full((len(self.NAMES),), float("nan"), dtype=torch.float64, device=dev)
+        return dev
+
+    def _accumulators(self, query, counts, sums):
+        """the workspace `query` sizes for a whole batch, then ``counts`` int64 and ``sums`` float64 on the model's device"""
+        nbytes = getattr(H.lib(), query)(self.T, self.B, self.B, self.G)
         if nbytes < 0:
-            H.check(int(nbytes), "air_localization_workspace_bytes")
-        H.require_device(model.input_images, "the model's input buffer", "Localization")
-        dev = self.device = model.input_images.device
-        self.model, self.T, self.B, self.G, self.iou_threshold = model, T, B, G, tau
-        self.counts = torch.zeros(H.LOC_COUNTS + (G + 1) * (T + 1), dtype=torch.int64, device=dev)
-        self.sums = torch.zeros(H.LOC_SUMS, dtype=torch.float64, device=dev)
+            H.check(int(nbytes), query)
+        dev = self._on_device()
+        self.counts = torch.zeros(counts, dtype=torch.int64, device=dev)
+        self.sums = torch.zeros(sums, dtype=torch.float64, device=dev)
         self.workspace = torch.empty(int(nbytes) // 8, dtype=torch.float64, device=dev)
-        self.match = torch.full((B, G), -1, dtype=torch.int32, device=dev) if per_digit else None
-        self.iou = torch.zeros(B, G, dtype=torch.float64, device=dev) if per_digit else None
-        self._nan = torch.full((len(NAMES),), float("nan"), dtype=torch.float64, device=dev)
+        return dev
 
-    @staticmethod
-    def names():
-        return list(NAMES)
+    @classmethod
+    def names(cls):
+        return list(cls.NAMES)
 
     def reset(self):
         """zeroes the accumulators on the current stream"""
         self.counts.zero_()
         self.sums.zero_()
 
+    def evaluate(self, *truth):
+        """reset() and update(*truth): the model's last pass alone, on the current stream"""
+        self.reset()
+        self.update(*truth)
+
+    def _images(self, k, first):
+        """update()'s k: by default all rows of the first ground-truth array, and at most the model's batch"""
+        if k is None:
+            k = int(first.shape[0]) if hasattr(first, "shape") else len(first)
+        k = int(k)
+        if not 1 <= k <= self.B:
+            raise ValueError("%s.update: k = %d images, the model's batch holds %d" % (self.op, k, self.B))
+        return k
+
     def _truth(self, t, what, k, width):
+        """`t` as a contiguous int32 device tensor of `width` values for each of at least k images (numpy is copied)"""
         if not torch.is_tensor(t):
             t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.int32)).to(self.device)
-        H.require_device(t, what, "Localization.update")
+        H.require_device(t, what, self.op + ".update")
         if t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device:
-            raise ValueError("Localization.update: %s must be a contiguous int32 tensor on %s" % (what, self.device))
+            raise ValueError("%s.update: %s must be a contiguous int32 tensor on %s" % (self.op, what, self.device))
         if t.dim() < 1 or int(t.shape[0]) < k or t.numel() != int(t.shape[0]) * width:
-            raise ValueError("Localization.update: %s must hold %d values for each of at least %d images, got %r"
-                             % (what, width, k, tuple(t.shape)))
+            raise ValueError("%s.update: %s must hold %d values for each of at least %d images, got %r"
+                             % (self.op, what, width, k, tuple(t.shape)))
         return t
+
+    def _ratios(self, num, den, out):
+        """values()'s tail: num / den, NaN where den is 0, into `out` when there is one"""
+        v = torch.where(den == 0, self._nan, num / den)
+        if out is None:
+            return v
+        out.copy_(v)
+        return out
+
+
+class Localization(_Instrument):
+    """mean_iou = IOU / PRESENT (an unmatched digit counts 0), recall = HITS / PRESENT, precision = HITS / INFERRED,
+    cover = COVER / PRESENT, center_dist = DIST / MATCHED (transformer units), count_accuracy = COUNT_CORRECT / IMAGES; a
+    zero denominator gives NaN.  per_digit=True also keeps ``match`` [B, G] int32 (the object matched to every digit, or
+    -1) and ``iou`` [B, G] float64 of the last update (rows >= k are not written)."""
+    NAMES = NAMES
+    prefix, group = "loc_", "localization/"
+    reported = NAMES[:5]                    # the sixth, count_accuracy, is the `accuracy` the model summarises itself
+
+    def __init__(self, model, max_gt_digits, iou_threshold=0.5, per_digit=False):
+        super().__init__(model, max_gt_digits)
+        T, B, G = self.T, self.B, self.G
+        self._refuse_beyond(T, G, H.LOC_MAX_STEPS, H.LOC_MAX_DIGITS, "%d steps, %d digits in one image" % (T, G))
+        tau = self.iou_threshold = float(iou_threshold)
+        if not 0.0 < tau <= 1.0:
+            raise ValueError("Localization: iou_threshold must lie in (0, 1]")
+        dev = self._accumulators("air_localization_workspace_bytes", H.LOC_COUNTS + (G + 1) * (T + 1), H.LOC_SUMS)
+        self.match = torch.full((B, G), -1, dtype=torch.int32, device=dev) if per_digit else None
+        self.iou = torch.zeros(B, G, dtype=torch.float64, device=dev) if per_digit else None
 
     def update(self, gt_count, gt_positions, gt_boxes, k=None):
         """One air_localization call over the model's last pass: its first k images (default: all rows of gt_count) against
@@ -100,11 +156,7 @@ class Localization:
         m = self.model
         m._ensure()
         H.require_device(m.att, "the model's records", "Localization.update")
-        if k is None:
-            k = int(gt_count.shape[0]) if hasattr(gt_count, "shape") else len(gt_count)
-        k = int(k)
-        if not 1 <= k <= self.B:
-            raise ValueError("Localization.update: k = %d images, the model's batch holds %d" % (k, self.B))
+        k = self._images(k, gt_count)
         gt = (self._truth(gt_count, "gt_count", k, 1), self._truth(gt_positions, "gt_positions", k, 2 * self.G),
               self._truth(gt_boxes, "gt_boxes", k, 2 * self.G))
         a = H.Localization(H.ptr(m.att), H.ptr(m.run_digits), *(H.ptr(t) for t in gt), H.ptr(self.match), H.ptr(self.iou),
@@ -118,11 +170,7 @@ class Localization:
                            c[H.LOC_COUNT_CORRECT].double()))
         den = torch.stack((c[H.LOC_PRESENT], c[H.LOC_PRESENT], c[H.LOC_INFERRED], c[H.LOC_PRESENT], c[H.LOC_MATCHED],
                            c[H.LOC_IMAGES])).double()
-        v = torch.where(den == 0, self._nan, num / den)
-        if out is None:
-            return v
-        out.copy_(v)
-        return out
+        return self._ratios(num, den, out)
 
     def confusion(self):
         """int64 [G + 1, T + 1] view of the accumulators: rows the true count, columns the inferred one"""
@@ -141,50 +189,30 @@ class Localization:
 SEG_NAMES = ("fg_ari", "mask_iou", "fg_missed", "bg_claimed")
 
 
-class Segmentation:
+class Segmentation(_Instrument):
     """fg_ari = ARI / SCORED (images with at least two foreground pixels), mask_iou = MASK_IOU / PRESENT (the best IoU of a
     predicted mask with every ground-truth object), fg_missed = FG_MISSED / FG_PIXELS (ink no object claims), bg_claimed =
     BG_CLAIMED / (IMAGES * C * C - FG_PIXELS) (background an object claims); a zero denominator gives NaN.  keep=True also
     keeps ``pred_mask`` [B, C * C] uint8, ``tables`` [B, G + 1, T + 1] int32 (truth x prediction), ``ari`` [B] and
     ``mask_iou`` [B, G] float64 of the last update (rows >= k are not written)."""
 
+    NAMES = reported = SEG_NAMES
+    prefix, group = "seg_", "segmentation/"
+
     def __init__(self, model, max_gt_digits, pred_threshold=0.5, keep=False):
-        T, B, G = int(model.max_steps), int(model.batch_size), int(max_gt_digits)
-        Cc, w = int(model.canvas_size), int(model.windows_size)
-        if G < 1:
-            raise ValueError("Segmentation: max_gt_digits must be positive")
-        if T > H.SEG_MAX_STEPS or G > H.SEG_MAX_DIGITS:
-            raise NotImplementedError("Segmentation: %d steps, %d digits in one image: the kernel holds %d and %d"
-                                      % (T, G, H.SEG_MAX_STEPS, H.SEG_MAX_DIGITS))
-        if Cc > H.SEG_MAX_CANVAS or w > H.SEG_MAX_WINDOW:
-            raise NotImplementedError("Segmentation: a %d x %d canvas, %d x %d windows: the kernel holds %d and %d"
-                                      % (Cc, Cc, w, w, H.SEG_MAX_CANVAS, H.SEG_MAX_WINDOW))
-        thr = float(pred_threshold)
+        super().__init__(model, max_gt_digits)
+        T, B, G = self.T, self.B, self.G
+        Cc, w = self.C, self.w = int(model.canvas_size), int(model.windows_size)
+        self._refuse_beyond(T, G, H.SEG_MAX_STEPS, H.SEG_MAX_DIGITS, "%d steps, %d digits in one image" % (T, G))
+        self._refuse_beyond(Cc, w, H.SEG_MAX_CANVAS, H.SEG_MAX_WINDOW, "a %d x %d canvas, %d x %d windows" % (Cc, Cc, w, w))
+        thr = self.pred_threshold = float(pred_threshold)
         if not 0.0 <= thr < 1.0:
             raise ValueError("Segmentation: pred_threshold must lie in [0, 1)")
-        nbytes = H.lib().air_segmentation_workspace_bytes(T, B, B, G)
-        if nbytes < 0:
-            H.check(int(nbytes), "air_segmentation_workspace_bytes")
-        H.require_device(model.input_images, "the model's input buffer", "Segmentation")
-        dev = self.device = model.input_images.device
-        self.model, self.T, self.B, self.G, self.C, self.w, self.pred_threshold = model, T, B, G, Cc, w, thr
-        self.counts = torch.zeros(H.SEG_COUNTS, dtype=torch.int64, device=dev)
-        self.sums = torch.zeros(H.SEG_SUMS, dtype=torch.float64, device=dev)
-        self.workspace = torch.empty(int(nbytes) // 8, dtype=torch.float64, device=dev)
+        dev = self._accumulators("air_segmentation_workspace_bytes", H.SEG_COUNTS, H.SEG_SUMS)
         self.pred_mask = torch.zeros(B, Cc * Cc, dtype=torch.uint8, device=dev) if keep else None
         self.tables = torch.zeros(B, G + 1, T + 1, dtype=torch.int32, device=dev) if keep else None
         self.ari = torch.full((B,), float("nan"), dtype=torch.float64, device=dev) if keep else None
         self.mask_iou = torch.zeros(B, G, dtype=torch.float64, device=dev) if keep else None
-        self._nan = torch.full((len(SEG_NAMES),), float("nan"), dtype=torch.float64, device=dev)
-
-    @staticmethod
-    def names():
-        return list(SEG_NAMES)
-
-    def reset(self):
-        """zeroes the accumulators on the current stream"""
-        self.counts.zero_()
-        self.sums.zero_()
 
     def update(self, gt_mask, k=None):
         """One air_segmentation call over the model's last pass: its first k images (default: all rows of gt_mask) against
@@ -198,11 +226,7 @@ class Segmentation:
         H.require_device(gt_mask, "gt_mask", "Segmentation.update")
         if gt_mask.dtype != torch.uint8 or not gt_mask.is_contiguous() or gt_mask.device != self.device:
             raise ValueError("Segmentation.update: gt_mask must be a contiguous uint8 tensor on %s" % self.device)
-        if k is None:
-            k = int(gt_mask.shape[0]) if gt_mask.dim() else 0
-        k = int(k)
-        if not 1 <= k <= self.B:
-            raise ValueError("Segmentation.update: k = %d images, the model's batch holds %d" % (k, self.B))
+        k = self._images(k, gt_mask if gt_mask.dim() else ())        # (a scalar has no rows)
         if gt_mask.dim() < 2 or int(gt_mask.shape[0]) < k or gt_mask.numel() != int(gt_mask.shape[0]) * self.C * self.C:
             raise ValueError("Segmentation.update: gt_mask must hold %d labels for each of at least %d images, got %r"
                              % (self.C * self.C, k, tuple(gt_mask.shape)))
@@ -217,11 +241,7 @@ class Segmentation:
         num = torch.stack((s[H.SEG_ARI], s[H.SEG_MASK_IOU], c[H.SEG_FG_MISSED].double(), c[H.SEG_BG_CLAIMED].double()))
         den = torch.stack((c[H.SEG_SCORED], c[H.SEG_PRESENT], c[H.SEG_FG_PIXELS],
                            c[H.SEG_IMAGES] * (self.C * self.C) - c[H.SEG_FG_PIXELS])).double()
-        v = torch.where(den == 0, self._nan, num / den)
-        if out is None:
-            return v
-        out.copy_(v)
-        return out
+        return self._ratios(num, den, out)
 
     def result(self):
         """the values as a dict of floats and the raw totals -- synchronises"""
@@ -320,7 +340,7 @@ class _ProbeBuffers:
                     mean=moments[:self.Z].copy(), variance=moments[self.Z:].copy())
 
 
-class LatentProbe:
+class LatentProbe(_Instrument):
     """Do the what-codes say WHAT the digits are?  The latent codes (posterior means) of the matched digits of an evaluation
     set, scored by air_latent_probe (include/air_hip.h has the semantics): the leave-one-out k-nearest-neighbour accuracy of
     their labels with its confusion matrix, and the active units (dimensions whose mean varies over the set, variance >
@@ -338,12 +358,14 @@ class LatentProbe:
     the cursor; capacity defaults to batch_size * max_gt_digits (one pass), and digits beyond it set the overflow flag that
     result() reports.  per_row=True keeps ``pred`` [capacity], ``neighbours`` and ``neighbour_d2`` [capacity, k] of the last
     score()."""
+    NAMES = reported = PROBE_NAMES
+    prefix, group = "lat_", "latents/"
+    nan_in_events = False                     # (nothing scored yet: the scalar is left out, not written as NaN)
 
     def __init__(self, model, max_gt_digits, classes=10, k=5, capacity=None, au_threshold=0.01, per_row=False, max_distance=0.2):
-        T, B, G = int(model.max_steps), int(model.batch_size), int(max_gt_digits)
-        Z, w = int(model.vae_latent_dimensions), int(model.windows_size)
-        if G < 1:
-            raise ValueError("LatentProbe: max_gt_digits must be positive")
+        super().__init__(model, max_gt_digits)
+        T, B, G = self.T, self.B, self.G
+        Z, w = self.Z, self.w = int(model.vae_latent_dimensions), int(model.windows_size)
         capacity = B * G if capacity is None else int(capacity)
         if capacity < 1:
             raise ValueError("LatentProbe: capacity must be positive")
@@ -354,9 +376,7 @@ class LatentProbe:
         if nints < 0:
             raise NotImplementedError("LatentProbe: %d steps, %d digits in one image: the collector holds %d and %d"
                                       % (T, G, H.EMBED_MAX_STEPS, H.EMBED_MAX_DIGITS))
-        H.require_device(model.input_images, "the model's input buffer", "LatentProbe", capture_too=True)
-        dev = self.device = self.buffers.device = model.input_images.device
-        self.model, self.T, self.B, self.G, self.Z, self.w = model, T, B, G, Z, w
+        dev = self.buffers.device = self._on_device(capture_too=True)
         self.k, self.classes, self.capacity, self.max_distance = self.buffers.k, self.buffers.classes, capacity, float(max_distance)
         self.buffers.allocate()
         self.counts, self.moments = self.buffers.counts, self.buffers.moments
@@ -368,28 +388,17 @@ class LatentProbe:
         self._ids = torch.empty(capacity, dtype=torch.int32, device=dev)
         self._match = torch.empty(B, G, dtype=torch.int32, device=dev)
         self._workspace = torch.empty(int(nints), dtype=torch.int32, device=dev)
-        self._nan = torch.full((len(PROBE_NAMES),), float("nan"), dtype=torch.float64, device=dev)
         self._one = torch.ones(1, dtype=torch.float64, device=dev)
-
-    @staticmethod
-    def names():
-        return list(PROBE_NAMES)
 
     def reset(self):
         """zeroes the row cursor and the counts on the current stream"""
         self.counters.zero_()
         self.counts.zero_()
 
-    def _truth(self, t, what, k, width):
-        if not torch.is_tensor(t):
-            t = torch.from_numpy(np.ascontiguousarray(np.asarray(t), dtype=np.int32)).to(self.device)
-        H.require_device(t, what, "LatentProbe.update")
-        if t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device:
-            raise ValueError("LatentProbe.update: %s must be a contiguous int32 tensor on %s" % (what, self.device))
-        if t.dim() < 1 or int(t.shape[0]) < k or t.numel() != int(t.shape[0]) * width:
-            raise ValueError("LatentProbe.update: %s must hold %d values for each of at least %d images, got %r"
-                             % (what, width, k, tuple(t.shape)))
-        return t
+    def evaluate(self, *truth):
+        """reset(), update(*truth) and score()"""
+        super().evaluate(*truth)
+        self.score()
 
     def update(self, gt_count, gt_positions, gt_boxes, gt_labels, k=None):
         """One air_embed_collect call over the model's last pass: the digits of its first k images (default: all rows of
@@ -398,12 +407,8 @@ class LatentProbe:
         m = self.model
         m._ensure()
         H.require_device(m.att, "the model's records", "LatentProbe.update", capture_too=True)
-        if k is None:
-            k = int(gt_count.shape[0]) if hasattr(gt_count, "shape") else len(gt_count)
-        k = int(k)
-        if not 1 <= k <= self.B:
-            raise ValueError("LatentProbe.update: k = %d images, the model's batch holds %d" % (k, self.B))
-        gt = (self._truth(gt_count, "gt_count", k, 1), self._truth(gt_positions, "gt_positions", k, 2 * self.G),
+        k = self._images(k, gt_count)
+        gt =(self._truth(gt_count, "gt_count", k, 1), self._truth(gt_positions, "gt_positions", k, 2 * self.G),
               self._truth(gt_boxes, "gt_boxes", k, 2 * self.G), self._truth(gt_labels, "gt_labels", k, self.G))
         a = H.EmbedCollect(H.ptr(m.att), H.ptr(m.run_digits), H.ptr(m.ml), H.ptr(m.vrec), *(H.ptr(t) for t in gt), H.ptr(gt[3]),
                            H.ptr(self._match), H.ptr(self.counters), H.ptr(self.latents), H.ptr(self._windows),
@@ -422,11 +427,7 @@ class LatentProbe:
         c, n = self.counts.double(), self.counters.double()
         num = torch.stack((c[H.PROBE_CORRECT], c[H.PROBE_ACTIVE_UNITS], c[H.PROBE_SCORED], n[H.EMBED_MATCHED]))
         den = torch.stack((c[H.PROBE_SCORED], self._one[0], self._one[0], n[H.EMBED_PRESENT]))
-        v = torch.where(den == 0, self._nan, num / den)
-        if out is None:
-            return v
-        out.copy_(v)
-        return out
+        return self._ratios(num, den, out)
 
     def confusion(self):
         """int64 [classes, classes] view of the counts: rows the true class, columns the predicted one"""

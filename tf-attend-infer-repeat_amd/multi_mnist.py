@@ -253,27 +253,27 @@ def generate_dataset(max_digits=2, images_per_digit=20000, test_set_size=1000, s
                 test_boxes=padded_truth([boxes[i] for i in test], digits[:test_set_size], max_digits))
 
 
-def padded_truth(lists, digits, max_digits=None):
-    """per-image flat lists [x0, y0, x1, y1, ...] (positions, or boxes as w, h) -> int32 [n, G, 2], zeros behind digits[i];
-    G = max_digits (at least 1), or the largest count when None: the layout air_embed_collect and air_localization read"""
+def padded(lists, digits, width, max_digits=None):
+    """per-image flat lists of `width` values per digit -> int32 [n, G, width], zeros behind digits[i]; G = max_digits (at
+    least 1), or the largest count when None: the layout air_embed_collect and air_localization read"""
     digits = np.asarray(digits, np.int64).reshape(-1)
     G = max(1, int(digits.max()) if max_digits is None and len(digits) else int(max_digits or 1))
-    out = np.zeros((len(digits), G, 2), np.int32)
+    out = np.zeros((len(digits), G, width), np.int32)
     for i, n in enumerate(digits):
         if n:
-            out[i, :n] = np.asarray(lists[i], np.int32).reshape(-1)[:2 * n].reshape(n, 2)
+            out[i, :n] = np.asarray(lists[i], np.int32).reshape(-1)[:width * n].reshape(n, width)
     return out
+
+
+def padded_truth(lists, digits, max_digits=None):
+    """per-image flat lists [x0, y0, x1, y1, ...] (positions, or boxes as w, h) -> int32 [n, G, 2]"""
+    return padded(lists, digits, 2, max_digits)
 
 
 def padded_labels(lists, digits, max_digits=None):
-    """per-image label lists -> int32 [n, G], zeros behind digits[i]; G as padded_truth has it"""
-    digits = np.asarray(digits, np.int64).reshape(-1)
-    G = max(1, int(digits.max()) if max_digits is None and len(digits) else int(max_digits or 1))
-    out = np.zeros((len(digits), G), np.int32)
-    for i, n in enumerate(digits):
-        if n:
-            out[i, :n] = np.asarray(lists[i], np.int32).reshape(-1)[:n]
-    return out
+    """per-image label lists -> int32 [n, G]"""
+    out = padded(lists, digits, 1, max_digits)
+    return out.reshape(out.shape[:2])
 
 
 # ----------------------------------------------------------------------------- reference file format
@@ -769,17 +769,13 @@ def read_test_data(filename, shift_zero_digits_images=False):
 def shift_zero_digits_images(images, digits):
     """read_test_data(..., shift_zero_digits_images=True) :284-294: one empty image first,
     then all non-empty ones, then the remaining empty ones."""
-    empty = [i for i in range(len(digits)) if digits[i] == 0]
-    non_empty = [i for i in range(len(digits)) if digits[i] > 0]
-    if not empty:
-        return images, digits
-    order = [empty[0]] + non_empty + empty[1:]
+    order = shift_zero_digits_order(digits)
     return images[order], digits[order]
 
 
 def shift_zero_digits_order(digits):
-    """the permutation shift_zero_digits_images applies, as an index array: whatever belongs to the images (ground-truth
-    boxes) follows them by a[order]"""
+    """the permutation shift_zero_digits_images applies, as an index array (the identity where no image is empty): whatever
+    belongs to the images (ground-truth boxes) follows them by a[order]"""
     empty = [i for i in range(len(digits)) if digits[i] == 0]
     non_empty = [i for i in range(len(digits)) if digits[i] > 0]
     if not empty:

@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from multi_mnist import (JITTER_NEUTRAL, DeviceGlyphBank, DeviceSceneSource, ShuffleBatchQueue, generate_dataset, handwriting_bank,
-                         load_glyphs, padded_labels, padded_truth, shift_zero_digits_images, shift_zero_digits_order)
+                         load_glyphs, padded_labels, padded_truth, shift_zero_digits_order)
 from air.air_model import AIRModel
 
 EPOCHS = 300
@@ -58,13 +58,9 @@ TEST_SET_SIZE = 1000
 DEFAULT_RESULTS_FOLDER = "air_results"
 TRAIN_DATA_FILE = "multi_mnist_data/common.npz"
 TEST_DATA_FILE = "multi_mnist_data/test.npz"
-# --localization: what a row of scalars.jsonl gains (as loc_<name>) and TensorBoard shows (as localization/<name>); the
-# sixth number of air.metrics.Localization, count_accuracy, is the row's `accuracy`
-LOCALIZATION_KEYS = ("mean_iou", "recall", "precision", "cover", "center_dist")
-# --segmentation: likewise seg_<name> and segmentation/<name>, the four numbers of air.metrics.Segmentation
-SEGMENTATION_KEYS = ("fg_ari", "mask_iou", "fg_missed", "bg_claimed")
-# --latent-probe: likewise lat_<name> and latents/<name>, the four numbers of air.metrics.LatentProbe
-LATENT_KEYS = ("knn_accuracy", "active_units", "scored", "matched_share")
+# The test set is one record (load_data, device_test_set): `images` and `digits`, and what was asked for by name (`want`) --
+# `positions` (x, y) and `boxes` (w, h) as int32 [n, G, 2], `labels` (the digits' classes) as int32 [n, G], zeros behind an
+# image's digits, and the instance `masks` as uint8 [n, CANVAS_SIZE^2], which only a test set composed on the device has
 
 
 def load_background(bg_path="", bg_max_intensity=1.0):
@@ -81,63 +77,47 @@ def load_background(bg_path="", bg_max_intensity=1.0):
     return read_image(bg_path, bg_max_intensity)
 
 
-def cache_without_truth():
-    """the cached data set load_data would read, when its test file holds no ground-truth boxes; None otherwise"""
+def cache_without(keys):
+    """the cached data set load_data would read, when its test file lacks one of `keys`; None otherwise"""
     if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
         with np.load(TEST_DATA_FILE) as te:
-            if "positions" not in te.files or "boxes" not in te.files:
+            if any(k not in te.files for k in keys):
                 return TEST_DATA_FILE
     return None
 
 
-def cache_without_labels():
-    """the cached data set load_data would read, when its test file holds no digit labels; None otherwise"""
-    if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
-        with np.load(TEST_DATA_FILE) as te:
-            if "labels" not in te.files:
-                return TEST_DATA_FILE
-    return None
-
-
-def load_data(bg_path="", bg_max_intensity=1.0, truth=False, labels=False):
-    """-> train images, train digits, test images, test digits; truth: and the test set's ground-truth boxes, positions
-    (x, y) and boxes (w, h) as int32 [n, G, 2] (zeros behind an image's digits); labels: and, last, the classes of the test
-    set's digits, int32 [n, G]"""
+def load_data(bg_path="", bg_max_intensity=1.0, want=()):
+    """-> train images, train digits, the test-set record; want: which of positions, boxes and labels it also holds"""
     if os.path.exists(TRAIN_DATA_FILE) and os.path.exists(TEST_DATA_FILE):
         tr, te = np.load(TRAIN_DATA_FILE), np.load(TEST_DATA_FILE)
-        out = tr["images"], tr["digits"], te["images"], te["digits"]
-        n = len(te["digits"])
-        if truth:
-            out += (te["positions"].astype(np.int32).reshape(n, -1, 2), te["boxes"].astype(np.int32).reshape(n, -1, 2))
-        if labels:
-            out += (te["labels"].astype(np.int32).reshape(n, -1),)
-        return out
+        test = dict(images=te["images"], digits=te["digits"])
+        n = len(test["digits"])
+        test.update({k: te[k].astype(np.int32).reshape((n, -1) if k == "labels" else (n, -1, 2)) for k in want})
+        return tr["images"], tr["digits"], test
     rec_tr, rec_te = TRAIN_DATA_FILE.replace(".npz", ".tfrecords"), TEST_DATA_FILE.replace(".npz", ".tfrecords")
     if os.path.exists(rec_tr) and os.path.exists(rec_te):
         # the reference's own files (training.py:23-24: multi_mnist_data/common.tfrecords, test.tfrecords)
         from multi_mnist import read_test_data
         print("Reading the reference's TFRecord files...")
         tri, trd, *_ = read_test_data(rec_tr)
-        tei, ted, _, tep, teb, tel = read_test_data(rec_te)
-        out = tri, trd.astype(np.int32), tei, ted.astype(np.int32)
-        if truth:
-            out += (padded_truth(tep, ted), padded_truth(teb, ted))
-        return out + (padded_labels(tel, ted),) if labels else out
+        tei, ted, _, *lists = read_test_data(rec_te)
+        test = dict(images=tei, digits=ted.astype(np.int32))
+        for k, lst in zip(("positions", "boxes", "labels"), lists):
+            if k in want:
+                test[k] = padded_labels(lst, ted) if k == "labels" else padded_truth(lst, ted)
+        return tri, trd.astype(np.int32), test
     print("Generating multi-digit dataset in memory (multi_mnist.py defaults)...")
     ds = generate_dataset(bg=load_background(bg_path, bg_max_intensity))
-    out = ds["train_images"], ds["train_digits"], ds["test_images"], ds["test_digits"]
-    if truth:
-        out += (ds["test_positions"], ds["test_boxes"])
-    return out + (ds["test_labels"],) if labels else out
+    return ds["train_images"], ds["train_digits"], {k: ds["test_" + k] for k in ("images", "digits", *want)}
 
 
-def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=False, masks=False, labels=False):
+def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, want=()):
     """--glyph-style mnist-like: TEST_SET_SIZE scenes composed once on the device from one handwriting bank with a seed of its
-    own -> (images, digits) as numpy arrays; the bank and the source are dropped.  truth: and source.meta()'s positions and
-    boxes, int32 [n, max_digits, 2].  masks: and, last, the scenes' instance labels, uint8 [n, CANVAS_SIZE^2]
-    (air.metrics.Segmentation.scene_masks: made here, while the bank's glyph table is still the one the scenes came from).
-    labels: and, behind the boxes, the classes of the scenes' digits, int32 [n, max_digits] (the base glyph of every variant
-    the scenes drew, read here for the same reason; 0 behind an image's digits)"""
+    own -> the test-set record as numpy arrays; the bank and the source are dropped.  want: which of these it also holds --
+    source.meta()'s positions and boxes, int32 [n, max_digits, 2]; masks, the scenes' instance labels, uint8 [n,
+    CANVAS_SIZE^2] (air.metrics.Segmentation.scene_masks: made here, while the bank's glyph table is still the one the scenes
+    came from); labels, the classes of the scenes' digits, int32 [n, max_digits] (the base glyph of every variant the scenes
+    drew, read here for the same reason; 0 behind an image's digits)"""
     images = torch.zeros(TEST_SET_SIZE, CANVAS_SIZE ** 2, device=dev)
     digits = torch.zeros(TEST_SET_SIZE, dtype=torch.int32, device=dev)
     bank, base_labels = handwriting_bank(variants, 0x54455354 + seed, dev)
@@ -145,19 +125,37 @@ def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, truth=Fals
                                gap=gap, bg=bg, seed=0x5445535453 + seed)
     bank.refresh()
     source.next_batch()
-    out = images.cpu().numpy(), digits.cpu().numpy()
-    if truth:
-        meta = source.meta()
-        out += tuple(meta[k].cpu().numpy().reshape(TEST_SET_SIZE, -1, 2) for k in ("positions", "boxes"))
-    if labels:
+    test = dict(images=images.cpu().numpy(), digits=digits.cpu().numpy())
+    for k in ("positions", "boxes"):
+        if k in want:
+            test[k] = source.meta()[k].cpu().numpy().reshape(TEST_SET_SIZE, -1, 2)
+    if "labels" in want:
         indices = source.meta()["indices"].cpu().numpy().reshape(TEST_SET_SIZE, -1)
         of_variant = bank.labels(base_labels).astype(np.int32)
-        used = np.arange(indices.shape[1])[None, :] < out[1][:, None]
-        out += (np.where(used, of_variant[np.clip(indices, 0, len(of_variant) - 1)], 0).astype(np.int32),)
-    if masks:
+        used = np.arange(indices.shape[1])[None, :] < test["digits"][:, None]
+        test["labels"] = np.where(used, of_variant[np.clip(indices, 0, len(of_variant) - 1)], 0).astype(np.int32)
+    if "masks" in want:
         from air.metrics import Segmentation
-        out += (Segmentation.scene_masks(source, digits).cpu().numpy(),)
-    return out
+        test["masks"] = Segmentation.scene_masks(source, digits).cpu().numpy()
+    return test
+
+
+def shifted(test):
+    """a test-set record in the order of shift_zero_digits_images: every entry follows the one permutation"""
+    order = shift_zero_digits_order(test["digits"])
+    return {k: np.ascontiguousarray(a[order]) for k, a in test.items()}
+
+
+def reported_values(instrument, values):
+    """{name: value} of the names an instrument reports, from its `values` (names() order)"""
+    got = dict(zip(instrument.names(), values))
+    return {k: got[k] for k in instrument.reported}
+
+
+def row_fields(instrument, values):
+    """what a row of scalars.jsonl gains from an instrument's `values`: the reported ones under its prefix, rounded, a NaN
+    as null"""
+    return {instrument.prefix + k: (round(v, 5) if v == v else None) for k, v in reported_values(instrument, values).items()}
 
 
 class SummaryWriter:
@@ -166,54 +164,28 @@ class SummaryWriter:
     launch into a device vector; the vector is copied into a pinned host ring without blocking and a row is written
     when the NEXT evaluation has been enqueued, so the host never waits for the step it has just launched."""
 
-    def __init__(self, model, path, t0, slots=2, on_row=None, localization=None, on_localization=None, segmentation=None,
-                 on_segmentation=None, latent=None, on_latent=None):
-        """localization: (air.metrics.Localization of `model`, (gt_count, gt_positions, gt_boxes) on the device) -- every
-        evaluation is then also scored against the ground truth (reset + update + values: a few launches behind the
-        summaries one, fetched through the same ring) and the row gains the loc_* keys; on_localization(step, values).
-        segmentation: (air.metrics.Segmentation of `model`, the label planes on the device), in the same way: seg_* keys,
-        on_segmentation(step, values).  latent: (air.metrics.LatentProbe of `model`, (gt_count, gt_positions, gt_boxes,
-        gt_labels) on the device): reset + update + score + values, lat_* keys, on_latent(step, values)"""
-        self.model, self.t0, self.on_row = model, t0, on_row
+    def __init__(self, model, path, t0, slots=2, on_row=None, instruments=(), on_values=None):
+        """instruments: [(an air.metrics instrument of `model`, its ground truth on the device: evaluate()'s arguments)] --
+        every evaluation is then also scored by each (a few launches behind the summaries one, the values fetched through
+        a pinned ring of the instrument's own) and the row gains row_fields() of each, in list order;
+        on_values(step, instrument, the values of its reported names) is called for each after on_row"""
+        self.model, self.t0, self.on_row, self.on_values = model, t0, on_row, on_values
         self.names = model.summary_names()
         self.dev = torch.empty(len(self.names), dtype=torch.float32, device=model.input_images.device)
         self.host = torch.empty(slots, len(self.names), dtype=torch.float32).pin_memory()
         self.events = [torch.cuda.Event() for _ in range(slots)]
         self.pending, self.k, self.file = [], 0, open(path, "w")
-        self.loc, self.on_localization = localization, on_localization
-        if localization is not None:
-            self.loc_names = localization[0].names()
-            self.loc_host = torch.empty(slots, len(self.loc_names), dtype=torch.float64).pin_memory()
-        self.seg, self.on_segmentation = segmentation, on_segmentation
-        if segmentation is not None:
-            self.seg_names = segmentation[0].names()
-            self.seg_host = torch.empty(slots, len(self.seg_names), dtype=torch.float64).pin_memory()
-        self.lat, self.on_latent = latent, on_latent
-        if latent is not None:
-            self.lat_names = latent[0].names()
-            self.lat_host = torch.empty(slots, len(self.lat_names), dtype=torch.float64).pin_memory()
+        self.instruments = [(instrument, truth, torch.empty(slots, len(instrument.names()), dtype=torch.float64).pin_memory())
+                            for instrument, truth in instruments]
 
     def push(self, step):
         slot = self.k % len(self.events)
         self.k += 1
         self.model.numeric_summaries(self.dev)
         self.host[slot].copy_(self.dev, non_blocking=True)
-        if self.loc is not None:
-            loc, truth = self.loc
-            loc.reset()
-            loc.update(*truth)
-            self.loc_host[slot].copy_(loc.values(), non_blocking=True)
-        if self.seg is not None:
-            seg, planes = self.seg
-            seg.reset()
-            seg.update(planes)
-            self.seg_host[slot].copy_(seg.values(), non_blocking=True)
-        if self.lat is not None:
-            lat, truth = self.lat
-            lat.reset()
-            lat.update(*truth)
-            lat.score()
-            self.lat_host[slot].copy_(lat.values(), non_blocking=True)
+        for instrument, truth, ring in self.instruments:
+            instrument.evaluate(*truth)
+            ring[slot].copy_(instrument.values(), non_blocking=True)
         self.events[slot].record()
         self.pending.append((slot, step))
         while len(self.pending) > 1:
@@ -224,25 +196,16 @@ class SummaryWriter:
         self.events[slot].synchronize()
         row = {"step": step, "wall_s": round(time.perf_counter() - self.t0, 3)}
         row.update({k: (round(v, 5) if v == v else None) for k, v in zip(self.names, self.host[slot].tolist())})
-        if self.loc is not None:
-            located = dict(zip(self.loc_names, self.loc_host[slot].tolist()))
-            row.update({"loc_" + k: (round(located[k], 5) if located[k] == located[k] else None) for k in LOCALIZATION_KEYS})
-        if self.seg is not None:
-            segmented = dict(zip(self.seg_names, self.seg_host[slot].tolist()))
-            row.update({"seg_" + k: (round(segmented[k], 5) if segmented[k] == segmented[k] else None) for k in SEGMENTATION_KEYS})
-        if self.lat is not None:
-            probed = dict(zip(self.lat_names, self.lat_host[slot].tolist()))
-            row.update({"lat_" + k: (round(probed[k], 5) if probed[k] == probed[k] else None) for k in LATENT_KEYS})
+        scored = [(instrument, ring[slot].tolist()) for instrument, _, ring in self.instruments]
+        for instrument, values in scored:
+            row.update(row_fields(instrument, values))
         self.file.write(json.dumps(row) + "\n")
         self.file.flush()
         if self.on_row is not None:
             self.on_row(step, self.host[slot].tolist())
-        if self.loc is not None and self.on_localization is not None:
-            self.on_localization(step, [located[k] for k in LOCALIZATION_KEYS])
-        if self.seg is not None and self.on_segmentation is not None:
-            self.on_segmentation(step, [segmented[k] for k in SEGMENTATION_KEYS])
-        if self.lat is not None and self.on_latent is not None:
-            self.on_latent(step, [probed[k] for k in LATENT_KEYS])
+        if self.on_values is not None:
+            for instrument, values in scored:
+                self.on_values(step, instrument, list(reported_values(instrument, values).values()))
 
     def flush(self):
         while self.pending:
@@ -297,17 +260,11 @@ class TensorBoardWriter:
         """SummaryWriter's row of `step` (AIRModel.summary_names() order: loss, accuracy, then the reference's scalars)"""
         self.events.add_scalars(step, zip(self.tags.numeric, values[2:]))
 
-    def localization(self, step, values):
-        """--localization: the five LOCALIZATION_KEYS of the evaluation at `step`"""
-        self.events.add_scalars(step, [("localization/" + k, v) for k, v in zip(LOCALIZATION_KEYS, values)])
-
-    def segmentation(self, step, values):
-        """--segmentation: the four SEGMENTATION_KEYS of the evaluation at `step`"""
-        self.events.add_scalars(step, [("segmentation/" + k, v) for k, v in zip(SEGMENTATION_KEYS, values)])
-
-    def latents(self, step, values):
-        """--latent-probe: the four LATENT_KEYS of the evaluation at `step` (a NaN, nothing scored yet, is left out)"""
-        self.events.add_scalars(step, [("latents/" + k, v) for k, v in zip(LATENT_KEYS, values) if v == v])
+    def instrument(self, step, instrument, values):
+        """--localization, --segmentation, --latent-probe: the reported values of the evaluation at `step`, under the
+        instrument's group (SummaryWriter's on_values hook); whether a NaN is written is the instrument's to say"""
+        self.events.add_scalars(step, [(instrument.group + k, v) for k, v in zip(instrument.reported, values)
+                                       if v == v or instrument.nan_in_events])
 
     def variables(self, step):
         from air.summaries import decode_histograms
@@ -343,6 +300,29 @@ class TensorBoardWriter:
     def close(self):
         self.flush()
         self.events.close()
+
+
+def instruments(args, model, test):
+    """--localization, --segmentation, --latent-probe -> [(the air.metrics instrument of `model`, its ground truth out of the
+    test-set record on the device, headline)], in that order; headline(result()) -> what the run's last line about the
+    instrument says in front of and behind its reported values, and the title of its confusion matrix (None: it has none)"""
+    from air import metrics
+    out = []
+    if args.localization:
+        loc = metrics.Localization(model, int(test["positions"].shape[1]), args.localization_iou)
+        out.append((loc, (test["digits"], test["positions"], test["boxes"]), lambda res: (
+            "localization at IoU {:g}: ".format(loc.iou_threshold), "",
+            "count confusion (rows: digits present 0..{}, columns: objects inferred 0..{}):".format(loc.G, loc.T))))
+    if args.segmentation:
+        seg = metrics.Segmentation(model, args.online_max_digits, args.segmentation_threshold)
+        out.append((seg, (test["masks"],), lambda res: ("segmentation at {:g}: ".format(seg.pred_threshold), "", None)))
+    if args.latent_probe:
+        lat = metrics.LatentProbe(model, int(test["labels"].shape[1]), k=args.latent_k)
+        out.append((lat, (test["digits"], test["positions"], test["boxes"], test["labels"]), lambda res: (
+            "latent probe, {}-NN over {} matched digits: ".format(lat.k, res["scored"]),
+            "  (the store overflowed)" if res["overflow"] else "",
+            "digit confusion (rows: true class 0..{}, columns: predicted):".format(lat.classes - 1))))
+    return out
 
 
 def main():
@@ -430,11 +410,11 @@ def main():
     args = parser.parse_args()
     if args.latent_probe and not 1 <= args.latent_k <= 16:
         parser.error("--latent-k must lie in [1, 16]")
-    if args.latent_probe and args.glyph_style != "mnist-like" and (cache_without_truth() or cache_without_labels()):
+    if args.latent_probe and args.glyph_style != "mnist-like" and cache_without(("positions", "boxes", "labels")):
         parser.error("--latent-probe needs the ground-truth boxes and digit labels of the test set, and %s holds none (no "
                      "'positions' / 'boxes' / 'labels'): regenerate the cache with multi_mnist.py (or multi_mnist.py --device N), "
                      "which writes them, or remove it to have the data set generated in memory"
-                     % (cache_without_truth() or cache_without_labels()))
+                     % cache_without(("positions", "boxes", "labels")))
     if args.segmentation and not 0.0 <= args.segmentation_threshold < 1.0:
         parser.error("--segmentation-threshold must lie in [0, 1)")
     if args.segmentation and args.glyph_style != "mnist-like":
@@ -443,10 +423,10 @@ def main():
                      "test set does not have")
     if args.localization and not 0.0 < args.localization_iou <= 1.0:
         parser.error("--localization-iou must lie in (0, 1]")
-    if args.localization and args.glyph_style != "mnist-like" and cache_without_truth():
+    if args.localization and args.glyph_style != "mnist-like" and cache_without(("positions", "boxes")):
         parser.error("--localization needs the ground-truth boxes of the test set, and %s holds none (no 'positions' / 'boxes'): "
                      "regenerate the cache with multi_mnist.py (or multi_mnist.py --device N), which writes them, or remove it "
-                     "to have the data set generated in memory" % cache_without_truth())
+                     "to have the data set generated in memory" % cache_without(("positions", "boxes")))
     jitter = dict(min_w=args.min_width_scale, max_w=args.max_width_scale, min_h=args.min_height_scale,
                   max_h=args.max_height_scale, min_ang=args.min_rotation_angle, max_ang=args.max_rotation_angle)
     mnist_like = args.glyph_style == "mnist-like"
@@ -473,30 +453,21 @@ def main():
         os.makedirs(d)
 
     dev = torch.device("cuda", 0)
-    need_truth = args.localization or args.latent_probe
+    want = (("positions", "boxes") if args.localization or args.latent_probe else ()) + \
+        (("labels",) if args.latent_probe else ()) + (("masks",) if args.segmentation else ())
     print("Creating input pipeline...")
     if mnist_like:                                                   # no host generator: the test set is device work too
-        te_im, te_dg, *te_truth = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin,
-                                                  args.digit_gap, load_background(args.bg_path, args.bg_max_intensity),
-                                                  truth=need_truth, masks=args.segmentation, labels=args.latent_probe)
-        if args.segmentation:
-            *te_truth, te_masks = te_truth
+        test = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin, args.digit_gap,
+                               load_background(args.bg_path, args.bg_max_intensity), want)
     else:
-        tr_im, tr_dg, te_im, te_dg, *te_truth = load_data(args.bg_path, args.bg_max_intensity, truth=need_truth,
-                                                          labels=args.latent_probe)
-    if need_truth:                                                   # the ground truth follows the images' permutation
-        order = shift_zero_digits_order(te_dg)
-        te_truth = [torch.tensor(np.ascontiguousarray(a[order]).astype(np.int32), device=dev) for a in te_truth]
-        if args.latent_probe:                                        # (positions, boxes | labels)
-            *te_truth, te_labels = te_truth
-    if args.segmentation:                                            # ... and so do the instance masks
-        te_masks = torch.tensor(np.ascontiguousarray(te_masks[shift_zero_digits_order(te_dg)]), device=dev)
-    te_im, te_dg = shift_zero_digits_images(te_im, te_dg)
+        tr_im, tr_dg, test = load_data(args.bg_path, args.bg_max_intensity, want)
+    test = shifted(test)                                             # the ground truth follows the images' permutation
+    test["digits"] = test["digits"].astype(np.int32)
+    test = {k: torch.tensor(a, device=dev) for k, a in test.items()}
     if not args.online_data:
         train_images = torch.tensor(tr_im, device=dev)
         train_digits = torch.tensor(tr_dg.astype(np.int32), device=dev)
-    test_data = torch.tensor(np.ascontiguousarray(te_im), device=dev)
-    test_targets = torch.tensor(np.ascontiguousarray(te_dg).astype(np.int32), device=dev)
+    test_data, test_targets = test["images"], test["digits"]
     train_data = torch.zeros(BATCH_SIZE, CANVAS_SIZE ** 2, device=dev)
     train_targets = torch.zeros(BATCH_SIZE, dtype=torch.int32, device=dev)
 
@@ -575,22 +546,10 @@ def main():
     order = train_model.backward
     t0 = time.perf_counter()
     board = TensorBoardWriter(summaries_folder, train_model, test_model) if args.tensorboard else None
-    located = None
-    if args.localization:
-        from air.metrics import Localization
-        located = (Localization(test_model, int(te_truth[0].shape[1]), args.localization_iou), (test_targets, *te_truth))
-    segmented = None
-    if args.segmentation:
-        from air.metrics import Segmentation
-        segmented = (Segmentation(test_model, args.online_max_digits, args.segmentation_threshold), te_masks)
-    probed = None
-    if args.latent_probe:
-        from air.metrics import LatentProbe
-        probed = (LatentProbe(test_model, int(te_labels.shape[1]), k=args.latent_k), (test_targets, *te_truth, te_labels))
+    scored = instruments(args, test_model, test)
     writer = SummaryWriter(test_model, summaries_folder + "scalars.jsonl", t0, on_row=board.numeric if board else None,
-                           localization=located, on_localization=board.localization if board else None,
-                           segmentation=segmented, on_segmentation=board.segmentation if board else None,
-                           latent=probed, on_latent=board.latents if board else None)
+                           instruments=[(instrument, truth) for instrument, truth, _ in scored],
+                           on_values=board.instrument if board else None)
     while step < total:
         if step % NUM_SUMMARIES_EACH_ITERATIONS == 0:
             test_model.forward()
@@ -626,34 +585,15 @@ def main():
     print("training has ended")
     print("test accuracy {:.4f}  test loss {:.3f}  ({} iterations, {:.1f} s)".format(
         float(test_model.accuracy), float(test_model.loss), step, time.perf_counter() - t0))
-    if located:                                                      # the evaluation just made, the last of the run
-        loc, truth = located
-        loc.reset()
-        loc.update(*truth)
-        res = loc.result()
-        print("localization at IoU {:g}: ".format(loc.iou_threshold) + "  ".join(
-            "{} {:.4f}".format(k, res[k]) for k in LOCALIZATION_KEYS))
-        print("count confusion (rows: digits present 0..{}, columns: objects inferred 0..{}):".format(loc.G, loc.T))
-        for row in res["confusion"]:
-            print("  " + " ".join("{:6d}".format(int(v)) for v in row))
-    if segmented:
-        seg, planes = segmented
-        seg.reset()
-        seg.update(planes)
-        res = seg.result()
-        print("segmentation at {:g}: ".format(seg.pred_threshold) + "  ".join(
-            "{} {:.4f}".format(k, res[k]) for k in SEGMENTATION_KEYS))
-    if probed:
-        lat, truth = probed
-        lat.reset()
-        lat.update(*truth)
-        lat.score()
-        res = lat.result()
-        print("latent probe, {}-NN over {} matched digits: ".format(lat.k, res["scored"]) + "  ".join(
-            "{} {:.4f}".format(k, res[k]) for k in LATENT_KEYS) + ("  (the store overflowed)" if res["overflow"] else ""))
-        print("digit confusion (rows: true class 0..{}, columns: predicted):".format(lat.classes - 1))
-        for row in res["confusion"]:
-            print("  " + " ".join("{:6d}".format(int(v)) for v in row))
+    for instrument, truth, headline in scored:                       # the evaluation just made, the last of the run
+        instrument.evaluate(*truth)
+        res = instrument.result()
+        lead, tail, matrix = headline(res)
+        print(lead + "  ".join("{} {:.4f}".format(k, res[k]) for k in instrument.reported) + tail)
+        if matrix:
+            print(matrix)
+            for row in res["confusion"]:
+                print("  " + " ".join("{:6d}".format(int(v)) for v in row))
     if args.online_data:
         print("online data: {} batches composed on the device, {} canvases given up".format(
             int(batches.counter), int(batches.gave_up())) + ("" if bank is None else
