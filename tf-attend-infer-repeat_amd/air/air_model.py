@@ -95,7 +95,7 @@ KERNEL_NAMES = {
     "air_philox_fill": "philox_fill_kernel",
     "air_scene_records": "scene_records_kernel",
     "air_render": "render_kernel",
-    "air_glyph_distort": "glyph_distort_kernel",                        # (multi_mnist.DeviceHandwritingBank launches it)
+    "air_glyph_distort": "glyph_distort_kernel",                        # (air.sources.DeviceHandwritingBank launches it)
     "air_localization": "loc_match_kernel",                             # (air.metrics.Localization; then loc_fold_kernel)
     "air_segmentation": "seg_image_kernel",                             # (air.metrics.Segmentation; then seg_fold_kernel)
     "air_scene_masks": "scene_masks_kernel",                            # (Segmentation.scene_masks)
@@ -1233,7 +1233,7 @@ class AIRModel:
         one step per replay.  Noise and schedules are keyed by the device-side global_step, so the steps of a replay
         differ as they would in separate replays; `between_steps(i)` (optional, graph-capturable device work such as
         the next batch's gather) is captured before step i, `after_steps()` after the last one (e.g. the join of a branch
-        that between_steps forked: multi_mnist.ShuffleBatchQueue.graph_hooks).  training() then advances `steps` steps."""
+        that between_steps forked: air.sources.ShuffleBatchQueue.graph_hooks).  training() then advances `steps` steps."""
         if not self.train:
             return self._capture_forward_graph()
         self._capture_args = dict(steps=steps, between_steps=between_steps, after_steps=after_steps)

@@ -12,7 +12,7 @@ blocking; ``result()`` is the one method that synchronises.
     loc.values()                                        # float64 [6] on the device, names() order
     loc.result()                                        # dict of floats + "confusion" [G + 1, T + 1] (truth x inferred)
 
-The ground truth has the layouts of air_embed_collect and of multi_mnist.DeviceSceneSource: positions (x, y) and boxes
+The ground truth has the layouts of air_embed_collect and of air.sources.DeviceSceneSource: positions (x, y) and boxes
 (w, h) as [k, G, 2] or [k, 2 G], so ``source.meta()`` can be passed straight in.  There is no CPU fallback.
 
 ``Segmentation(model, max_gt_digits)`` is the per-pixel instrument beside it: which object explains which ink?  One call of
@@ -256,7 +256,7 @@ class Segmentation(_Instrument):
     def scene_masks(source_or_arrays, digits, ink_threshold=0.0):
         """uint8 [B, C * C] instance labels of composed scenes, one air_scene_masks launch on the current stream: pixel p of
         scene b is g + 1 for the first digit g < digits[b] whose glyph has ink (a value > ink_threshold) there, 0 elsewhere.
-        source_or_arrays: a multi_mnist.DeviceSceneSource (its glyphs, crops and meta() of the last batch), or a dict of
+        source_or_arrays: an air.sources.DeviceSceneSource (its glyphs, crops and meta() of the last batch), or a dict of
         device tensors glyphs [Gn, gd * gd] float32, crops [Gn, 4], indices [B, max_digits], positions [B, 2 max_digits]
         int32 and the int canvas_dim.  digits: int32 [B] on the device."""
         src = source_or_arrays

@@ -10,20 +10,20 @@ AIRModel._summarize_by_digit_count (air_model.py:160-182, 614-617).  With --tens
 groups are also written to summary/events.out.tfevents.* (TensorBoardWriter; tf_events.py) at its cadences (:165-218).
 
 The whole dataset lives in HBM.  A batch comes out of tf.train.shuffle_batch's queue, kept on the
-device (multi_mnist.ShuffleBatchQueue; multi_mnist.py:240-249: capacity 10 000 + 10 * batch, min_after_dequeue
+device (air.sources.ShuffleBatchQueue; multi_mnist.py:240-249: capacity 10 000 + 10 * batch, min_after_dequeue
 10 000, over the epoch-repeating record stream of training.py:76-81) and is gathered into the train model's input
 buffer; with --print-every 0 fifty train steps and their batches are one hipGraph replay (the queue's picks for the
 fifty batches in its first launch, a row gather in front of every step), and the evaluation every 50 iterations is one replay of the
 test model's forward + one summaries launch whose numbers are fetched without blocking (SummaryWriter).
 
---online-data replaces the queue and the train set by multi_mnist.DeviceSceneSource: the generator's default path as one
+--online-data replaces the queue and the train set by air.sources.DeviceSceneSource: the generator's default path as one
 launch per step that composes a fresh batch into the train model's input buffers (inside the replay when there is one), so
 no canvas is trained on twice; the evaluation set stays the fixed one.  The run ends with a line that says how many
 batches were composed and how many canvases the bounded rejection sampler gave up on.  With the generator's scale /
 rotation flags (--min-width-scale ... --max-rotation-angle) the digits come from a bank of --jitter-bank jittered glyphs
-(multi_mnist.DeviceGlyphBank), remade on the device every --graph-steps steps -- by the replay itself when there is one, so
+(air.sources.DeviceGlyphBank), remade on the device every --graph-steps steps -- by the replay itself when there is one, so
 the batches are the same with and without --no-graph; the last line then also counts the banks and the unusable variants.
---glyph-style mnist-like takes the digits from a multi_mnist.DeviceHandwritingBank instead (the 8x8 handwritten digits
+--glyph-style mnist-like takes the digits from an air.sources.DeviceHandwritingBank instead (the 8x8 handwritten digits
 distorted on the device into MNIST's 20-in-28 geometry), remade at the same steps; the evaluation set is then 1 000 scenes
 composed once on the device from a bank with a seed of its own, and the host generator does not run at all.
 """
@@ -123,8 +123,7 @@ def device_test_set(dev, variants, seed, max_digits, margin, gap, bg, want=()):
     bank, base_labels = handwriting_bank(variants, 0x54455354 + seed, dev)
     source = DeviceSceneSource(bank, TEST_SET_SIZE, images, digits, canvas_dim=CANVAS_SIZE, max_digits=max_digits, margin=margin,
                                gap=gap, bg=bg, seed=0x5445535453 + seed)
-    bank.refresh()
-    source.next_batch()
+    source.fresh_batch()
     test = dict(images=images.cpu().numpy(), digits=digits.cpu().numpy())
     for k in ("positions", "boxes"):
         if k in want:
@@ -366,7 +365,7 @@ def main():
                              "training.py passes cnn=False)")
     parser.add_argument("--cnn-filters", type=int, default=8)
     parser.add_argument("--online-data", action="store_true",
-                        help="compose every train batch on the device (multi_mnist.DeviceSceneSource: the generator's default "
+                        help="compose every train batch on the device (air.sources.DeviceSceneSource: the generator's default "
                              "path, a fresh batch per step, no canvas seen twice) instead of drawing it from the fixed train set; "
                              "--bg-path applies; the evaluation set stays the fixed one")
     parser.add_argument("--online-max-digits", type=int, default=2, help="--online-data: scenes hold 0 .. this many digits")
@@ -381,10 +380,10 @@ def main():
     parser.add_argument("--max-rotation-angle", type=float, default=0.0)
     parser.add_argument("--jitter-bank", type=int, default=4096, metavar="V",
                         help="--online-data with jitter: digits are drawn from a bank of V jittered glyphs made on the device "
-                             "(multi_mnist.DeviceGlyphBank), a fresh bank every --graph-steps steps")
+                             "(air.sources.DeviceGlyphBank), a fresh bank every --graph-steps steps")
     parser.add_argument("--glyph-style", default="standin", choices=["standin", "mnist-like"],
                         help="--online-data: mnist-like draws the digits from a bank of --jitter-bank handwritten digits "
-                             "distorted on the device into MNIST's geometry (multi_mnist.DeviceHandwritingBank: a 20-pixel "
+                             "distorted on the device into MNIST's geometry (air.sources.DeviceHandwritingBank: a 20-pixel "
                              "box centred in a 28-pixel frame), a fresh bank every --graph-steps steps; the evaluation set is "
                              "composed on the device too")
     parser.add_argument("--localization", action="store_true",
