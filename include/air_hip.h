@@ -1417,6 +1417,106 @@ int64_t air_latent_probe_workspace_bytes(int M, int Z, int k);
  * AIR_PROBE_MAX_ROWS -- no GPU is touched */
 int air_latent_probe_splits(int M);
 
+/* ---- importance-weighted evaluation bound (additive to ABI 6) ----------------------------------------------------------------
+ * The K-sample importance-weighted bound of a variational scene model, log (1/K) sum_k w_k, its effective sample size and
+ * the posterior over the object count, from K passes of a test model on fresh noise (AIRModel.forward_sampled).  Two entry
+ * points: air_importance_logw turns the buffers one pass left on the device into one row of log-weights, and
+ * air_importance_fold reduces the K rows to per-image numbers and adds them to accumulators.  air/metrics.py
+ * (ImportanceBound) is the caller; tests/importance_cases.py restates every operation below.
+ *
+ * All arithmetic is fp64 in exactly the order written here (the translation unit has -ffp-contract=off); every fp32 input
+ * is widened first, one by one.  i < k is an image, t < T a step, j < Z a latent dimension.
+ *
+ * air_importance_logw -- row `sample` of the tables, ONE launch.  The weight of a sample is p(x, z) / q(z | x) at the
+ * sample: log w = -(rec_loss + the log-ratios log q - log p of every latent the pass drew).
+ *   lr(z, eps, lv, pm, pv, plv) = 0.5 * ((((z - pm) * (z - pm)) / pv + plv) - eps * eps - lv)
+ * is that log-ratio of a Gaussian posterior N(mean, exp(lv)) against the prior N(pm, pv) (plv = log pv, the dyn slot the
+ * loss reads), at the sample the noise eps gave: log q(z) = -0.5 (eps^2 + lv) and log p(z) = -0.5 ((z - pm)^2 / pv + plv) up
+ * to the same constant.  It has no transcendental.  The pixel noise eps_x is drawn from ITS prior under q as well (the
+ * likelihood noise of vae.py:37 is no latent of the posterior): its ratio is 1 and it has no term.
+ *   scale_t = lr(att[t][i][AIR_ATT_S], eps_scale[t][i], out7[t][i][1], dyn[AIR_DYN_SCALE_PM], [SCALE_PV], [SCALE_PLV])
+ *   shift_t = lr(att[t][i][AIR_ATT_X], eps_shift[t][i][0], out7[t][i][4], dyn[AIR_DYN_SHIFT_PM], [SHIFT_PV], [SHIFT_PLV])
+ *           + lr(att[t][i][AIR_ATT_Y], eps_shift[t][i][1], out7[t][i][5], the same three)                     (x first)
+ *   what_t  = (((+0.0 + l_0) + l_1) + ...) over j = 0 .. Z - 1 IN ORDER, l_j = lr(z[t][i][j], eps_z[t][i][j],
+ *             ml[t][i][Z + j], dyn[AIR_DYN_VAE_PM], [VAE_PV], [VAE_PLV]); z is addressed with ldz (0 = Z) as in
+ *             air_bottleneck_fwd_t.  The sum is SEQUENTIAL: one lane owns an (image, step) and runs the Z loop alone.
+ *   a_t = att[t][i][AIR_ATT_MASK_PREV] != 0 ? (double)att[t][i][AIR_ATT_KL_Z] : 0.0     (the Monte-Carlo z_pres log-ratio)
+ *   b_t = att[t][i][AIR_ATT_MASK] != 0 ? (scale_t + shift_t) + what_t : 0.0
+ *   loss_i = ((((double)rec_loss[i] + (a_0 + b_0)) + (a_1 + b_1)) + ...) over t = 0 .. T - 1 in order;   logw_i = -loss_i
+ * The gates are SELECTS: whatever the records of a step hold that the gate closes (a NaN included) never reaches a result.
+ * logw[sample][i] = logw_i;  digits[sample][i] = run_digits[i];  when terms is given, terms[sample][i][AIR_IW_TERM_*] =
+ * (double)rec_loss[i], then the four sums (((+0.0 + v_0) + v_1) + ...) over t in order of a_t (Z_PRES) and of the gated
+ * scale_t, shift_t and what_t (MASK_t != 0 ? v : 0.0).  The tables have K rows of B columns; only row `sample`, columns
+ * < k, is written, and rows >= k of the inputs are never read.
+ * Refusals, on the host before any HIP call, in this order.  AIR_EINVAL: a null descriptor; T, B, k, Z or K < 1; k > B;
+ * ldz not 0 and < Z; sample not in [0, K).  AIR_ELIMIT: T > AIR_MAX_STEPS, K > AIR_IW_MAX_SAMPLES, Z > AIR_IW_MAX_Z.
+ * AIR_EINVAL: a null att, out7, ml, z, eps_scale, eps_shift, eps_z, rec_loss, run_digits, dyn, logw or digits. */
+#define AIR_IW_MAX_SAMPLES 64
+#define AIR_IW_MAX_Z 256
+enum { AIR_IW_TERM_REC = 0, AIR_IW_TERM_Z_PRES = 1, AIR_IW_TERM_SCALE = 2, AIR_IW_TERM_SHIFT = 3, AIR_IW_TERM_WHAT = 4,
+       AIR_IW_TERMS = 5 };
+typedef struct {
+    const float* att;                    /* [T, B, AIR_ATT_STRIDE] of the pass just run                                 */
+    const float* out7;                   /* [T, B, AIR_OUT_STRIDE]: the posterior parameters of scale and shift         */
+    const float* ml;                     /* [T, B, 2 Z]: mean | log-variance of the what-code                           */
+    const float* z;                      /* [T, B, ldz]: the what-code samples                                          */
+    const float* eps_scale;              /* [T, B]                                                                      */
+    const float* eps_shift;              /* [T, B, 2]                                                                   */
+    const float* eps_z;                  /* [T, B, Z]                                                                   */
+    const float* rec_loss;               /* [B]                                                                         */
+    const int32_t* run_digits;           /* [B]                                                                         */
+    const float* dyn;                    /* AIR_DYN_* device array                                                      */
+    double* logw;                        /* in / out [K, B]                                                             */
+    int32_t* digits;                     /* in / out [K, B]                                                             */
+    double* terms;                       /* in / out [K, B, AIR_IW_TERMS], nullable                                     */
+    int32_t T, B, k, Z, ldz, K;
+} air_importance_t;
+int air_importance_logw(const air_importance_t* args, int sample, void* stream);
+
+/* air_importance_fold -- the [K, k] tables folded into per-image numbers and the accumulators.  Per image i < k, with
+ * l_s = logw[s][i] and d_s = digits[s][i] clamped to [0, T], s = 0 .. K - 1 in order everywhere:
+ *   m = the first maximum: m = l_0; then s = 1 ..: if (l_s > m || l_s != l_s) m = l_s  (a NaN stays).  An image whose m is
+ *   not finite (every weight zero, an infinite one, a NaN) is DEGENERATE: it adds 1 to counts[AIR_IW_DEGENERATE] and nothing
+ *   else to any sum or count but IMAGES; its optional outputs are NaN, NaN and -1.  Otherwise, e_s = exp(l_s - m):
+ *   S = (((+0.0 + e_0) + e_1) + ...),  S2 = (((+0.0 + e_0 * e_0) + e_1 * e_1) + ...),  L = (((+0.0 + l_0) + l_1) + ...)
+ *   bound_i = m + log(S / K)     elbo_i = L / K     ess_i = (S * S) / S2          (K widened)
+ *   W_c = (((+0.0 + [d_0 == c] e_0) + ...), the terms of other counts skipped, for c = 0 .. T: the count posterior
+ *   map_i = the first c with the largest W_c (W_c > best, best starts at W_0)
+ *   entropy_i = -(((+0.0 + p_0 log p_0) + ...) over c in order, p_c = W_c / S, a c with W_c == 0 skipped
+ *   split_i = any d_s != d_0
+ * exp and log are the device library's fp64 functions (within 3 ulp: the tests allow 8 (K + T + 2) 2^-52 on the sums).
+ * Accumulators: the caller zeroes them once; a call ADDS, so the chunks of a test set add up.
+ *   counts[AIR_IW_IMAGES] += k, [DEGENERATE] += the degenerate ones, [SCORED] += the others, [SPLIT] += sum split_i and,
+ *   when targets is given (g_i = targets[i] clamped to [0, T]): [MAP_CORRECT] += images with map_i == g_i, and the confusion
+ *   matrix counts[AIR_IW_COUNTS + g_i * (T + 1) + map_i] += 1  ((T + 1) rows, truth, of (T + 1), MAP).  Integer atomics.
+ *   sums[AIR_IW_BOUND / ELBO / ESS / ENTROPY] += bound_i / elbo_i / ess_i / entropy_i, each in the ONE order of
+ *   air_localization's sums with its group AIR_LOC_GROUP: the values of a group (+0.0 for an image >= k or degenerate)
+ *   folded by the adjacent pairwise tree, the group totals added in group order from +0.0, then sums[.] = incoming + the
+ *   batch total.  The order depends on k alone, so the same tables give the same bits; two calls over the halves of a
+ *   batch associate the additions differently from one call over the whole and agree with it to rounding only.
+ * bound, ess [k] fp64 and map [k] int32 are nullable, each on its own.  Two launches, no synchronisation, no host read.
+ * Refusals, in this order.  AIR_EINVAL: a null descriptor; T, B, k or K < 1; k > B.  AIR_ELIMIT: T > AIR_MAX_STEPS,
+ * K > AIR_IW_MAX_SAMPLES.  AIR_EINVAL: a null logw, digits, counts, sums or workspace. */
+enum { AIR_IW_IMAGES = 0, AIR_IW_SCORED = 1, AIR_IW_DEGENERATE = 2, AIR_IW_MAP_CORRECT = 3, AIR_IW_SPLIT = 4,
+       AIR_IW_COUNTS = 5 };
+enum { AIR_IW_BOUND = 0, AIR_IW_ELBO = 1, AIR_IW_ESS = 2, AIR_IW_ENTROPY = 3, AIR_IW_SUMS = 4 };
+typedef struct {
+    const double* logw;                  /* [K, B]                                                                      */
+    const int32_t* digits;               /* [K, B]                                                                      */
+    const int32_t* targets;              /* [k] true counts, nullable                                                   */
+    double* bound;                       /* out [k], nullable                                                           */
+    double* ess;                         /* out [k], nullable                                                           */
+    int32_t* map;                        /* out [k], nullable                                                           */
+    int64_t* counts;                     /* in / out [AIR_IW_COUNTS + (T + 1) * (T + 1)]                                */
+    double* sums;                        /* in / out [AIR_IW_SUMS]                                                      */
+    int32_t T, B, k, K;
+} air_importance_fold_t;
+/* `workspace`: a device buffer of at least air_importance_fold_workspace_bytes(T, B, k, K) bytes, 8-byte aligned (the
+ * per-group partial sums) */
+int air_importance_fold(const air_importance_fold_t* args, void* workspace, void* stream);
+/* bytes of `workspace`, or AIR_EINVAL / AIR_ELIMIT for a (T, B, k, K) the entry point refuses -- no GPU is touched */
+int64_t air_importance_fold_workspace_bytes(int T, int B, int k, int K);
+
 #ifdef __cplusplus
 }
 #endif

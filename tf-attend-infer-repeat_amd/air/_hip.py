@@ -285,6 +285,27 @@ class LatentProbe(C.Structure):
                 ("au_threshold", C.c_double)]
 
 
+IW_MAX_SAMPLES, IW_MAX_Z = 64, 256
+IW_TERM_REC, IW_TERM_Z_PRES, IW_TERM_SCALE, IW_TERM_SHIFT, IW_TERM_WHAT, IW_TERMS = 0, 1, 2, 3, 4, 5
+IW_IMAGES, IW_SCORED, IW_DEGENERATE, IW_MAP_CORRECT, IW_SPLIT, IW_COUNTS = 0, 1, 2, 3, 4, 5
+IW_BOUND, IW_ELBO, IW_ESS, IW_ENTROPY, IW_SUMS = 0, 1, 2, 3, 4
+
+
+class Importance(C.Structure):
+    """air_importance_t: the records, posterior parameters, samples and noise one pass left on the device in, row `sample`
+    of the log-weight, count and (nullable) term tables out"""
+    _fields_ = [("att", _p), ("out7", _p), ("ml", _p), ("z", _p), ("eps_scale", _p), ("eps_shift", _p), ("eps_z", _p),
+                ("rec_loss", _p), ("run_digits", _p), ("dyn", _p), ("logw", _p), ("digits", _p), ("terms", _p),
+                ("T", _i), ("B", _i), ("k", _i), ("Z", _i), ("ldz", _i), ("K", _i)]
+
+
+class ImportanceFold(C.Structure):
+    """air_importance_fold_t: the [K, B] tables and the nullable true counts in, the optional per-image outputs out, and the
+    int64 / fp64 accumulators a call adds to"""
+    _fields_ = [("logw", _p), ("digits", _p), ("targets", _p), ("bound", _p), ("ess", _p), ("map", _p),
+                ("counts", _p), ("sums", _p), ("T", _i), ("B", _i), ("k", _i), ("K", _i)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -379,6 +400,9 @@ _SIGNATURES = {
     "air_latent_probe": (C.c_int, [C.POINTER(LatentProbe), _p, _p]),
     "air_latent_probe_workspace_bytes": (C.c_int64, [C.c_int] * 3),
     "air_latent_probe_splits": (C.c_int, [C.c_int]),
+    "air_importance_logw": (C.c_int, [C.POINTER(Importance), C.c_int, _p]),
+    "air_importance_fold": (C.c_int, [C.POINTER(ImportanceFold), _p, _p]),
+    "air_importance_fold_workspace_bytes": (C.c_int64, [C.c_int] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -101,6 +101,8 @@ KERNEL_NAMES = {
     "air_scene_masks": "scene_masks_kernel",                            # (Segmentation.scene_masks)
     "air_latent_probe": "probe_pairs_kernel",                           # (air.metrics.LatentProbe; probe_valid / probe_moments
     #                                                                      before, probe_merge after; the *16_kernel pair for k > 8)
+    "air_importance_logw": "iw_logw_kernel",                            # (air.metrics.ImportanceBound, once per sampled pass)
+    "air_importance_fold": "iw_image_kernel",                           # (then iw_fold_kernel)
 }
 
 
@@ -1082,6 +1084,22 @@ class AIRModel:
             self._graph[0].replay()
         else:
             self._run_forward(self._stream())
+        self._dirty = False
+        self._steps_executed = None
+        return self
+
+    def forward_sampled(self, call, seed=None):
+        """One evaluation pass on FRESH noise (air.metrics.ImportanceBound): air_philox_fill under the key (seed or the
+        model's seed, call) into the model's own noise buffers, then the forward launches that read them as given.  A test
+        model's global_step never moves, so forward() draws the same noise every time; here the caller counts its calls.
+        Eager only, on the current stream: the injected-noise flag, a captured graph and global_step are not touched, and a
+        forward() afterwards draws its own noise again and gives what it gave before."""
+        H.require_device(self.input_images, "the model's input buffer", "AIRModel.forward_sampled", capture_too=True)
+        self._fresh_shadow()
+        seed = self._seed if seed is None else int(seed)
+        H.launch("air_philox_fill", self.input_images.device, _ptr(self.normals), self.normals.numel(), _ptr(self.uniforms),
+                 self.uniforms.numel(), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(call)))
+        _enqueue(self._forward_plan(injected=True), self._stream())
         self._dirty = False
         self._steps_executed = None
         return self

@@ -38,7 +38,18 @@ them: exact leave-one-out k-nearest-neighbour digit accuracy with its confusion 
 
 All three are one protocol (_Instrument): ``evaluate(*truth)`` is reset() + update(*truth) (+ score() for the probe), the
 model's last pass scored alone; ``prefix``, ``group``, ``reported`` and ``nan_in_events`` say how a driver names and writes
-the values, so training.py carries a list of instruments without knowing which they are."""
+the values, so training.py carries a list of instruments without knowing which they are.
+
+``ImportanceBound(model, samples=K)`` is the fourth, and the one that runs passes of its own: HOW LIKELY is the data, and how
+sure is the model of the count?  ``evaluate(targets)`` runs K passes on fresh noise (AIRModel.forward_sampled), turns each
+into a row of log-weights (air_importance_logw) and folds the rows (air_importance_fold) into the K-sample
+importance-weighted bound, the effective sample size and the posterior over the object count.
+
+    iw = ImportanceBound(test_model, samples=16)
+    iw.evaluate(targets)                                # K x (forward_sampled, air_importance_logw), one fold
+    iw.values()                                         # float64 [7] on the device: nll_bound, sample_loss, gap, ...
+
+It leaves the buffers of its LAST SAMPLED pass in the model: instruments that score forward()'s pass go before it."""
 import ctypes as C
 
 import numpy as np
@@ -441,4 +452,117 @@ class LatentProbe(_Instrument):
         out.update(zip(PROBE_NAMES, values))
         out.update(matched=counters[H.EMBED_MATCHED], present=counters[H.EMBED_PRESENT], inferred=counters[H.EMBED_INFERRED],
                    overflow=bool(counters[H.EMBED_OVERFLOW]), capacity=self.capacity)
+        return out
+
+
+IW_NAMES = ("nll_bound", "sample_loss", "gap", "ess_share", "count_accuracy", "count_entropy", "count_split")
+_IW_SALT = 0x4957                                  # the instrument's noise is not the generator's at the same call number
+
+
+class ImportanceBound(_Instrument):
+    """How likely is the data, and how sure is the model of the count?  K passes on fresh noise, each turned into a row of
+    log-weights log p(x, z) - log q(z | x) by air_importance_logw, and the rows folded by air_importance_fold
+    (include/air_hip.h has the semantics of both) into fp64 accumulators on the device, so the chunks of a test set add up.
+
+        iw = ImportanceBound(test_model, samples=16)
+        iw.evaluate(targets)                  # reset(), K x add_sample(), fold(targets)
+        iw.values()                           # float64 [7] on the device, names() order; never blocks
+        iw.result()                           # dict of floats + "confusion" [T + 1, T + 1] (true count x MAP count)
+
+    nll_bound = -BOUND / SCORED (the K-sample importance-weighted bound on -log p(x): it tightens with K), sample_loss =
+    -ELBO / SCORED (the mean one-sample bound of the same K passes), gap = sample_loss - nll_bound (>= 0), ess_share = ESS /
+    (K SCORED) (1: the weights are equal; 1 / K: one sample carries the image), count_accuracy = MAP_CORRECT / SCORED (the
+    count with the largest posterior weight against `targets`; NaN without), count_entropy = ENTROPY / SCORED (nats, of the
+    count posterior), count_split = SPLIT / SCORED (images whose K passes did not agree on the count); a zero denominator
+    gives NaN.  An image without a finite weight is counted as degenerate and left out of SCORED.
+
+    The noise of pass n is air_philox_fill's under (seed, n): ``calls`` runs on across evaluations, so successive
+    evaluations see different noise, and the same (seed, calls) reproduces every bit.  The model keeps the buffers of the
+    last sampled pass; forward() afterwards gives what it gave before.  keep=True also keeps ``terms`` [K, B, 5] float64
+    (rec, z_pres, scale, shift, what of every weight) and ``bound``, ``ess`` [B] float64, ``map`` [B] int32 of the last
+    fold (rows >= k are not written)."""
+    NAMES = reported = IW_NAMES
+    prefix, group = "iw_", "importance/"
+
+    def __init__(self, model, samples=16, seed=0, keep=False):
+        self.op = "ImportanceBound"
+        self.model, self.T, self.B = model, int(model.max_steps), int(model.batch_size)
+        K = self.K = self.G = int(samples)            # (G: where _accumulators passes the fourth size of the workspace query)
+        T, B, Z = self.T, self.B, int(model.vae_latent_dimensions)
+        if K < 1:
+            raise ValueError("ImportanceBound: samples must be positive")
+        if T > H.MAX_STEPS or K > H.IW_MAX_SAMPLES or Z > H.IW_MAX_Z:
+            raise NotImplementedError("ImportanceBound: %d steps, %d samples, %d latent dimensions: the kernels hold %d, %d and %d"
+                                      % (T, K, Z, H.MAX_STEPS, H.IW_MAX_SAMPLES, H.IW_MAX_Z))
+        self.Z, self.seed, self.calls, self._sample, self._targets = Z, int(seed), 0, 0, False
+        dev = self._accumulators("air_importance_fold_workspace_bytes", H.IW_COUNTS + (T + 1) * (T + 1), H.IW_SUMS)
+        self.logw = torch.full((K, B), float("nan"), dtype=torch.float64, device=dev)
+        self.digits = torch.zeros(K, B, dtype=torch.int32, device=dev)
+        self.terms = torch.full((K, B, H.IW_TERMS), float("nan"), dtype=torch.float64, device=dev) if keep else None
+        self.bound = torch.full((B,), float("nan"), dtype=torch.float64, device=dev) if keep else None
+        self.ess = torch.full((B,), float("nan"), dtype=torch.float64, device=dev) if keep else None
+        self.map = torch.full((B,), -1, dtype=torch.int32, device=dev) if keep else None
+
+    def reset(self):
+        """zeroes the accumulators on the current stream and forgets the passes sampled so far (not the call counter)"""
+        super().reset()
+        self._sample = 0
+
+    def add_sample(self, k=None):
+        """One pass of the model on fresh noise and one air_importance_logw call: the next row of the tables, for the first k
+        images (default: the whole batch).  K of them, then fold()."""
+        if self._sample >= self.K:
+            raise RuntimeError("ImportanceBound.add_sample: all %d samples are drawn -- fold() them first" % self.K)
+        k = self._images(self.B if k is None else k, None)
+        m = self.model
+        m.forward_sampled(self.calls, (self.seed ^ _IW_SALT) & 0xFFFFFFFFFFFFFFFF)
+        self.calls += 1
+        a = H.Importance(H.ptr(m.att), H.ptr(m.out7), H.ptr(m.ml), H.ptr(m.zs), H.ptr(m.eps_scale), H.ptr(m.eps_shift),
+                         H.ptr(m.eps_z), H.ptr(m._rec_loss), H.ptr(m.run_digits), H.ptr(m.dyn), H.ptr(self.logw),
+                         H.ptr(self.digits), H.ptr(self.terms), self.T, self.B, k, self.Z, int(m.zs.stride(1)), self.K)
+        H.launch("air_importance_logw", self.device, C.byref(a), self._sample)
+        self._sample += 1
+
+    def fold(self, targets=None, k=None):
+        """One air_importance_fold call over the K rows drawn since the last fold, added to the accumulators.  targets: the
+        true counts of at least k images (a device int32 tensor, or a numpy array: copied), or None."""
+        if self._sample != self.K:
+            raise RuntimeError("ImportanceBound.fold: %d of %d samples are drawn" % (self._sample, self.K))
+        k = self._images(self.B if k is None else k, None)
+        if targets is not None:
+            targets = self._truth(targets, "targets", k, 1)
+        self._targets = targets is not None
+        a = H.ImportanceFold(H.ptr(self.logw), H.ptr(self.digits), H.ptr(targets), H.ptr(self.bound), H.ptr(self.ess),
+                             H.ptr(self.map), H.ptr(self.counts), H.ptr(self.sums), self.T, self.B, k, self.K)
+        H.launch("air_importance_fold", self.device, C.byref(a), H.ptr(self.workspace))
+        self._sample = 0
+
+    def evaluate(self, targets=None, k=None):
+        """reset(), K x add_sample() and fold(targets): the model's current batch scored from zero, on the current stream"""
+        self.reset()
+        for _ in range(self.K):
+            self.add_sample(k)
+        self.fold(targets, k)
+
+    def values(self, out=None):
+        """float64 [len(names())] on the device, from the accumulators as they stand on the current stream; never blocks"""
+        c, s = self.counts, self.sums
+        scored = c[H.IW_SCORED].double()
+        correct = c[H.IW_MAP_CORRECT].double() if self._targets else self._nan[0]
+        num = torch.stack((-s[H.IW_BOUND], -s[H.IW_ELBO], s[H.IW_BOUND] - s[H.IW_ELBO], s[H.IW_ESS], correct, s[H.IW_ENTROPY],
+                           c[H.IW_SPLIT].double()))
+        den = torch.stack((scored, scored, scored, scored * self.K, scored, scored, scored))
+        return self._ratios(num, den, out)
+
+    def confusion(self):
+        """int64 [T + 1, T + 1] view of the accumulators: rows the true count, columns the MAP count"""
+        return self.counts[H.IW_COUNTS:].view(self.T + 1, self.T + 1)
+
+    def result(self):
+        """the values as a dict of floats, the raw totals and the confusion matrix as numpy -- synchronises"""
+        values, counts, sums = self.values().cpu().tolist(), self.counts.cpu().numpy(), self.sums.cpu().numpy()
+        out = dict(zip(IW_NAMES, values))
+        out.update(images=int(counts[H.IW_IMAGES]), scored=int(counts[H.IW_SCORED]), degenerate=int(counts[H.IW_DEGENERATE]),
+                   samples=self.K, calls=self.calls,
+                   confusion=counts[H.IW_COUNTS:].reshape(self.T + 1, self.T + 1).copy(), sums=sums)
         return out

@@ -321,6 +321,11 @@ def instruments(args, model, test):
             "latent probe, {}-NN over {} matched digits: ".format(lat.k, res["scored"]),
             "  (the store overflowed)" if res["overflow"] else "",
             "digit confusion (rows: true class 0..{}, columns: predicted):".format(lat.classes - 1))))
+    if args.importance_samples:                 # LAST: its sampled passes replace the buffers the others read
+        iw = metrics.ImportanceBound(model, args.importance_samples, seed=args.seed)
+        out.append((iw, (test["digits"],), lambda res: (
+            "importance bound, {} samples over {} images ({} degenerate): ".format(iw.K, res["scored"], res["degenerate"]), "",
+            "count confusion (rows: digits present 0..{}, columns: the posterior's most likely count 0..{}):".format(iw.T, iw.T))))
     return out
 
 
@@ -406,7 +411,15 @@ def main():
                              "units): the rows of summary/scalars.jsonl gain lat_* keys, --tensorboard gains latents/* scalars, "
                              "and the run ends with the confusion matrix of the digits.  Needs the boxes and labels of the test set")
     parser.add_argument("--latent-k", type=int, default=5, help="--latent-probe: the neighbours that vote (1 .. 16)")
+    parser.add_argument("--importance-samples", type=int, default=0, metavar="K",
+                        help="score every evaluation by K passes of the test model on fresh noise as well (air.metrics."
+                             "ImportanceBound; 0: off, at most 64): the K-sample importance-weighted bound on the negative "
+                             "log-likelihood, the effective sample size and the posterior over the object count.  The rows of "
+                             "summary/scalars.jsonl gain iw_* keys, --tensorboard gains importance/* scalars, and the run ends "
+                             "with the confusion matrix of the most likely counts")
     args = parser.parse_args()
+    if not 0 <= args.importance_samples <= 64:
+        parser.error("--importance-samples must lie in 0 .. 64")
     if args.latent_probe and not 1 <= args.latent_k <= 16:
         parser.error("--latent-k must lie in [1, 16]")
     if args.latent_probe and args.glyph_style != "mnist-like" and cache_without(("positions", "boxes", "labels")):
@@ -555,6 +568,8 @@ def main():
             writer.push(step)
             if board and step % VAR_SUMMARIES_EACH_ITERATIONS == 0:
                 if step % IMG_SUMMARIES_EACH_ITERATIONS == 0:
+                    if args.importance_samples:                       # (the model holds the last SAMPLED pass: the images are
+                        test_model.forward()                          # those of the pass the other summaries describe)
                     board.image(step)
                 board.variables(step)
         if step % SAVE_PARAMS_EACH_ITERATIONS == 0:
