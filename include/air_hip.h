@@ -1517,6 +1517,88 @@ int air_importance_fold(const air_importance_fold_t* args, void* workspace, void
 /* bytes of `workspace`, or AIR_EINVAL / AIR_ELIMIT for a (T, B, k, K) the entry point refuses -- no GPU is touched */
 int64_t air_importance_fold_workspace_bytes(int T, int B, int k, int K);
 
+/* ---- latent clusters (additive to ABI 6) -------------------------------------------------------------------------------------
+ * Do classes emerge in the what-codes ON THEIR OWN?  Exact k-means (Lloyd's loop, R restarts from seeded draws) over a set of
+ * latent codes, and -- where labels are given -- the cluster x class table of the best restart with each cluster's majority
+ * class, from which the caller derives clustering accuracy (purity), the adjusted Rand index and the normalised mutual
+ * information.  air/metrics.py (LatentClusters) and air/embeddings.py (cluster) are the callers;
+ * tests/latent_kmeans_cases.py restates every operation below.  All arithmetic is fp64 in exactly the order written here (the
+ * translation unit has -ffp-contract=off); no floating-point atomics, no grid-wide wait: the same inputs give the same bits.
+ *
+ * Rows.  M_eff = rows ? clamp(*rows, 0, M) : M, as for the latent probe; rows >= M_eff of latents and labels are never read.
+ * x[i][z] = latents[i * Z + z], read float by float (rows are only 4-byte aligned).  Row i < M_eff is VALID when all its Z
+ * values are finite -- the label plays no part.  A valid row is LABELLED when labels is not null and 0 <= labels[i] < classes.
+ * V = the number of valid rows, k_eff = min(k, V).  Clusters c >= k_eff do not exist.
+ *
+ * Squared distance of a valid row and a centroid:  d2(i, c) = (((+0.0 + e_0 * e_0) + e_1 * e_1) + ...), z ascending,
+ *   e_z = (double)x[i][z] - mu[c][z].
+ *
+ * Start of restart r < R.  idx[0 .. V - 1] = the valid rows in ascending order.  For t = 0 .. k_eff - 1:
+ *   j = t + umulhi(word_t, V - t) (the high 32 bits of the 64-bit product), swap idx[t] and idx[j]; then mu[t][z] =
+ *   (double)x[idx[t]][z].  word_t is word t & 3 of Philox4x32-10 (csrc/air_philox.h) with key (seed & 0xffffffff, seed >> 32)
+ *   and counter (r, t >> 2, 0, 0x4B4D4E53).  Integers only; the k_eff start rows of a restart are distinct rows.
+ *
+ * Lloyd's loop of a restart.  a[i] = -1 for every row; for it = 1 .. max_iters:
+ *   assign  a'[i] = the c < k_eff with the smallest d2(i, c), a tie to the lowest c, for every valid row;
+ *           changed = the valid rows with a'[i] != a[i];  a = a'.
+ *   stop    when changed == 0 (CONVERGED, restart_iters[r] = it) or it == max_iters (not converged unless changed == 0).
+ *   update  otherwise, for every cluster with n_c > 0 members: mu[c][z] = S / (double)n_c, S = the sum of (double)x[i][z]
+ *           over its members added one by one from +0.0 in ascending row order.  A cluster without members keeps its
+ *           centroid (and may win rows later).
+ * The restart's assignment, its per-row d2, its centroids and its inertia are those of the LAST assign step (so the centroids
+ * of a converged restart are the stated means of its members).  restart_inertia[r] = the sum of d2(i, a[i]) over the valid
+ * rows, added one by one from +0.0 in ascending row order.
+ * Best restart: the lowest inertia, a tie to the lowest r (restarts that find the same partition under permuted cluster
+ * indices tie to the bit).
+ *
+ * Outputs: EVERY element is written on EVERY call.
+ *   assignment [M]: the cluster of the best restart; -1 for an invalid row and a row >= M_eff.
+ *   row_d2 [M] (nullable): d2(i, assignment[i]); +0.0 where the assignment is -1.
+ *   centroids [k, Z]: of the best restart; clusters >= k_eff hold the quiet NaN 0x7FF8000000000000.
+ *   restart_inertia [R], restart_iters [R].
+ *   counts[AIR_KMEANS_ROWS] = M_eff, [VALID] = V, [LABELLED] = labelled rows, [CORRECT] = sum over c of max_l table[c][l],
+ *   [LIVE] = clusters of the best restart with members, [BEST] = its index, [ITERS] = its iterations, [CONVERGED] = 0 / 1 for
+ *   it, [RESTARTS_CONVERGED] = how many restarts converged; then sizes[k] (valid members per cluster), majority[k] (the first
+ *   maximum of table[c][.], -1 for a cluster without labelled members) and table[k x classes] (the labelled rows by
+ *   cluster x label) at counts[AIR_KMEANS_COUNTS], [AIR_KMEANS_COUNTS + k] and [AIR_KMEANS_COUNTS + 2 k].
+ * V == 0: no restart runs.  restart_inertia is the quiet NaN, restart_iters 0, every centroid NaN, every assignment -1, and
+ * every count but ROWS is 0 (majority: -1).
+ *
+ * Three launches on the caller's stream, no synchronisation, no host read: validity flags (a thread per row); the restarts (a
+ * workgroup per restart, its whole loop inside the kernel, the centroids in up to 130 KiB of LDS); the pick (one workgroup:
+ * the winner copied out, the table and the counts).  Call it eagerly once before capturing it (the LDS grant).
+ *
+ * Refusals, on the host before any HIP call, in this order.  AIR_EINVAL: a null descriptor; M, Z, k, classes, restarts or
+ * max_iters < 1.  AIR_ELIMIT: k > AIR_KMEANS_MAX_K, restarts > AIR_KMEANS_MAX_RESTARTS, max_iters > AIR_KMEANS_MAX_ITERS,
+ * Z > AIR_PROBE_MAX_Z, classes > AIR_PROBE_MAX_CLASSES, M > AIR_PROBE_MAX_ROWS.  AIR_EINVAL: a null latents, assignment,
+ * centroids, restart_inertia, restart_iters, counts or workspace.  AIR_EALIGN: row_d2, centroids, restart_inertia or the
+ * workspace not 8-byte aligned. */
+#define AIR_KMEANS_MAX_K 64
+#define AIR_KMEANS_MAX_RESTARTS 32
+#define AIR_KMEANS_MAX_ITERS 1000
+enum { AIR_KMEANS_ROWS = 0, AIR_KMEANS_VALID = 1, AIR_KMEANS_LABELLED = 2, AIR_KMEANS_CORRECT = 3, AIR_KMEANS_LIVE = 4,
+       AIR_KMEANS_BEST = 5, AIR_KMEANS_ITERS = 6, AIR_KMEANS_CONVERGED = 7, AIR_KMEANS_RESTARTS_CONVERGED = 8,
+       AIR_KMEANS_COUNTS = 9 };
+typedef struct {
+    const float* latents;                /* [M, Z]                                                                      */
+    const int32_t* labels;               /* [M], nullable: clustering needs none                                        */
+    const int32_t* rows;                 /* nullable: ONE device int32, the rows in use (clamped to [0, M])             */
+    int32_t* assignment;                 /* out [M]                                                                     */
+    double* row_d2;                      /* out [M], nullable                                                           */
+    double* centroids;                   /* out [k, Z]                                                                  */
+    double* restart_inertia;             /* out [restarts]                                                              */
+    int32_t* restart_iters;              /* out [restarts]                                                              */
+    int64_t* counts;                     /* out [AIR_KMEANS_COUNTS + 2 k + k * classes]                                 */
+    int32_t M, Z, k, classes, restarts, max_iters;
+    uint64_t seed;
+} air_latent_kmeans_t;
+/* `workspace`: a device buffer of at least air_latent_kmeans_workspace_bytes(M, Z, k, restarts) bytes, 8-byte aligned (the
+ * assignment, d2 and centroids of every restart, the validity flags) */
+int air_latent_kmeans(const air_latent_kmeans_t* args, void* workspace, void* stream);
+/* bytes of `workspace`: 8 R M + 8 R k Z + pad8(4 R M) + pad8(4 M) + pad8(4 R), or AIR_EINVAL / AIR_ELIMIT for an
+ * (M, Z, k, restarts) the entry point refuses -- no GPU is touched */
+int64_t air_latent_kmeans_workspace_bytes(int M, int Z, int k, int restarts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -306,6 +306,20 @@ class ImportanceFold(C.Structure):
                 ("counts", _p), ("sums", _p), ("T", _i), ("B", _i), ("k", _i), ("K", _i)]
 
 
+KMEANS_MAX_K, KMEANS_MAX_RESTARTS, KMEANS_MAX_ITERS = 64, 32, 1000
+KMEANS_ROWS, KMEANS_VALID, KMEANS_LABELLED, KMEANS_CORRECT, KMEANS_LIVE, KMEANS_BEST, KMEANS_ITERS = 0, 1, 2, 3, 4, 5, 6
+KMEANS_CONVERGED, KMEANS_RESTARTS_CONVERGED, KMEANS_COUNTS = 7, 8, 9
+
+
+class LatentKmeans(C.Structure):
+    """air_latent_kmeans_t: latent codes and their nullable labels in (rows: a nullable device int32, how many are in use),
+    the best restart's assignment, optional d2 and centroids, every restart's inertia and iterations and the int64 counts
+    (scalars, sizes[k], majority[k], table[k x classes]) out -- all written whole"""
+    _fields_ = [("latents", _p), ("labels", _p), ("rows", _p), ("assignment", _p), ("row_d2", _p), ("centroids", _p),
+                ("restart_inertia", _p), ("restart_iters", _p), ("counts", _p),
+                ("M", _i), ("Z", _i), ("k", _i), ("classes", _i), ("restarts", _i), ("max_iters", _i), ("seed", C.c_uint64)]
+
+
 _SIGNATURES = {
     "air_abi_version": (C.c_int, []),
     "air_strerror": (C.c_char_p, [C.c_int]),
@@ -403,6 +417,8 @@ _SIGNATURES = {
     "air_importance_logw": (C.c_int, [C.POINTER(Importance), C.c_int, _p]),
     "air_importance_fold": (C.c_int, [C.POINTER(ImportanceFold), _p, _p]),
     "air_importance_fold_workspace_bytes": (C.c_int64, [C.c_int] * 4),
+    "air_latent_kmeans": (C.c_int, [C.POINTER(LatentKmeans), _p, _p]),
+    "air_latent_kmeans_workspace_bytes": (C.c_int64, [C.c_int] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

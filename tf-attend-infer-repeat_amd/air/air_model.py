@@ -103,6 +103,8 @@ KERNEL_NAMES = {
     #                                                                      before, probe_merge after; the *16_kernel pair for k > 8)
     "air_importance_logw": "iw_logw_kernel",                            # (air.metrics.ImportanceBound, once per sampled pass)
     "air_importance_fold": "iw_image_kernel",                           # (then iw_fold_kernel)
+    "air_latent_kmeans": "kmeans_restart_kernel",                       # (air.metrics.LatentClusters; kmeans_valid before,
+    #                                                                      kmeans_pick after)
 }
 
 

@@ -152,6 +152,75 @@ def write_probe(folder, summary, name="latent_probe.json"):
     return path
 
 
+def cluster(latents, labels=None, clusters=10, classes=10, restarts=8, max_iters=50, seed=0):
+    """Do classes emerge in the latents on their own?  Exact k-means over latents [M, Z] (float32, on the device) and, where
+    labels [M] (int32) are given, every cluster mapped to its majority class: one air_latent_kmeans call
+    (air.metrics.LatentClusters has the dict's keys: accuracy, ari, nmi, inertia, the table, sizes, majority, centroids,
+    assignment, every restart's inertia and iterations).  labels=None clusters without scoring."""
+    from .metrics import _KMeansBuffers
+    H.require_device(latents, "latents", "embeddings.cluster", capture_too=True)
+    if labels is not None:
+        H.require_device(labels, "labels", "embeddings.cluster")
+        if labels.dtype != torch.int32 or labels.dim() != 1 or labels.shape[0] != latents.shape[0] or labels.device != latents.device:
+            raise ValueError("embeddings.cluster: labels must be int32 [M] on the device of the latents")
+        labels = labels.contiguous()
+    if latents.dim() != 2 or latents.dtype != torch.float32:
+        raise ValueError("embeddings.cluster: latents must be float32 [M, Z]")
+    M, Z = int(latents.shape[0]), int(latents.shape[1])
+    if M < 1:
+        raise ValueError("embeddings.cluster: no rows, nothing to cluster")
+    buffers = _KMeansBuffers("embeddings.cluster", latents.device, M, Z, clusters, classes, restarts, max_iters, seed, False).allocate()
+    buffers.run(latents.contiguous(), labels)
+    return buffers.summary()
+
+
+def centroid_windows(model, centroids):
+    """What does each discovered class look like?  centroids [n, Z] (what-codes: cluster()'s, NaN rows left out by the
+    caller) -> float32 [n, w, w] on the device: the decoder's window of each, through AIRModel.decode -- centroid i is
+    object 0 of its own scene with z_pres 1, the other objects absent, batch_size scenes a call.  Eager only."""
+    B, N, Z, w = int(model.batch_size), int(model.max_steps), int(model.vae_latent_dimensions), int(model.windows_size)
+    dev = model.input_images.device
+    H.require_device(model.input_images, "the model's input buffer", "embeddings.centroid_windows", capture_too=True)
+    codes = torch.as_tensor(np.asarray(_host(centroids), np.float32)).to(dev)
+    if codes.dim() != 2 or int(codes.shape[1]) != Z or not bool(torch.isfinite(codes).all()):
+        raise ValueError("embeddings.centroid_windows: centroids must be finite [n, %d]" % Z)
+    n = int(codes.shape[0])
+    out = torch.empty(n, w, w, dtype=torch.float32, device=dev)
+    scales, shifts = torch.ones(B, N, 1, device=dev), torch.zeros(B, N, 2, device=dev)
+    z_pres = torch.zeros(B, N, device=dev)
+    z_pres[:, 0] = 1.0
+    for lo in range(0, n, B):
+        take = min(B, n - lo)
+        latents = torch.zeros(B, N, Z, device=dev)
+        latents[:take, 0] = codes[lo:lo + take]
+        scenes = model.decode(latents, scales, shifts, z_pres)
+        out[lo:lo + take] = scenes.windows[:take, 0].reshape(take, w, w)
+    return out
+
+
+def write_clusters(folder, summary, model=None, name="clusters.npz", sheet_name="cluster_sprites.png"):
+    """cluster()'s dict as clusters.npz (centroids, assignment, table, sizes, majority, the restarts' inertia and iterations,
+    `values` in `names` order) and, with a model, cluster_sprites.png: centroid_windows() of the clusters with members, laid
+    out by sprite_sheet(); returns the paths"""
+    import tf_events
+    from .metrics import CLUSTER_NAMES
+    folder = os.path.abspath(folder)
+    os.makedirs(folder, exist_ok=True)
+    paths = {"clusters": os.path.join(folder, name)}
+    live = np.nonzero(summary["sizes"] > 0)[0]
+    np.savez(paths["clusters"], centroids=summary["centroids"], assignment=summary["assignment"], table=summary["table"],
+             sizes=summary["sizes"], majority=summary["majority"], restart_inertia=summary["restart_inertia"],
+             restart_iters=summary["restart_iters"], live=live, names=np.asarray(CLUSTER_NAMES),
+             values=np.asarray([summary[k] for k in CLUSTER_NAMES], np.float64),
+             best=summary["best"], iters=summary["iters"], converged=summary["converged"])
+    if model is not None and len(live):
+        sheet = sprite_sheet(centroid_windows(model, summary["centroids"][live]))
+        paths["sprites"] = os.path.join(folder, sheet_name)
+        with open(paths["sprites"], "wb") as f:
+            f.write(tf_events.encode_png(_host(sheet)))
+    return paths
+
+
 def _host(t):
     return t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
 

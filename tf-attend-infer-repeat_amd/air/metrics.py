@@ -36,7 +36,17 @@ them: exact leave-one-out k-nearest-neighbour digit accuracy with its confusion 
     probe.score()
     probe.values()                                      # float64 [4] on the device: knn_accuracy, active_units, scored, matched_share
 
-All three are one protocol (_Instrument): ``evaluate(*truth)`` is reset() + update(*truth) (+ score() for the probe), the
+``LatentClusters(model, max_gt_digits)`` asks the same store a question that needs no labelled neighbours: do digit classes
+emerge in the what-codes ON THEIR OWN?  ``update()`` is LatentProbe's (the two share the store and the collector call),
+``score()`` is one air_latent_kmeans call: exact k-means with seeded restarts, every cluster mapped to its majority class.
+
+    clu = LatentClusters(test_model, max_gt_digits=2)
+    test_model.forward()
+    clu.update(gt_count, gt_positions, gt_boxes, gt_labels)
+    clu.score()
+    clu.values()                                        # float64 [6] on the device: accuracy, ari, nmi, inertia, live_clusters, scored
+
+All of them are one protocol (_Instrument): ``evaluate(*truth)`` is reset() + update(*truth) (+ score() for the two above), the
 model's last pass scored alone; ``prefix``, ``group``, ``reported`` and ``nan_in_events`` say how a driver names and writes
 the values, so training.py carries a list of instruments without knowing which they are.
 
@@ -351,7 +361,74 @@ class _ProbeBuffers:
                     mean=moments[:self.Z].copy(), variance=moments[self.Z:].copy())
 
 
-class LatentProbe(_Instrument):
+class _LatentStore(_Instrument):
+    """What the instruments over the what-codes share (LatentProbe, LatentClusters): the store ``latents`` [capacity, Z] /
+    ``labels`` [capacity] of the matched digits' posterior means, with the collector's device counters as the cursor, and the
+    one air_embed_collect call that appends a pass to it.  A subclass holds ``counts``, which reset() zeroes, and score()."""
+
+    def _store_sizes(self, capacity, max_distance):
+        """the sizes of the store, checked on the host: capacity defaults to batch_size * max_gt_digits (one pass)"""
+        self.Z, self.w = int(self.model.vae_latent_dimensions), int(self.model.windows_size)
+        capacity = self.B * self.G if capacity is None else int(capacity)
+        if capacity < 1:
+            raise ValueError("%s: capacity must be positive" % self.op)
+        if not float(max_distance) > 0.0:
+            raise ValueError("%s: max_distance must be positive" % self.op)
+        self.capacity, self.max_distance = capacity, float(max_distance)
+        return capacity
+
+    def _store_allocate(self):
+        """the collector's workspace query, then the store on the model's device (which is returned)"""
+        T, B, G, Z, w, capacity = self.T, self.B, self.G, self.Z, self.w, self.capacity
+        nints = H.lib().air_embed_collect_workspace_ints(T, B, B, G)
+        if nints < 0:
+            raise NotImplementedError("%s: %d steps, %d digits in one image: the collector holds %d and %d"
+                                      % (self.op, T, G, H.EMBED_MAX_STEPS, H.EMBED_MAX_DIGITS))
+        dev = self._on_device(capture_too=True)
+        self.latents = torch.zeros(capacity, Z, dtype=torch.float32, device=dev)
+        self.labels = torch.zeros(capacity, dtype=torch.int32, device=dev)
+        self.counters = torch.zeros(H.EMBED_COUNTERS, dtype=torch.int32, device=dev)
+        self._windows = torch.empty(capacity, w * w, dtype=torch.float32, device=dev)       # the collector writes them: unused
+        self._ids = torch.empty(capacity, dtype=torch.int32, device=dev)
+        self._match = torch.empty(B, G, dtype=torch.int32, device=dev)
+        self._workspace = torch.empty(int(nints), dtype=torch.int32, device=dev)
+        self._one = torch.ones(1, dtype=torch.float64, device=dev)
+        return dev
+
+    def reset(self):
+        """zeroes the row cursor and the counts on the current stream"""
+        self.counters.zero_()
+        self.counts.zero_()
+
+    def evaluate(self, *truth):
+        """reset(), update(*truth) and score()"""
+        super().evaluate(*truth)
+        self.score()
+
+    def update(self, gt_count, gt_positions, gt_boxes, gt_labels, k=None):
+        """One air_embed_collect call over the model's last pass: the digits of its first k images (default: all rows of
+        gt_count) matched to the inferred objects by centre distance, the latent means of the matched ones appended to the
+        store with gt_labels [>= k, G] as their labels.  gt_positions / gt_boxes: [>= k, G, 2] or [>= k, 2 G]."""
+        m = self.model
+        m._ensure()
+        H.require_device(m.att, "the model's records", self.op + ".update", capture_too=True)
+        k = self._images(k, gt_count)
+        gt = (self._truth(gt_count, "gt_count", k, 1), self._truth(gt_positions, "gt_positions", k, 2 * self.G),
+              self._truth(gt_boxes, "gt_boxes", k, 2 * self.G), self._truth(gt_labels, "gt_labels", k, self.G))
+        a = H.EmbedCollect(H.ptr(m.att), H.ptr(m.run_digits), H.ptr(m.ml), H.ptr(m.vrec), *(H.ptr(t) for t in gt), H.ptr(gt[3]),
+                           H.ptr(self._match), H.ptr(self.counters), H.ptr(self.latents), H.ptr(self._windows),
+                           H.ptr(self.labels), H.ptr(self._ids), self.T, self.B, k, self.G, self.Z, self.w, self.capacity,
+                           m.canvas_size, self.max_distance)
+        H.launch("air_embed_collect", self.device, C.byref(a), H.ptr(self._workspace))
+
+    def _collected(self):
+        """the collector's totals as a dict of host values -- synchronises"""
+        counters = self.counters.cpu().tolist()
+        return dict(matched=counters[H.EMBED_MATCHED], present=counters[H.EMBED_PRESENT], inferred=counters[H.EMBED_INFERRED],
+                    overflow=bool(counters[H.EMBED_OVERFLOW]), capacity=self.capacity)
+
+
+class LatentProbe(_LatentStore):
     """Do the what-codes say WHAT the digits are?  The latent codes (posterior means) of the matched digits of an evaluation
     set, scored by air_latent_probe (include/air_hip.h has the semantics): the leave-one-out k-nearest-neighbour accuracy of
     their labels with its confusion matrix, and the active units (dimensions whose mean varies over the set, variance >
@@ -375,57 +452,13 @@ class LatentProbe(_Instrument):
 
     def __init__(self, model, max_gt_digits, classes=10, k=5, capacity=None, au_threshold=0.01, per_row=False, max_distance=0.2):
         super().__init__(model, max_gt_digits)
-        T, B, G = self.T, self.B, self.G
-        Z, w = self.Z, self.w = int(model.vae_latent_dimensions), int(model.windows_size)
-        capacity = B * G if capacity is None else int(capacity)
-        if capacity < 1:
-            raise ValueError("LatentProbe: capacity must be positive")
-        if not float(max_distance) > 0.0:
-            raise ValueError("LatentProbe: max_distance must be positive")
-        self.buffers = _ProbeBuffers("LatentProbe", None, capacity, Z, k, classes, au_threshold, per_row)
-        nints = H.lib().air_embed_collect_workspace_ints(T, B, B, G)
-        if nints < 0:
-            raise NotImplementedError("LatentProbe: %d steps, %d digits in one image: the collector holds %d and %d"
-                                      % (T, G, H.EMBED_MAX_STEPS, H.EMBED_MAX_DIGITS))
-        dev = self.buffers.device = self._on_device(capture_too=True)
-        self.k, self.classes, self.capacity, self.max_distance = self.buffers.k, self.buffers.classes, capacity, float(max_distance)
+        capacity = self._store_sizes(capacity, max_distance)
+        self.buffers = _ProbeBuffers("LatentProbe", None, capacity, self.Z, k, classes, au_threshold, per_row)
+        self.buffers.device = self._store_allocate()
+        self.k, self.classes = self.buffers.k, self.buffers.classes
         self.buffers.allocate()
         self.counts, self.moments = self.buffers.counts, self.buffers.moments
         self.pred, self.neighbours, self.neighbour_d2 = self.buffers.pred, self.buffers.neighbours, self.buffers.neighbour_d2
-        self.latents = torch.zeros(capacity, Z, dtype=torch.float32, device=dev)
-        self.labels = torch.zeros(capacity, dtype=torch.int32, device=dev)
-        self.counters = torch.zeros(H.EMBED_COUNTERS, dtype=torch.int32, device=dev)
-        self._windows = torch.empty(capacity, w * w, dtype=torch.float32, device=dev)       # the collector writes them: unused
-        self._ids = torch.empty(capacity, dtype=torch.int32, device=dev)
-        self._match = torch.empty(B, G, dtype=torch.int32, device=dev)
-        self._workspace = torch.empty(int(nints), dtype=torch.int32, device=dev)
-        self._one = torch.ones(1, dtype=torch.float64, device=dev)
-
-    def reset(self):
-        """zeroes the row cursor and the counts on the current stream"""
-        self.counters.zero_()
-        self.counts.zero_()
-
-    def evaluate(self, *truth):
-        """reset(), update(*truth) and score()"""
-        super().evaluate(*truth)
-        self.score()
-
-    def update(self, gt_count, gt_positions, gt_boxes, gt_labels, k=None):
-        """One air_embed_collect call over the model's last pass: the digits of its first k images (default: all rows of
-        gt_count) matched to the inferred objects by centre distance, the latent means of the matched ones appended to the
-        store with gt_labels [>= k, G] as their labels.  gt_positions / gt_boxes: [>= k, G, 2] or [>= k, 2 G]."""
-        m = self.model
-        m._ensure()
-        H.require_device(m.att, "the model's records", "LatentProbe.update", capture_too=True)
-        k = self._images(k, gt_count)
-        gt =(self._truth(gt_count, "gt_count", k, 1), self._truth(gt_positions, "gt_positions", k, 2 * self.G),
-              self._truth(gt_boxes, "gt_boxes", k, 2 * self.G), self._truth(gt_labels, "gt_labels", k, self.G))
-        a = H.EmbedCollect(H.ptr(m.att), H.ptr(m.run_digits), H.ptr(m.ml), H.ptr(m.vrec), *(H.ptr(t) for t in gt), H.ptr(gt[3]),
-                           H.ptr(self._match), H.ptr(self.counters), H.ptr(self.latents), H.ptr(self._windows),
-                           H.ptr(self.labels), H.ptr(self._ids), self.T, self.B, k, self.G, self.Z, self.w, self.capacity,
-                           m.canvas_size, self.max_distance)
-        H.launch("air_embed_collect", self.device, C.byref(a), H.ptr(self._workspace))
 
     def score(self):
         """One air_latent_probe call over the rows collected so far (the device cursor says how many: no host read)"""
@@ -447,11 +480,157 @@ class LatentProbe(_Instrument):
     def result(self):
         """the values as a dict of floats, the totals, the confusion matrix, the per-class recall and the moments as numpy
         -- synchronises"""
-        values, counters = self.values().cpu().tolist(), self.counters.cpu().tolist()
+        values = self.values().cpu().tolist()
         out = self.buffers.summary()
         out.update(zip(PROBE_NAMES, values))
-        out.update(matched=counters[H.EMBED_MATCHED], present=counters[H.EMBED_PRESENT], inferred=counters[H.EMBED_INFERRED],
-                   overflow=bool(counters[H.EMBED_OVERFLOW]), capacity=self.capacity)
+        out.update(self._collected())
+        return out
+
+
+CLUSTER_NAMES = ("accuracy", "ari", "nmi", "inertia", "live_clusters", "scored")
+
+
+class _KMeansBuffers:
+    """the outputs and the workspace of air_latent_kmeans for up to M rows of Z dimensions, the one call, and the numbers
+    derived from its counts"""
+
+    def __init__(self, op, dev, M, Z, k, classes, restarts, max_iters, seed, per_row):
+        k, classes, R, iters = int(k), int(classes), int(restarts), int(max_iters)
+        if k < 1 or classes < 1 or R < 1 or iters < 1 or M < 1 or Z < 1:
+            raise ValueError("%s: clusters, classes, restarts, max_iters, the rows and their dimensions must be positive" % op)
+        if k > H.KMEANS_MAX_K or classes > H.PROBE_MAX_CLASSES or R > H.KMEANS_MAX_RESTARTS or iters > H.KMEANS_MAX_ITERS \
+                or Z > H.PROBE_MAX_Z or M > H.PROBE_MAX_ROWS:
+            raise NotImplementedError(
+                "%s: %d clusters, %d classes, %d restarts, %d iterations, %d dimensions, %d rows: the kernel holds %d, %d, %d, %d, "
+                "%d and %d" % (op, k, classes, R, iters, Z, M, H.KMEANS_MAX_K, H.PROBE_MAX_CLASSES, H.KMEANS_MAX_RESTARTS,
+                               H.KMEANS_MAX_ITERS, H.PROBE_MAX_Z, H.PROBE_MAX_ROWS))
+        nbytes = H.lib().air_latent_kmeans_workspace_bytes(M, Z, k, R)
+        if nbytes < 0:
+            H.check(int(nbytes), "air_latent_kmeans_workspace_bytes")
+        self.op, self.device, self.M, self.Z, self.k, self.classes, self.restarts, self.max_iters = op, dev, M, Z, k, classes, R, iters
+        self.seed, self.nbytes, self.per_row = int(seed) & 0xFFFFFFFFFFFFFFFF, int(nbytes), bool(per_row)
+
+    def allocate(self):
+        dev, M, k = self.device, self.M, self.k
+        self.counts = torch.zeros(H.KMEANS_COUNTS + 2 * k + k * self.classes, dtype=torch.int64, device=dev)
+        self.assignment = torch.full((M,), -1, dtype=torch.int32, device=dev)
+        self.row_d2 = torch.zeros(M, dtype=torch.float64, device=dev) if self.per_row else None
+        self.centroids = torch.full((k, self.Z), float("nan"), dtype=torch.float64, device=dev)
+        self.restart_inertia = torch.full((self.restarts,), float("nan"), dtype=torch.float64, device=dev)
+        self.restart_iters = torch.zeros(self.restarts, dtype=torch.int32, device=dev)
+        self.workspace = torch.empty(self.nbytes // 8, dtype=torch.float64, device=dev)
+        self._nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        self._zero = torch.zeros((), dtype=torch.float64, device=dev)
+        return self
+
+    def run(self, latents, labels=None, rows=None):
+        """one air_latent_kmeans call on the current stream; labels: None clusters without scoring; rows: a device int32
+        tensor whose first element says how many rows are in use, or None for all M"""
+        a = H.LatentKmeans(H.ptr(latents), H.ptr(labels), H.ptr(rows), H.ptr(self.assignment), H.ptr(self.row_d2),
+                           H.ptr(self.centroids), H.ptr(self.restart_inertia), H.ptr(self.restart_iters), H.ptr(self.counts),
+                           self.M, self.Z, self.k, self.classes, self.restarts, self.max_iters, self.seed)
+        H.launch("air_latent_kmeans", self.device, C.byref(a), H.ptr(self.workspace))
+
+    def table(self):
+        """int64 [k, classes] view of the counts: rows the cluster, columns the class"""
+        return self.counts[H.KMEANS_COUNTS + 2 * self.k:].view(self.k, self.classes)
+
+    def values(self):
+        """float64 [6] on the device in CLUSTER_NAMES order, fp64 torch ops over the integer counts; never blocks"""
+        c, nan = self.counts, self._nan
+        t = self.table().double()
+        n = t.sum()
+        pairs = lambda v: (v * (v - 1.0) / 2.0).sum()            # noqa: E731  (integers below 2^53: exact)
+        rows_, cols = t.sum(dim=1), t.sum(dim=0)
+        I, A, B, N = pairs(t), pairs(rows_), pairs(cols), n * (n - 1.0) / 2.0
+        E = torch.where(N == 0, nan, A * B / N)
+        den = (A + B) / 2.0 - E
+        ari = torch.where(den == 0, nan, (I - E) / den)
+        plogp = lambda v: torch.where(v > 0, (v / n) * torch.log(v / n), self._zero).sum()      # noqa: E731
+        hc, hl, hcl = -plogp(rows_), -plogp(cols), -plogp(t.reshape(-1))
+        nmi = torch.where((hc + hl == 0) | (n == 0), nan, 2.0 * (hc + hl - hcl) / (hc + hl))
+        ari = torch.where(n == 0, nan, ari)
+        labelled, valid = c[H.KMEANS_LABELLED].double(), c[H.KMEANS_VALID].double()
+        inertia = self.restart_inertia.index_select(0, c[H.KMEANS_BEST:H.KMEANS_BEST + 1])[0]
+        num = torch.stack((c[H.KMEANS_CORRECT].double(), ari, nmi, inertia, c[H.KMEANS_LIVE].double(), labelled))
+        one = torch.ones_like(valid)
+        den = torch.stack((labelled, one, one, valid, one, one))
+        return torch.where(den == 0, nan, num / den)
+
+    def summary(self):
+        """the values, the counts, the table, sizes, majority, centroids and every restart's inertia and iterations as a dict
+        of host values -- synchronises"""
+        values, counts, k, n = self.values().cpu().tolist(), self.counts.cpu().numpy(), self.k, self.classes
+        at = H.KMEANS_COUNTS
+        table = counts[at + 2 * k:].reshape(k, n).copy()
+        out = dict(zip(CLUSTER_NAMES, values))
+        out.update(rows=int(counts[H.KMEANS_ROWS]), valid=int(counts[H.KMEANS_VALID]), labelled=int(counts[H.KMEANS_LABELLED]),
+                   correct=int(counts[H.KMEANS_CORRECT]), live=int(counts[H.KMEANS_LIVE]), best=int(counts[H.KMEANS_BEST]),
+                   iters=int(counts[H.KMEANS_ITERS]), converged=bool(counts[H.KMEANS_CONVERGED]),
+                   restarts_converged=int(counts[H.KMEANS_RESTARTS_CONVERGED]), clusters=k, classes=n, restarts=self.restarts,
+                   max_iters=self.max_iters, seed=self.seed, table=table, confusion=table,
+                   sizes=counts[at:at + k].copy(), majority=counts[at + k:at + 2 * k].copy(),
+                   centroids=self.centroids.cpu().numpy(), assignment=self.assignment.cpu().numpy(),
+                   restart_inertia=self.restart_inertia.cpu().numpy(), restart_iters=self.restart_iters.cpu().numpy())
+        return out
+
+
+class LatentClusters(_LatentStore):
+    """Do digit classes emerge in the what-codes ON THEIR OWN?  The store of LatentProbe (the posterior means of the matched
+    digits), clustered without their labels by air_latent_kmeans (include/air_hip.h has the semantics: exact k-means, fp64 in
+    a fixed order, `restarts` seeded starts, the lowest inertia wins), then every cluster mapped to its majority class.
+
+        clu = LatentClusters(test_model, max_gt_digits=2)
+        test_model.forward()
+        clu.update(gt_count, gt_positions, gt_boxes, gt_labels)     # LatentProbe's: one air_embed_collect call
+        clu.score()                                                 # one air_latent_kmeans call over the rows collected so far
+        clu.values()                                                # float64 [6] on the device, names() order
+
+    accuracy = CORRECT / LABELLED (clustering accuracy, or purity: the rows that carry their cluster's majority class),
+    ari = the adjusted Rand index of the cluster x class table, (I - E) / ((A + B) / 2 - E) over its pair counts,
+    nmi = 2 I(c; l) / (H(c) + H(l)), inertia = the best restart's, per valid row, live_clusters and scored (the labelled
+    rows) as counted; a zero denominator gives NaN.  Derived on the device in fp64 from the integer counts; nothing blocks but
+    result().  ``centroids`` [clusters, Z] float64 are what-codes: AIRModel.decode draws what each cluster looks like.
+    per_row=True keeps ``row_d2`` [capacity] of the last score() beside ``assignment`` [capacity]."""
+    NAMES = reported = CLUSTER_NAMES
+    prefix, group = "clu_", "clusters/"
+    nan_in_events = False
+
+    def __init__(self, model, max_gt_digits, classes=10, clusters=None, restarts=8, max_iters=50, seed=0, capacity=None,
+                 max_distance=0.2, per_row=False):
+        super().__init__(model, max_gt_digits)
+        capacity = self._store_sizes(capacity, max_distance)
+        self.buffers = _KMeansBuffers("LatentClusters", None, capacity, self.Z, classes if clusters is None else clusters, classes,
+                                      restarts, max_iters, seed, per_row)
+        self.buffers.device = self._store_allocate()
+        b = self.buffers.allocate()
+        self.clusters, self.classes, self.restarts, self.max_iters, self.seed = b.k, b.classes, b.restarts, b.max_iters, b.seed
+        self.counts, self.assignment, self.row_d2, self.centroids = b.counts, b.assignment, b.row_d2, b.centroids
+        self.restart_inertia, self.restart_iters = b.restart_inertia, b.restart_iters
+
+    def score(self):
+        """One air_latent_kmeans call over the rows collected so far (the device cursor says how many: no host read)"""
+        H.require_device(self.latents, "the store", "LatentClusters.score", capture_too=True)
+        self.buffers.run(self.latents, self.labels, self.counters[H.EMBED_MATCHED:])
+
+    def values(self, out=None):
+        """float64 [len(names())] on the device, from the counts of the last score() as they stand on the current stream;
+        never blocks"""
+        v = self.buffers.values()
+        if out is None:
+            return v
+        out.copy_(v)
+        return out
+
+    def table(self):
+        """int64 [clusters, classes] view of the counts: rows the cluster, columns the true class"""
+        return self.buffers.table()
+
+    def result(self):
+        """the values as a dict of floats, the totals, the cluster x class table (also under "confusion"), sizes, majority,
+        centroids, every restart's inertia and iterations and the converged flags as numpy -- synchronises"""
+        out = self.buffers.summary()
+        out.update(self._collected())
         return out
 
 

@@ -3,14 +3,17 @@ found to the ground truth and writes what TensorBoard's embedding projector open
 the latents as variable `air_mnist`, an event file, projector_config.pbtxt).
 
   python embeddings.py --model air_results/models/air-model-60000.pt [--data multi_mnist_data/test.tfrecords]
-                       [--out ./embeddings] [--max-distance 0.2] [--precision fp32] [--batch-size 64] [--knn 5]
+                       [--out ./embeddings] [--max-distance 0.2] [--precision fp32] [--batch-size 64] [--knn 5] [--kmeans 10]
 
   tensorboard --logdir ./embeddings
 
 The match, the gathering of latents and windows and the sprite sheet run on the device (air/embeddings.py).  The reference
 also reads MNIST, only to print a line; that is left out.  --knn K scores what the projector shows as numbers
 (air.embeddings.probe: leave-one-out K-nearest-neighbour digit accuracy, confusion matrix, active units) and writes
-latent_probe.json beside the projector files.
+latent_probe.json beside the projector files.  --kmeans K asks whether the classes emerge without labels
+(air.embeddings.cluster: exact K-means over the matched latents, every cluster mapped to its majority class): it prints
+clustering accuracy, adjusted Rand index and NMI, and writes clusters.npz and cluster_sprites.png, the decoder's window of
+every centroid that has members.
 """
 import argparse
 import os
@@ -39,9 +42,19 @@ def main():
     ap.add_argument("--knn", type=int, default=0, metavar="K",
                     help="also score the matched latents: leave-one-out K-nearest-neighbour digit accuracy, its confusion "
                          "matrix and the active units (air.embeddings.probe), printed and written to latent_probe.json")
+    ap.add_argument("--kmeans", type=int, default=0, metavar="K",
+                    help="also cluster the matched latents without their labels: exact K-means, clustering accuracy, adjusted "
+                         "Rand index and NMI against the digit labels (air.embeddings.cluster), printed and written to "
+                         "clusters.npz, with cluster_sprites.png: what the decoder draws for every centroid")
+    ap.add_argument("--kmeans-restarts", type=int, default=8, metavar="R", help="--kmeans: the seeded starts (1 .. 32)")
+    ap.add_argument("--kmeans-seed", type=int, default=0, help="--kmeans: the seed of the starts")
     args = ap.parse_args()
     if args.knn < 0 or args.knn > 16:
         ap.error("--knn must lie in [1, 16] (0: no probe)")
+    if args.kmeans < 0 or args.kmeans > 64:
+        ap.error("--kmeans must lie in [1, 64] (0: no clustering)")
+    if args.kmeans and not 1 <= args.kmeans_restarts <= 32:
+        ap.error("--kmeans-restarts must lie in [1, 32]")
 
     out = os.path.abspath(args.out)
     shutil.rmtree(out, ignore_errors=True)                                          # embeddings.py:145-146
@@ -91,8 +104,22 @@ def main():
         print("Confusion matrix (rows: true digit, columns: predicted):")
         print(probed["confusion"])
         print()
+    clustered = None
+    if args.kmeans:
+        clustered = embeddings.cluster(result.latents, result.labels, clusters=args.kmeans, classes=max(10, max(label_dic) + 1),
+                                       restarts=args.kmeans_restarts, seed=args.kmeans_seed)
+        print("Latent clusters ({0}-means, {1} restarts, best {2} after {3} iterations{4}, over {5} matched digits):".format(
+            args.kmeans, args.kmeans_restarts, clustered["best"], clustered["iters"],
+            "" if clustered["converged"] else ", not converged", clustered["labelled"]))
+        print("Clustering accuracy: {0:.4f}  ARI: {1:.4f}  NMI: {2:.4f}  live clusters: {3}".format(
+            clustered["accuracy"], clustered["ari"], clustered["nmi"], clustered["live"]))
+        print("Cluster table (rows: cluster, columns: true digit):")
+        print(clustered["table"])
+        print()
     print("Saving embeddings...")
     embeddings.write_projector(out, result)
+    if clustered is not None:
+        embeddings.write_clusters(out, clustered, air_model)
     if probed is not None:
         embeddings.write_probe(out, probed)
 

@@ -260,7 +260,7 @@ class TensorBoardWriter:
         self.events.add_scalars(step, zip(self.tags.numeric, values[2:]))
 
     def instrument(self, step, instrument, values):
-        """--localization, --segmentation, --latent-probe: the reported values of the evaluation at `step`, under the
+        """--localization, --segmentation, --latent-probe, --latent-clusters: the reported values of the evaluation at `step`, under the
         instrument's group (SummaryWriter's on_values hook); whether a NaN is written is the instrument's to say"""
         self.events.add_scalars(step, [(instrument.group + k, v) for k, v in zip(instrument.reported, values)
                                        if v == v or instrument.nan_in_events])
@@ -302,7 +302,7 @@ class TensorBoardWriter:
 
 
 def instruments(args, model, test):
-    """--localization, --segmentation, --latent-probe -> [(the air.metrics instrument of `model`, its ground truth out of the
+    """--localization, --segmentation, --latent-probe, --latent-clusters -> [(the air.metrics instrument of `model`, its ground truth out of the
     test-set record on the device, headline)], in that order; headline(result()) -> what the run's last line about the
     instrument says in front of and behind its reported values, and the title of its confusion matrix (None: it has none)"""
     from air import metrics
@@ -321,6 +321,14 @@ def instruments(args, model, test):
             "latent probe, {}-NN over {} matched digits: ".format(lat.k, res["scored"]),
             "  (the store overflowed)" if res["overflow"] else "",
             "digit confusion (rows: true class 0..{}, columns: predicted):".format(lat.classes - 1))))
+    if args.latent_clusters:
+        clu = metrics.LatentClusters(model, int(test["labels"].shape[1]), clusters=args.cluster_count,
+                                     restarts=args.cluster_restarts, seed=args.seed)
+        out.append((clu, (test["digits"], test["positions"], test["boxes"], test["labels"]), lambda res: (
+            "latent clusters, {}-means ({} restarts, best {} after {} iterations{}) over {} matched digits: ".format(
+                clu.clusters, clu.restarts, res["best"], res["iters"], "" if res["converged"] else ", not converged", res["scored"]),
+            "  (the store overflowed)" if res["overflow"] else "",
+            "cluster table (rows: cluster 0..{}, columns: true class 0..{}):".format(clu.clusters - 1, clu.classes - 1))))
     if args.importance_samples:                 # LAST: its sampled passes replace the buffers the others read
         iw = metrics.ImportanceBound(model, args.importance_samples, seed=args.seed)
         out.append((iw, (test["digits"],), lambda res: (
@@ -411,6 +419,15 @@ def main():
                              "units): the rows of summary/scalars.jsonl gain lat_* keys, --tensorboard gains latents/* scalars, "
                              "and the run ends with the confusion matrix of the digits.  Needs the boxes and labels of the test set")
     parser.add_argument("--latent-k", type=int, default=5, help="--latent-probe: the neighbours that vote (1 .. 16)")
+    parser.add_argument("--latent-clusters", action="store_true",
+                        help="cluster the what-codes of the test model at every evaluation (air.metrics.LatentClusters: exact "
+                             "k-means over the latent means of the matched digits, every cluster mapped to its majority class: "
+                             "clustering accuracy, adjusted Rand index, NMI): the rows of summary/scalars.jsonl gain clu_* keys, "
+                             "--tensorboard gains clusters/* scalars, and the run ends with the cluster x class table.  Needs "
+                             "the boxes and labels of the test set, as --latent-probe does")
+    parser.add_argument("--cluster-count", type=int, default=10, metavar="K", help="--latent-clusters: the clusters (1 .. 64)")
+    parser.add_argument("--cluster-restarts", type=int, default=8, metavar="R",
+                        help="--latent-clusters: the seeded starts of which the lowest inertia wins (1 .. 32)")
     parser.add_argument("--importance-samples", type=int, default=0, metavar="K",
                         help="score every evaluation by K passes of the test model on fresh noise as well (air.metrics."
                              "ImportanceBound; 0: off, at most 64): the K-sample importance-weighted bound on the negative "
@@ -422,6 +439,15 @@ def main():
         parser.error("--importance-samples must lie in 0 .. 64")
     if args.latent_probe and not 1 <= args.latent_k <= 16:
         parser.error("--latent-k must lie in [1, 16]")
+    if args.latent_clusters and not 1 <= args.cluster_count <= 64:
+        parser.error("--cluster-count must lie in [1, 64]")
+    if args.latent_clusters and not 1 <= args.cluster_restarts <= 32:
+        parser.error("--cluster-restarts must lie in [1, 32]")
+    if args.latent_clusters and args.glyph_style != "mnist-like" and cache_without(("positions", "boxes", "labels")):
+        parser.error("--latent-clusters needs the ground-truth boxes and digit labels of the test set, and %s holds none (no "
+                     "'positions' / 'boxes' / 'labels'): regenerate the cache with multi_mnist.py (or multi_mnist.py --device N), "
+                     "which writes them, or remove it to have the data set generated in memory"
+                     % cache_without(("positions", "boxes", "labels")))
     if args.latent_probe and args.glyph_style != "mnist-like" and cache_without(("positions", "boxes", "labels")):
         parser.error("--latent-probe needs the ground-truth boxes and digit labels of the test set, and %s holds none (no "
                      "'positions' / 'boxes' / 'labels'): regenerate the cache with multi_mnist.py (or multi_mnist.py --device N), "
@@ -465,8 +491,8 @@ def main():
         os.makedirs(d)
 
     dev = torch.device("cuda", 0)
-    want = (("positions", "boxes") if args.localization or args.latent_probe else ()) + \
-        (("labels",) if args.latent_probe else ()) + (("masks",) if args.segmentation else ())
+    want = (("positions", "boxes") if args.localization or args.latent_probe or args.latent_clusters else ()) + \
+        (("labels",) if args.latent_probe or args.latent_clusters else ()) + (("masks",) if args.segmentation else ())
     print("Creating input pipeline...")
     if mnist_like:                                                   # no host generator: the test set is device work too
         test = device_test_set(dev, args.jitter_bank, args.seed, args.online_max_digits, args.canvas_margin, args.digit_gap,
